@@ -7,7 +7,12 @@ parameters, flat-buffer gradient all-reduce (N>1), fused clip + AdamW.  Syntheti
 named shape, random-init weights of the named architecture (no network for checkpoints), all resident in HBM before
 the timed region.  Prints ONE JSON line on rank 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|cfg5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, unit, higher_is_better, dtype, ms_per_step, ...).
+`--full` adds everything else the benchmark measures: the per-kernel table and roofline objects (live HIP events in the timed steps), socket
+energy, the geometry-scorer block, the CPU baseline, the secondary configurations (cfg2 default shape, 1 GPU) and the collective A/B (N > 1).
+`--dump-outputs DIR` writes what the last timed step computed to DIR/<name>.npy (rank 0; see dump_outputs) before the line is printed.
 
 cfg5 = BASELINE.json configs[4] (Wan2.2-TI2V-5B, 81f x 704x1280, fp8 feed-forward) is a separate bench line with its own metric name; the
 default (and what the driver runs) is cfg2, the configuration the headline metric is quoted on.
@@ -494,6 +499,49 @@ def cpu_baseline_scorer(pc, colors, K, E, H, W, T):
     return (time.perf_counter() - t0) * 1e3 * T
 
 
+DUMP_SAMPLE = 4096                  # adapter / optimizer-state elements sampled per LoRA tensor by dump_outputs
+DUMP_MAX_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(out_dir, engine, logs):
+    """What the last timed step handed its caller, as DIR/<name>.npy (float64 scalars, float32 tensors), so that two builds can be compared output
+    for output: the logged scalars of the step (loss, reward margin / accuracy, their rank means), the global gradient norm the clip used, and the
+    LoRA adapters with AdamW's two moments after the update.  The adapters (66 M fp32 values for cfg2) are sampled: DUMP_SAMPLE elements per
+    tensor at indices drawn from a generator seeded by the tensor's name, tensors in name order -- the same elements on every run and build."""
+    import zlib
+
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    opt = engine.opt
+    where = {id(p): o for p, o in zip(opt.flat.params, opt.flat.offsets)}
+    named = sorted((n, p) for n, p in engine.trainer.transformer.named_parameters() if id(p) in where)
+    if len(named) != len(where):
+        raise RuntimeError(f"dump_outputs: {len(where)} tensors in the optimizer's flat buffer, {len(named)} of them found by name")
+    idx = []
+    for n, p in named:
+        k = min(DUMP_SAMPLE, p.numel())
+        g = torch.Generator().manual_seed(zlib.crc32(n.encode()))
+        idx.append(where[id(p)] + torch.randperm(p.numel(), generator=g)[:k].sort().values)
+    idx = torch.cat(idx).to(opt.flat.flat.device)
+    f64 = lambda t: t.detach().double().reshape(-1).cpu().numpy()
+    arrays = {
+        "loss": f64(logs["train/loss"]),
+        "reward_margin": f64(logs["train/reward_margin"]),
+        "reward_accuracy": f64(logs["train/reward_accuracy"]),
+        "rank_mean_loss_margin_accuracy": f64(logs["sync"]),
+        "grad_norm": f64(opt.total_norm),
+        "lora_params": opt.flat.flat[idx].float().cpu().numpy(),
+        "adamw_exp_avg": opt.exp_avg[idx].float().cpu().numpy(),
+        "adamw_exp_avg_sq": opt.exp_avg_sq[idx].float().cpu().numpy(),
+    }
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise RuntimeError(f"dump_outputs: {total} bytes > {DUMP_MAX_BYTES}")
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
+
+
 OTHER_CONFIGS = ("cfg3", "cfg3_batch2", "cfg4", "cfg5")
 
 
@@ -502,7 +550,7 @@ CHILD_CPUS = 16      # host threads fenced off for the secondary-config child pr
 
 def split_host_cpus():
     """(cpus for the CPU leg, cpus for the child benches): the children get the CHILD_CPUS highest-numbered hardware threads this process may run on, the
-    CPU leg everything else -- the two overlap in TIME (so that the default run still ends within minutes) but never share a core.  On a host too small
+    CPU leg everything else -- the two overlap in TIME (so that a --full run still ends within minutes) but never share a core.  On a host too small
     to split (<= 2 x CHILD_CPUS threads) both get everything and the report says so."""
     try:
         cpus = sorted(os.sched_getaffinity(0))
@@ -542,7 +590,7 @@ def run_other_configs(steps=3, warmup=1, timeout_s=420, cpus=None):
             name_arg, extra = "cfg3", ["--pairs", "2"]
         else:
             name_arg = name
-        cmd = [sys.executable, os.path.abspath(__file__), "--config", name_arg, "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline",
+        cmd = [sys.executable, os.path.abspath(__file__), "--config", name_arg, "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline",
                "--no-other-configs", *extra]
         t0 = time.perf_counter()
         try:
@@ -637,10 +685,10 @@ def main_wan(args, C, world, rank, dev, force_dist):
         engine.micro_step(batch)
     engine.flush()
     engine.opt.comm_report()          # drop the warm-up's exchange events: `comm` covers the timed steps only
-    if rank == 0 and not args.no_kernel_timer:
+    if rank == 0 and args.full and not args.no_kernel_timer:
         ops.TIMER = ops.KernelTimer(full_steps=TIMER_FULL_STEPS, always=TIMER_ALWAYS)
     barrier()
-    e0 = read_joules(dev.index or 0) if rank == 0 else None
+    e0 = read_joules(dev.index or 0) if rank == 0 and args.full else None
     t0 = time.perf_counter()
     logs = None
     for _ in range(args.steps):
@@ -650,12 +698,14 @@ def main_wan(args, C, world, rank, dev, force_dist):
     logs.update(engine.flush())
     barrier()
     dt_local = time.perf_counter() - t0
-    e1 = read_joules(dev.index or 0) if rank == 0 else None
+    e1 = read_joules(dev.index or 0) if rank == 0 and args.full else None
     dt = dt_local
     tt = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1 or force_dist:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine, logs)
     drep = dist_report(engine, dt_local, args.steps, dev, world, force_dist)
     if getattr(args, "preflight", None):
         drep["preflight"] = args.preflight
@@ -693,7 +743,7 @@ def main_wan(args, C, world, rank, dev, force_dist):
                                 "estimated_score_error_log2_max": max(est) if est else None}
         out.update(drep)
         add_kernel_report(out, ops, args.steps, ms, use_pmc=named)
-        if not ckpt:
+        if args.full and not ckpt:
             out["energy"] = energy_report(e0, e1, dt_local, args.steps, F_step)
         print(json.dumps(out), flush=True)
     if world > 1 or force_dist:
@@ -724,15 +774,20 @@ def main():
     ap.add_argument("--no-fp8-attn", action="store_true", help="cfg5 only: keep the e4m3 feed-forward but run the self-attention forward in bf16")
     ap.add_argument("--fp8-attn-auto", action="store_true", help="cfg5 only: enable_fp8(attention='auto') -- every self-attention layer decides from its first call's score range "
                     "whether e4m3 scores are accurate enough (ops.F8AttnPolicy); NOT the BASELINE line (which pins the e4m3 kernel)")
+    ap.add_argument("--full", action="store_true", help="also measure everything besides the headline: per-kernel table and roofline, energy, scorer block, CPU "
+                    "baseline, secondary configurations, collective A/B (the --no-* switches below refine this)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (bench.dump_outputs)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-timer", action="store_true")
     ap.add_argument("--no-tuned-gemms", action="store_true", help="run the vendor GEMMs on hipBLASLt's default heuristic instead of the solutions of videogpa_amd/tuned/ (the A/B of tools/gemm_tune.py)")
     ap.add_argument("--no-collective-ab", action="store_true", help="N > 1: skip the second short timed region that runs the other gradient-exchange form (all_reduce <-> rs_ag)")
     ap.add_argument("--no-scorer", action="store_true", help="skip the geometry-scorer block (a few milliseconds of GPU work after the headline's timed region)")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run (1 GPU, cfg2, no debug flags) also measures cfg3 / cfg4 / cfg5 for 3 steps each "
+    ap.add_argument("--no-other-configs", action="store_true", help="--full run (1 GPU, cfg2, no debug flags) also measures cfg3 / cfg4 / cfg5 for 3 steps each "
                     "and attaches them as `other_configs`; this switches that off")
     args = ap.parse_args()
-    if os.environ.get("VGPA_BENCH_CPUS"):        # a secondary-config child of the default run: stay off the cores the parent's CPU leg is being timed on
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if os.environ.get("VGPA_BENCH_CPUS"):        # a secondary-config child of a --full run: stay off the cores the parent's CPU leg is being timed on
         try:
             pin_all_threads({int(c) for c in os.environ["VGPA_BENCH_CPUS"].split(",")})
         except (AttributeError, OSError, ValueError):
@@ -826,10 +881,10 @@ def main():
         engine.micro_step(batch)
     engine.flush()
     engine.opt.comm_report()          # drop the warm-up's exchange events: `comm` covers the timed steps only
-    if rank == 0 and not args.no_kernel_timer:
+    if rank == 0 and args.full and not args.no_kernel_timer:
         ops.TIMER = ops.KernelTimer(full_steps=TIMER_FULL_STEPS, always=TIMER_ALWAYS)
     barrier()
-    e0 = read_joules(dev.index or 0) if rank == 0 else None
+    e0 = read_joules(dev.index or 0) if rank == 0 and args.full else None
     t0 = time.perf_counter()
     logs = None
     for _ in range(args.steps):
@@ -839,14 +894,16 @@ def main():
     logs.update(engine.flush())       # the last optimizer step (applied one micro-step late when the all-reduce is overlapped) is inside the timed region
     barrier()
     dt_local = time.perf_counter() - t0
-    e1 = read_joules(dev.index or 0) if rank == 0 else None
+    e1 = read_joules(dev.index or 0) if rank == 0 and args.full else None
     dt = dt_local
     tt = torch.tensor([dt], dtype=torch.float64, device=dev)
     if world > 1 or force_dist:
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
     dt = float(tt.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, engine, logs)
     drep = dist_report(engine, dt_local, args.steps, dev, world, force_dist)
-    if (world > 1 or force_dist) and not args.no_collective_ab:
+    if args.full and (world > 1 or force_dist) and not args.no_collective_ab:
         ab = collective_ab(engine, batch, min(args.steps, 3), world, force_dist, dev, barrier)
         if drep.get("comm"):
             drep["collective_ab"] = dict({drep["comm"]["collective"]: {"steps": args.steps, "ms_per_step": dt / args.steps * 1e3, "comm": drep["comm"]}}, **ab)
@@ -880,12 +937,12 @@ def main():
         }
         out.update(drep)
         add_kernel_report(out, ops, args.steps, ms, use_pmc=named and args.config in ("cfg2", "cfg3"))
-        if not ckpt:      # with block recompute the executed count would also carry the recomputed forwards
+        if args.full and not ckpt:      # with block recompute the executed count would also carry the recomputed forwards
             out["energy"] = energy_report(e0, e1, dt_local, args.steps, F_step, F_step + P_ * 6.0 * args.layers * 2 * cfg_kw["num_attention_heads"] * 64.0 * S * S)
-        if world == 1 and not force_dist and named and args.config == "cfg2" and not args.no_scorer:
+        if args.full and world == 1 and not force_dist and named and args.config == "cfg2" and not args.no_scorer:
             out["scorer"] = scorer_report(dev, with_cpu=not args.no_cpu_baseline)
         others = None
-        if world == 1 and not force_dist and named and args.config == "cfg2" and not args.no_other_configs:
+        if args.full and world == 1 and not force_dist and named and args.config == "cfg2" and not args.no_other_configs:
             # the secondary configurations run on the (now idle) GPU in child processes WHILE the host cores time the CPU leg: the timed region of the
             # headline is over, this process's device memory is released first, and the two legs are fenced onto DISJOINT host cores (split_host_cpus):
             # the children (each builds a 5 B-parameter model on the host before its timed steps) cannot slow the CPU baseline down
@@ -900,7 +957,7 @@ def main():
             others.start()
             if leg_cpus and not args.no_cpu_baseline:
                 pin_all_threads(leg_cpus)                  # this process is done with the GPU work that needed its launch threads
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(F_step)
             if others is not None:
                 out["cpu_baseline"]["legs_overlapped"] = True

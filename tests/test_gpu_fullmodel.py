@@ -246,7 +246,7 @@ def test_bench_line_under_a_forced_process_group_carries_the_comm_attribution():
             port = sk.getsockname()[1]
         env = dict(os.environ, VGPA_FORCE_DIST="1", VGPA_DP_COLLECTIVE=coll, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--layers", "2", "--frames", "3", "--height", "16", "--width", "16", "--steps", "3",
-                            "--warmup", "1", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=600, env=env)
+                            "--warmup", "1", "--full", "--no-cpu-baseline", "--no-other-configs"], capture_output=True, text=True, timeout=600, env=env)
         assert r.returncode == 0, r.stderr[-2000:]
         j = json.loads(next(ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{")))
         assert j["ranks_seen"] == 1 and j["n_gpus"] == 1 and len(j["ms_per_step_by_rank"]) == 1
@@ -260,6 +260,40 @@ def test_bench_line_under_a_forced_process_group_carries_the_comm_attribution():
         assert len(pre) == 1 and pre[0]["rank"] == 0 and pre[0]["free_gb"] > 1 and pre[0]["rccl_version"][0].isdigit()
         assert "preflight: rank 0" in r.stderr
         print({coll: c, "ab": {k: v["ms_per_step"] for k, v in ab.items()}})
+
+
+def test_bench_plain_line_is_lean_and_dumps_the_same_outputs_as_the_full_run(tmp_path):
+    """`bench.py` without --full times its steps and prints the headline fields only (no per-kernel events, energy or CPU leg); with --full the
+    per-kernel table is back.  Both write the last timed step's outputs under --dump-outputs, and on the same arguments (the same seeded inputs)
+    they agree: the live kernel timing of --full does not change what the step computes."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    shape = ["--layers", "2", "--frames", "3", "--height", "16", "--width", "16", "--steps", "2", "--warmup", "1"]
+    lines, dumps = {}, {}
+    for kind, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-other-configs"])):
+        d = str(tmp_path / kind)
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), *shape, *extra, "--dump-outputs", d], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines[kind] = json.loads(next(ln for ln in reversed(r.stdout.splitlines()) if ln.startswith("{")))
+        dumps[kind] = {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    p, f = lines["plain"], lines["full"]
+    for j in (p, f):
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(j) and j["steps"] == 2 and j["warmup"] == 1
+        assert j["ms_per_step"] > 0 and abs(j["value"] - 1e3 / j["ms_per_step"]) <= 1e-9 * j["value"]
+    assert not {"kernels", "roofline", "energy", "cpu_baseline", "scorer", "other_configs"} & set(p)
+    assert "kernels" in f and "roofline" in f and "energy" in f
+    a, b = dumps["plain"], dumps["full"]
+    assert set(a) == set(b) and {"loss", "grad_norm", "lora_params", "adamw_exp_avg", "adamw_exp_avg_sq"} <= set(a)
+    assert sum(x.nbytes for x in a.values()) <= 64 * 2 ** 20
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].shape == b[k].shape and np.isfinite(a[k]).all(), k
+        assert np.linalg.norm(a[k] - b[k]) <= 1e-3 * np.linalg.norm(a[k]), (k, float(np.abs(a[k] - b[k]).max()))
+    assert abs(float(a["loss"][0]) - p["loss"]) <= 1e-6 * abs(p["loss"])
+    print({k: lines[k]["ms_per_step"] for k in lines})
 
 
 @pytest.mark.parametrize("recompute,mem_gb", [(True, 80), (False, 230)])

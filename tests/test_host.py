@@ -359,3 +359,36 @@ def test_tuned_gemm_file_is_wired_but_off_without_a_gpu(monkeypatch):
     monkeypatch.setenv("PYTORCH_TUNABLEOP_ENABLED", "0")
     st = ops.use_tuned_gemms(True)
     assert "left as is" in st.get("note", "")
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_of_the_step_results(tmp_path):
+    """bench.py::dump_outputs (--dump-outputs DIR): one .npy per output of the last step, float32 / float64 only, under 64 MB; the adapter and
+    AdamW-moment samples are the same elements on every call (indices seeded by the tensor name) and line up with the parameters they came from."""
+    import importlib.util
+
+    import numpy as np
+    from videogpa_amd.trainer import DPOEngine
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    eng = DPOEngine(_tiny_trainer())
+    opt = eng.opt
+    g = torch.Generator().manual_seed(3)
+    opt.flat.flat.copy_(torch.randn(opt.flat.flat.shape, generator=g))
+    opt.exp_avg.copy_(torch.randn(opt.exp_avg.shape, generator=g))
+    opt.exp_avg_sq.copy_(torch.rand(opt.exp_avg_sq.shape, generator=g))
+    opt.total_norm.fill_(0.25)
+    logs = {"train/loss": torch.tensor(0.69), "train/reward_margin": torch.tensor([0.1]), "train/reward_accuracy": torch.tensor(1.0),
+            "sync": torch.tensor([0.69, 0.1, 1.0])}
+    names = bench.dump_outputs(str(tmp_path / "a"), eng, logs)
+    bench.dump_outputs(str(tmp_path / "b"), eng, logs)
+    assert sorted(f[:-4] for f in os.listdir(tmp_path / "a")) == names
+    a = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    b = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    assert all(a[n].dtype in (np.float32, np.float64) and np.array_equal(a[n], b[n]) for n in names)
+    assert sum(x.nbytes for x in a.values()) <= bench.DUMP_MAX_BYTES
+    assert a["grad_norm"].tolist() == [0.25] and abs(a["loss"][0] - 0.69) < 1e-6 and a["rank_mean_loss_margin_accuracy"].shape == (3,)
+    per = [min(bench.DUMP_SAMPLE, p.numel()) for p in opt.flat.params]
+    assert a["lora_params"].shape == a["adamw_exp_avg"].shape == a["adamw_exp_avg_sq"].shape == (sum(per),)
+    vals = set(opt.flat.flat.tolist())
+    assert all(v in vals for v in a["lora_params"].tolist()) and len(set(a["lora_params"].tolist())) == sum(per)     # distinct elements of the adapters

@@ -4,8 +4,8 @@ cd ${GRAFT_REPO_ROOT:-/root/repo}
 export GRAFT_REPO_ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
 timeout 900 python -m pytest tests/test_gpu_wan_kernels.py tests/test_gpu_wan_cfg1.py tests/test_gpu_wan.py -m gpu -q -s 2>&1 | cut -c1-500 | tail -50 > $O/r06_b10_tests.log
-timeout 600 python bench.py --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 2.5 > $O/r06_bench_cfg5_trained_like_after.json 2> $O/r06_bench_cfg5_trained_like_after.err
-timeout 600 python bench.py --config cfg5 --steps 3 --warmup 1 > $O/r06_bench_cfg5_after.json 2> $O/r06_bench_cfg5_after.err
+timeout 600 python bench.py --full --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 2.5 > $O/r06_bench_cfg5_trained_like_after.json 2> $O/r06_bench_cfg5_trained_like_after.err
+timeout 600 python bench.py --full --config cfg5 --steps 3 --warmup 1 > $O/r06_bench_cfg5_after.json 2> $O/r06_bench_cfg5_after.err
 for f in $O/r06_bench_cfg5_trained_like_after.json $O/r06_bench_cfg5_after.json; do python - $f <<'PYEOF'
 import json, sys
 try:

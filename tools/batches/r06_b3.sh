@@ -15,8 +15,8 @@ timeout 900 python -m pytest tests/test_gpu_depth.py -x -q -k order_one 2>&1 | t
 timeout 2400 python tools/gemm_tune.py tune --configs cfg2 --fresh > $O/gemm_tune.log 2>&1
 timeout 900 python tools/gemm_tune.py table > $O/gemm_tune_table.txt 2>&1
 for i in 1 2; do
-  timeout 600 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer --no-tuned-gemms > $O/ab_gemm_default_$i.json 2> $O/ab_gemm_default_$i.err
-  timeout 600 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer > $O/ab_gemm_tuned_$i.json 2> $O/ab_gemm_tuned_$i.err
+  timeout 600 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer --no-tuned-gemms > $O/ab_gemm_default_$i.json 2> $O/ab_gemm_default_$i.err
+  timeout 600 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer > $O/ab_gemm_tuned_$i.json 2> $O/ab_gemm_tuned_$i.err
 done
 cp videogpa_amd/tuned/tunableop_gfx950.csv $O/ 2>/dev/null
 tail -3 $O/depthwan_L2.log $O/attn_policy.log $O/kernels_regress.log $O/loss_curve.log $O/depthwan_L30.log $O/depth_rich.log $O/gemm_tune.log

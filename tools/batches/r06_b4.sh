@@ -18,7 +18,7 @@ timeout 900 python tools/gemm_tune.py table --file $O/tunableop_cfg5.csv --json 
 timeout 600 python tools/scorer_bench.py > $O/scorer_bench.log 2>&1
 timeout 1500 bash tools/pmc_fwd_budget.sh > $O/pmc_fwd_budget.log 2>&1
 for i in 1 2; do
-  timeout 600 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer --no-tuned-gemms > $O/ab2_gemm_default_$i.json 2> $O/ab2_gemm_default_$i.err
-  timeout 600 python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer > $O/ab2_gemm_tuned_$i.json 2> $O/ab2_gemm_tuned_$i.err
+  timeout 600 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer --no-tuned-gemms > $O/ab2_gemm_default_$i.json 2> $O/ab2_gemm_default_$i.err
+  timeout 600 python bench.py --full --steps 5 --warmup 1 --no-cpu-baseline --no-other-configs --no-scorer > $O/ab2_gemm_tuned_$i.json 2> $O/ab2_gemm_tuned_$i.err
 done
 for f in attn_policy kernels_regress loss_curve depthwan_L30 fwd_knob_mfsum zbuf_probe scorer_bench; do echo "== $f"; tail -n 4 $O/$f.log | cut -c1-300; done

@@ -3,9 +3,9 @@
 cd ${GRAFT_REPO_ROOT:-/root/repo}
 export GRAFT_REPO_ROOT=${GRAFT_REPO_ROOT:-/root/repo}
 O=gpurun_out
-timeout 600 python bench.py --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 2.5 > $O/r06_bench_cfg5_trained_like.json 2> $O/r06_bench_cfg5_trained_like.err
-timeout 600 python bench.py --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 2.5 --no-fp8-attn > $O/r06_bench_cfg5_trained_like_bf16attn.json 2> $O/r06_bench_cfg5_trained_like_bf16attn.err
-timeout 600 python bench.py --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 4.0 > $O/r06_bench_cfg5_trained_like_g4.json 2> $O/r06_bench_cfg5_trained_like_g4.err
+timeout 600 python bench.py --full --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 2.5 > $O/r06_bench_cfg5_trained_like.json 2> $O/r06_bench_cfg5_trained_like.err
+timeout 600 python bench.py --full --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 2.5 --no-fp8-attn > $O/r06_bench_cfg5_trained_like_bf16attn.json 2> $O/r06_bench_cfg5_trained_like_bf16attn.err
+timeout 600 python bench.py --full --config cfg5 --steps 2 --warmup 1 --weights trained_like --qk-gain 4.0 > $O/r06_bench_cfg5_trained_like_g4.json 2> $O/r06_bench_cfg5_trained_like_g4.err
 for f in $O/r06_bench_cfg5_trained_like*.json; do python - $f <<'PYEOF'
 import json, sys
 try:

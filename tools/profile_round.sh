@@ -11,6 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 # the HEADLINE process only (--no-other-configs --no-scorer: round 5 profiled the default command, whose cfg3 child wrote the first csv `find | head -1` picked up)
 PSTEPS=2; PWARM=1
 timeout 900 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_$tag --output-format csv -- python $R/bench.py --steps $PSTEPS --warmup $PWARM --no-cpu-baseline \
+    --full \
     --no-other-configs --no-scorer > $R/gpurun_out/prof_${tag}_bench.json 2> $R/gpurun_out/prof_$tag.log
 nf=$(find $R/gpurun_out/prof_$tag -name "*kernel_stats.csv" | wc -l)
 [ "$nf" -ne 1 ] && echo "profile_round.sh: expected ONE kernel_stats.csv (one traced process), found $nf" | tee -a $R/gpurun_out/prof_$tag.log
@@ -38,6 +39,7 @@ timeout 300 rocprofv3 --pmc FETCH_SIZE -d $R/gpurun_out/pmc_${tag}_fetch_ew --ou
 timeout 300 rocprofv3 --pmc WRITE_SIZE -d $R/gpurun_out/pmc_${tag}_write_ew --output-format csv -- python $R/tools/ew_bench.py > $R/gpurun_out/pmc_${tag}_write_ew.log 2>&1
 # cfg5 (Wan2.2-TI2V-5B): kernel stats of its bench line, and the same PMC passes over the head_dim-128 attention kernels at the pair-batch shape
 timeout 600 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_${tag}_cfg5 --output-format csv -- python $R/bench.py --config cfg5 --steps 2 --warmup 1 \
+    --full \
     > $R/gpurun_out/prof_${tag}_bench_cfg5.json 2> $R/gpurun_out/prof_${tag}_cfg5.log
 f5=$(find $R/gpurun_out/prof_${tag}_cfg5 -name "*kernel_stats.csv" | head -1)
 [ -n "$f5" ] && cp $f5 $R/gpurun_out/${tag}_bench_cfg5_kernel_stats.csv && python $R/profiles/summarize.py $f5 40 > $R/gpurun_out/${tag}_bench_cfg5_kernel_stats_summary.txt
@@ -55,6 +57,7 @@ find $R/gpurun_out/prof_${tag}_a128 -name "*kernel_trace.csv" -delete
 # socket power / shader clock during the default bench command (the power-limit evidence of DESIGN section 4.2)
 rocm-smi --showpower --showclocks --showmaxpower --json > $R/gpurun_out/${tag}_rocm_smi_idle.json 2>&1
 timeout 300 python $R/tools/power_trace.py --out $R/gpurun_out/power_${tag}.json -- python $R/bench.py --steps 6 --warmup 1 --no-cpu-baseline --no-kernel-timer \
+    --full \
     > $R/gpurun_out/power_${tag}_bench.json 2> $R/gpurun_out/power_${tag}.log
 # the geometry scorer at the reference's scale (10 x 518^2): kernel stats + FETCH / WRITE traffic of project_zbuf / project_resolve / conf_threshold / mvcs / mse
 timeout 300 rocprofv3 --kernel-trace --stats -d $R/gpurun_out/prof_${tag}_scorer --output-format csv -- python $R/tools/scorer_bench.py > $R/gpurun_out/prof_${tag}_scorer.log 2>&1

@@ -392,6 +392,14 @@ int32_t vgpa_frame_metric(const void* gt, int32_t gt_dtype, int32_t gt_layout, i
                           int32_t rep_dtype, int32_t rep_layout, int32_t rep_is_tensor, int64_t T, int64_t C, int64_t H,
                           int64_t W, int64_t H2, int64_t W2, int32_t psnr, float* out, void* workspace, size_t ws_bytes,
                           vgpa_stream_t stream);
+/* SSIMMetric.compute, metrics/mse.py:101-134 = piq.ssim(gt, rep, data_range=1.0) at piq's defaults (11 x 11 Gaussian window, sigma 1.5,
+ * k1 0.01, k2 0.03, average pool by max(1, round_half_even(min(H, W) / 256)) unless downsample == 0).  gt and rep share [T,C,H,W]
+ * (no resize; a pooled side below 11 is an invalid argument); dtype / layout / is_tensor as vgpa_frame_metric.  out_per_frame fp32 [T]
+ * and / or out_mean fp32 [1] (either may be NULL).  Results are run-to-run bit-identical (fixed-order fp64 reduction, no float atomics). */
+size_t vgpa_frame_ssim_workspace_bytes(int64_t T, int64_t C, int64_t H, int64_t W);
+int32_t vgpa_frame_ssim(const void* gt, int32_t gt_dtype, int32_t gt_layout, int32_t gt_is_tensor, const void* rep, int32_t rep_dtype,
+                        int32_t rep_layout, int32_t rep_is_tensor, int64_t T, int64_t C, int64_t H, int64_t W, int32_t downsample,
+                        float* out_per_frame, float* out_mean, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
 /* Input side of LPIPSMetric.compute, metrics/lpips.py:21-63 (the LPIPS network itself is the caller's): frames -> fp32
  * [T,C,Ho,Wo] in [-1,1] by the reference's range rules, bilinearly resized when (Ho,Wo) != (H,W). */
 int32_t vgpa_frames_to_pm1(const void* src, int32_t dtype, int32_t layout, int32_t is_tensor, int64_t T, int64_t C, int64_t H,

@@ -1,6 +1,6 @@
 """The geometry scorer at the reference's scale (10 views x 518 x 518, a cloud of 10 * 518 * 518 points: train/01_preference_pair.py:33-34, utils/projection_utils.py):
 the SAME measurement bench.py attaches as its `scorer` block (bench.scorer_report: ms per video, point-views / s, algorithmic GB/s against the 8 TB/s peak, atomics / s,
-the reference's argsort + scatter formulation on this GPU, the CPU oracle), plus the kernels that block does not touch (confidence cut, MVCS, 8-point + Sampson) so that
+the reference's argsort + scatter formulation on this GPU, the CPU oracle), plus the kernels that block does not touch (confidence cut, MVCS, 8-point + Sampson, SSIM) so that
 a rocprofv3 pass over this script (tools/profile_round.sh) sees every scorer kernel.
     python tools/scorer_bench.py [--quick] [--json gpurun_out/scorer_bench.json]      # --quick: two launches of everything, no timing loops (PMC passes)"""
 import argparse
@@ -68,6 +68,40 @@ out["other_kernels"] = {"conf_threshold_ms": ms_c, "conf_threshold_gbs": N * 4 *
                         "mvcs_gbs": (T - 1) * H * W * 8 / ms_m / 1e6, "epipolar_9x2048_ms_incl_host_packing": ms_e}
 print(f"confidence cut (radix select over {N} values): {ms_c:.3f} ms; fused filter + reproject at conf_thres 50: {ms_p:.3f} ms; MVCS: {ms_m:.3f} ms; "
       f"8-point + Sampson, 9 pairs x 2048 matches: {ms_e:.3f} ms")
+
+# SSIM (csrc/scorer_ssim.hip) on the reference's scorer workload, 10 frames of 518 x 518 x 3, next to the same computation composed from torch ops on this GPU in
+# fp32 (piq.ssim's own formulation: avg_pool2d + five grouped 11 x 11 convolutions + elementwise); GB/s = the bytes of both inputs once over the time.
+def torch_ssim(gt, rep):
+    x, y = [(t.float().permute(0, 3, 1, 2) if t.shape[-1] == 3 else t.float()) for t in (gt, rep)]
+    x, y = [((t + 1) / 2 if t.min() < 0 else (t / 255 if t.max() > 1 else t)) for t in (x, y)]
+    f = max(1, round(min(x.shape[-2:]) / 256))
+    if f > 1:
+        x, y = torch.nn.functional.avg_pool2d(x, f), torch.nn.functional.avg_pool2d(y, f)
+    c = torch.arange(11, dtype=torch.float32, device=x.device) - 5
+    g = torch.exp(-(c[:, None] ** 2 + c[None, :] ** 2) / (2 * 1.5 ** 2))
+    g = (g / g.sum()).expand(x.shape[1], 1, 11, 11).contiguous()
+    conv = lambda t: torch.nn.functional.conv2d(t, g, groups=t.shape[1])
+    mx, my = conv(x), conv(y)
+    sxx, syy, sxy = conv(x * x) - mx * mx, conv(y * y) - my * my, conv(x * y) - mx * my
+    ss = (2 * mx * my + 1e-4) / (mx * mx + my * my + 1e-4) * (2 * sxy + 9e-4) / (sxx + syy + 9e-4)
+    return ss.mean(dim=(1, 2, 3)).mean()
+
+
+gs = torch.Generator(device=dev).manual_seed(2)
+f_gt = torch.rand(T, 3, H, W, generator=gs, device=dev)
+f_rep = (f_gt + 0.05 * torch.randn(T, 3, H, W, generator=gs, device=dev)).clamp(0, 1)
+ssim_rows = {}
+for form, x_gt, x_rep in (("f32_nchw", f_gt, f_rep),
+                          ("u8_nhwc", (f_gt * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous(), (f_rep * 255).round().to(torch.uint8).permute(0, 2, 3, 1).contiguous())):
+    n_s = 2 if a.quick else 200
+    ms_k, v_k = timeit(lambda: scorer.ssim(x_gt, x_rep), n_s)
+    ms_t, v_t = timeit(lambda: torch_ssim(x_gt, x_rep), n_s)
+    nbytes = 2 * x_gt.numel() * x_gt.element_size()
+    ssim_rows[form] = {"ssim_ms": ms_k, "ssim_gbs": nbytes / ms_k / 1e6, "frac_of_hbm_peak": nbytes / ms_k / 1e6 / 8000.0, "torch_ops_ms_same_gpu": ms_t,
+                       "speedup_vs_torch_ops": ms_t / ms_k, "value": float(v_k), "torch_ops_value": float(v_t)}
+    print(f"frame SSIM [{form:8s}] {ms_k:.4f} ms = {nbytes / ms_k / 1e6:.0f} GB/s ({nbytes / ms_k / 1e6 / 8000.0:.3f} of 8 TB/s); torch-op composition on this GPU {ms_t:.4f} ms "
+          f"({ms_t / ms_k:.1f}x); values {float(v_k):.6f} / {float(v_t):.6f}")
+out["ssim"] = ssim_rows
 if not a.quick:
     os.makedirs(os.path.dirname(a.json), exist_ok=True)
     with open(a.json, "w") as f:

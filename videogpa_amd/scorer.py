@@ -1,8 +1,8 @@
 """On-device geometry-consistency scorer: drop-ins for the reference's `batch_reproject` / `project_points`
 (utils/projection_utils.py), `get_colored_pointcloud` (utils/pointcloud_utils.py), `Metric` / `MSEMetric`
-(metrics/base.py, metrics/mse.py), `compute_motion_score_vectorized` / `Consistency_Score`
+/ `PSNRMetric` / `SSIMMetric` (metrics/base.py, metrics/mse.py), `compute_motion_score_vectorized` / `Consistency_Score`
 (metrics/consistency_score.py) and the geometry half of `EpipolarMetric` (metrics/epipolar.py:161-213).
-Kernels: videogpa_amd/csrc/scorer.hip.  Third-party networks (LPIPS-VGG, SIFT / LightGlue matchers, VGGT / DA3
+Kernels: videogpa_amd/csrc/{scorer,scorer2,scorer_ssim}.hip.  Third-party networks (LPIPS-VGG, SIFT / LightGlue matchers, VGGT / DA3
 backbones) are outside the hot path: they are passed in as callables / precomputed matches."""
 from abc import ABC, abstractmethod
 from typing import Any
@@ -174,6 +174,46 @@ class PSNRMetric(Metric):
 
     def compute(self, *, gt, rep, **kwargs) -> float:
         return float(_frame_metric(gt, rep, psnr=True).item())
+
+
+def ssim(gt, rep, *, downsample=True, reduction="mean"):
+    """piq.ssim(gt01, rep01, data_range=1.0) as metrics/mse.py:101-110 calls it (11 x 11 Gaussian window, sigma 1.5, k1 0.01, k2 0.03,
+    average pool by max(1, round(min(H, W) / 256)) unless `downsample` is False) in one fused kernel (csrc/scorer_ssim.hip).  Inputs take
+    every form of `_to_tensor_01` (:112-134) and are brought to [0,1] on the device, so the data range is always 1.  -> device fp32
+    scalar (`reduction="mean"`) or the per-frame values [T] (`"none"`).  Unlike MSE / PSNR nothing is resized: sizes must agree."""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f"reduction must be 'mean' or 'none', got {reduction!r}")
+    if not torch.cuda.is_available():
+        raise RuntimeError("videogpa_amd.scorer.ssim runs on the GPU only (no CPU fallback)")
+    g, gd, gl, gt_t, T, C, H, W = _img_desc(gt)
+    r, rd, rl, rt_t, T2, C2, H2, W2 = _img_desc(rep)
+    if (T, C) != (T2, C2):
+        raise ValueError(f"gt and rep disagree in frames / channels: {(T, C)} vs {(T2, C2)}")
+    if (H, W) != (H2, W2):
+        raise ValueError(f"SSIM does not resize: gt is {H} x {W}, rep is {H2} x {W2}")
+    f = max(1, round(min(H, W) / 256)) if downsample else 1
+    if min(H // f, W // f) < 11:
+        raise ValueError(f"SSIM needs at least 11 x 11 pixels after the {f} x {f} average pool, got {H // f} x {W // f}")
+    per_frame = torch.empty(T, dtype=torch.float32, device=g.device)
+    mean = torch.empty(1, dtype=torch.float32, device=g.device)
+    ws_bytes = _lib.query("vgpa_frame_ssim_workspace_bytes", T, C, H, W)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=g.device)
+    _lib.call("vgpa_frame_ssim", g, gd, gl, gt_t, r, rd, rl, rt_t, T, C, H, W, 1 if downsample else 0, per_frame, mean, ws, ws_bytes, _stream())
+    return mean[0] if reduction == "mean" else per_frame
+
+
+class SSIMMetric(Metric):
+    """metrics/mse.py:101-110: mean structural similarity of the frames, 1.0 for identical inputs."""
+
+    def __init__(self, device="cuda"):
+        super().__init__(name="ssim")
+        self.device = device
+
+    def compute_device(self, *, gt, rep):
+        return ssim(gt, rep)
+
+    def compute(self, *, gt, rep, **kwargs) -> float:
+        return float(self.compute_device(gt=gt, rep=rep).item())
 
 
 class MVCSMetric(Metric):

@@ -419,6 +419,35 @@ int32_t vgpa_unproject_depth(const float* depth, const float* K, const float* E,
 int32_t vgpa_pose_decode(const float* pose_enc, int64_t n, float image_h, float image_w, float* ext, float* intr,
                          vgpa_stream_t stream);
 
+/* ---- VGGT prediction heads: vggt/heads/dpt_head.py, camera_head.py (csrc/vggt_heads.hip) ---------------------------------
+ * All fp32, channels-last (NHWC), forward only, 16-byte aligned bases.  The convolutions are implicit GEMMs on the exact-fp32
+ * MFMA (v_mfma_f32_32x32x2_f32); Cin and Cout multiples of 16, H and W arbitrary.
+ *
+ * 3x3, pad 1, stride 1 | 2:  out = conv(relu?(x)) + bias? + relu?(res)? + res2?   (bias / res / res2 may be NULL; res, res2 and out
+ * are [N,Ho,Wo,Cout], Ho = (H - 1) / stride + 1).  flags bit0: ReLU on the input, bit1: ReLU on `res` -- the reference's
+ * ResidualConvUnit applies its in-place ReLU to the tensor it later adds (dpt_head.py:366-386).  w_packed = [3][3][Cin][Cout]. */
+int32_t vgpa_conv3x3_f32(const float* x, const float* w_packed, const float* bias, const float* res, const float* res2, float* out,
+                         int64_t N, int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t stride, int32_t flags,
+                         vgpa_stream_t stream);
+/* 1x1 convolution on the same core: out [M,Cout] = x [M,Cin] . w_packed [Cin][Cout] + bias?  (projects.N, out_conv, and the
+ * kernel = stride ConvTranspose2d as a GEMM in front of a pixel shuffle).  Every output element sums in the same order whatever M. */
+int32_t vgpa_conv1x1_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t M, int64_t Cin, int64_t Cout,
+                         vgpa_stream_t stream);
+/* The end of DPTHead._forward_impl (dpt_head.py:229-247) in one launch: x [N,h,w,C] is sampled bilinearly (align_corners=True) at
+ * the (H,W) grid, xtab [W,C/2] / ytab [H,C/2] (the 0.1-scaled halves of position_grid_to_embed; both NULL = no embedding) are
+ * added, then 3x3 conv C -> 32 (w1_packed [3][3][C][32]) + b1 + ReLU, 1x1 conv 32 -> output_dim (w2 [output_dim][32]) + b2,
+ * activate_head: preds [N,H,W,output_dim-1] (activation 0 exp, 1 inv_log), conf [N,H,W] = 1 + exp.  No [N,H,W,C] tensor is built. */
+int32_t vgpa_dpt_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1,
+                          const float* w2, const float* b2, float* preds, float* conf, int64_t N, int64_t h, int64_t w, int64_t C,
+                          int64_t H, int64_t W, int32_t output_dim, int32_t activation, vgpa_stream_t stream);
+/* F.interpolate(bilinear, align_corners=True) of x [N,h,w,C] to out [N,H,W,C] (+ the separable embedding tables as above, or NULL). */
+int32_t vgpa_upsample_bilinear_ac_f32(const float* x, const float* xtab, const float* ytab, float* out, int64_t N, int64_t h,
+                                      int64_t w, int64_t C, int64_t H, int64_t W, vgpa_stream_t stream);
+/* softmax(scale q k^T) v in fp32 for the camera trunk: S <= 128 tokens, D a multiple of 32 (<= 256), one workgroup per (batch, head).
+ * q / k / v element (b,h,s,d) at base[b * stride_b + h * stride_h + s * stride_s + d]; o [B,S,H,D] contiguous. */
+int32_t vgpa_attn_small_f32(const float* q, const float* k, const float* v, int64_t stride_b, int64_t stride_h, int64_t stride_s,
+                            float* o, int64_t B, int64_t H, int64_t S, int64_t D, float scale, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,6 +1,6 @@
 """The geometry scorer at the reference's scale (10 views x 518 x 518, a cloud of 10 * 518 * 518 points: train/01_preference_pair.py:33-34, utils/projection_utils.py):
 the SAME measurement bench.py attaches as its `scorer` block (bench.scorer_report: ms per video, point-views / s, algorithmic GB/s against the 8 TB/s peak, atomics / s,
-the reference's argsort + scatter formulation on this GPU, the CPU oracle), plus the kernels that block does not touch (confidence cut, MVCS, 8-point + Sampson, SSIM) so that
+the reference's argsort + scatter formulation on this GPU, the CPU oracle), plus the kernels that block does not touch (confidence cut, MVCS, 8-point + Sampson, SSIM, the VGGT heads) so that
 a rocprofv3 pass over this script (tools/profile_round.sh) sees every scorer kernel.
     python tools/scorer_bench.py [--quick] [--json gpurun_out/scorer_bench.json]      # --quick: two launches of everything, no timing loops (PMC passes)"""
 import argparse
@@ -102,6 +102,62 @@ for form, x_gt, x_rep in (("f32_nchw", f_gt, f_rep),
     print(f"frame SSIM [{form:8s}] {ms_k:.4f} ms = {nbytes / ms_k / 1e6:.0f} GB/s ({nbytes / ms_k / 1e6 / 8000.0:.3f} of 8 TB/s); torch-op composition on this GPU {ms_t:.4f} ms "
           f"({ms_t / ms_k:.1f}x); values {float(v_k):.6f} / {float(v_t):.6f}")
 out["ssim"] = ssim_rows
+
+# The VGGT heads (csrc/vggt_heads.hip) at the scorer's scale, 10 frames of 518 x 518 (37 x 37 patches), VGGT-1B widths: one DPT head and the camera head, next to the
+# same computation from torch ops (fp32, TF32 off) in the same process, and the convolution kernel per shape against the 157.3 TFLOP/s fp32-matrix peak.
+from videogpa_amd import ops  # noqa: E402
+from videogpa_amd.vggt import CameraHead, DPTHead  # noqa: E402
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import vggt_heads_ref as heads_ref  # noqa: E402
+
+torch.backends.cudnn.allow_tf32 = torch.backends.cuda.matmul.allow_tf32 = False
+F32_MATRIX_PEAK = 157.3e12
+n_h = 2 if a.quick else 5
+heads = {"conv3x3": {}}
+with torch.no_grad():
+    for tag, (nf, hw_, ci, co) in {"refinenet1 256->256 @148": (10, 148, 256, 256), "output_conv1 256->128 @296": (10, 296, 256, 128), "refinenet2 256->256 @74": (10, 74, 256, 256),
+                                    "layer2_rn 512->256 @74": (10, 74, 512, 256), "layer4_rn 1024->256 @19": (10, 19, 1024, 256)}.items():
+        x = torch.randn(nf, hw_, hw_, ci, device=dev)
+        w = torch.randn(co, ci, 3, 3, device=dev) / (9 * ci) ** 0.5
+        b = torch.randn(co, device=dev)
+        wp = ops.pack_conv_weight(w)
+        xc = x.permute(0, 3, 1, 2)                                             # the same memory as a channels_last NCHW tensor
+        ms_k, _ = timeit(lambda: ops.conv3x3_f32(x, wp, b, relu_in=True), n_h)
+        ms_t, _ = timeit(lambda: torch.nn.functional.conv2d(torch.relu(xc), w, b, padding=1), n_h)
+        fl = 2.0 * nf * hw_ * hw_ * 9 * ci * co
+        heads["conv3x3"][tag] = {"ms": ms_k, "tflops": fl / ms_k / 1e9, "frac_of_f32_matrix_peak": fl / ms_k / 1e-3 / F32_MATRIX_PEAK, "torch_conv2d_ms_same_gpu": ms_t}
+        print(f"conv3x3_f32 [{tag:28s}] {ms_k:.3f} ms = {fl / ms_k / 1e9:.1f} TFLOP/s ({fl / ms_k / 1e-3 / F32_MATRIX_PEAK:.3f} of the fp32-matrix peak); torch conv2d {ms_t:.3f} ms")
+        del x, w, xc
+    x = torch.randn(8, 296, 296, 128, device=dev)
+    w1, b1 = torch.randn(32, 128, 3, 3, device=dev) / 34, torch.randn(32, device=dev)
+    w2, b2 = torch.randn(2, 32, device=dev) * 0.2, torch.randn(2, device=dev)
+    tabs, w1p = ops.uv_embed_tables(518, 518, 128, 1.0, dev), ops.pack_conv_weight(w1)
+    sd_t = {"scratch.output_conv2.0.weight": w1, "scratch.output_conv2.0.bias": b1, "scratch.output_conv2.2.weight": w2.reshape(2, 32, 1, 1), "scratch.output_conv2.2.bias": b2}
+    ms_k, _ = timeit(lambda: ops.dpt_tail_f32(x, 518, 518, w1p, b1, w2, b2, activation="exp", tabs=tabs), n_h)
+    xc = x.permute(0, 3, 1, 2).contiguous()
+    ms_t, _ = timeit(lambda: heads_ref.dpt_tail(sd_t, xc, (518, 518)), n_h)
+    fl = 2.0 * 8 * 518 * 518 * 9 * 128 * 32
+    heads["dpt_tail_8_frames"] = {"ms": ms_k, "tflops": fl / ms_k / 1e9, "frac_of_f32_matrix_peak": fl / ms_k / 1e-3 / F32_MATRIX_PEAK, "torch_ops_ms_same_gpu": ms_t}
+    print(f"dpt_tail_f32 [8 frames, 128 -> 32 -> 2 @518] {ms_k:.3f} ms = {fl / ms_k / 1e9:.1f} TFLOP/s; torch ops (interpolate + embed + conv + conv + exp) {ms_t:.3f} ms")
+    del x, xc
+    torch.manual_seed(0)
+    head = DPTHead(dim_in=2048, output_dim=2, activation="exp").to(dev).eval()
+    toks = [torch.randn(1, 10, 5 + 37 * 37, 2048, device=dev) if i in (4, 11, 17, 23) else None for i in range(24)]
+    images = torch.zeros(1, 10, 3, 518, 518, device=dev)
+    sd_h = {k: v.detach() for k, v in head.state_dict().items()}
+    ms_k, _ = timeit(lambda: head(toks, images, 5), n_h)
+    ms_t, _ = timeit(lambda: [heads_ref.dpt_head(sd_h, [t[:, s0:s0 + 8] if t is not None else None for t in toks], (518, 518), 5, layer_idx=(4, 11, 17, 23))
+                              for s0 in (0, 8)], n_h)
+    heads["dpt_head_10_frames"] = {"ms": ms_k, "torch_ops_ms_same_gpu": ms_t, "speedup_vs_torch_ops": ms_t / ms_k}
+    print(f"DPTHead [10 x 518 x 518, dim_in 2048, features 256, chunks of 8] {ms_k:.2f} ms; torch ops on this GPU {ms_t:.2f} ms ({ms_t / ms_k:.2f}x)")
+    cam = CameraHead(dim_in=2048).to(dev).eval()
+    sd_c = {k: v.detach() for k, v in cam.state_dict().items()}
+    ctoks = [torch.randn(1, 10, 1, 2048, device=dev)]
+    ms_k, _ = timeit(lambda: cam(ctoks), n_h)
+    ms_t, _ = timeit(lambda: heads_ref.camera_head(sd_c, ctoks, 16, 4), n_h)
+    heads["camera_head_10_frames"] = {"ms": ms_k, "torch_ops_ms_same_gpu": ms_t}
+    print(f"CameraHead [10 frames, dim 2048, 4 blocks, 4 iterations] {ms_k:.3f} ms; torch ops on this GPU {ms_t:.3f} ms")
+out["vggt_heads"] = heads
 if not a.quick:
     os.makedirs(os.path.dirname(a.json), exist_ok=True)
     with open(a.json, "w") as f:

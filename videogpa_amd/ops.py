@@ -1325,3 +1325,119 @@ def rope2d_tables(pos, head_dim=64, frequency=100.0):
     ang = pos.float()[:, :, None] * inv[None, None, :]                 # [N, 2, half/2]
     ang = torch.cat([ang, ang], dim=-1).reshape(pos.shape[0], head_dim)  # [y-angles x2 | x-angles x2]
     return ang.cos().contiguous(), ang.sin().contiguous()
+
+
+# ---- VGGT prediction heads (csrc/vggt_heads.hip): fp32, channels-last, forward only ------------------------------------------------------
+def _heads_in(*ts):
+    for t in ts:
+        if t is None:
+            continue
+        _req(t, torch.float32)
+        if torch.is_grad_enabled() and t.requires_grad:
+            raise RuntimeError("the VGGT head kernels are forward only: call them under torch.no_grad()")
+
+
+def pack_conv_weight(w):
+    """Conv2d weight [Cout, Cin, kh, kw] -> [kh][kw][Cin][Cout] fp32 contiguous, the layout the convolution kernels read"""
+    return w.detach().float().permute(2, 3, 1, 0).contiguous()
+
+
+def conv3x3_f32(x, w_packed, bias=None, res=None, res2=None, relu_in=False, relu_res=False, stride=1):
+    """x [N,H,W,Cin] -> conv3x3(relu?(x), pad 1, stride) + bias? + relu?(res)? + res2? as [N,Ho,Wo,Cout]; w_packed [3,3,Cin,Cout]"""
+    _heads_in(x, w_packed, bias, res, res2)
+    N, H, W, Cin = x.shape
+    Cout = w_packed.shape[-1]
+    if tuple(w_packed.shape) != (3, 3, Cin, Cout) or Cin % 16 or Cout % 16:
+        raise RuntimeError(f"conv3x3_f32: weight {tuple(w_packed.shape)} does not fit input channels {Cin} (multiples of 16)")
+    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
+    out = torch.empty(N, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
+    for r in (res, res2):
+        if r is not None and r.shape != out.shape:
+            raise RuntimeError("conv3x3_f32: residual shape differs from the output's")
+    _timed("conv3x3_f32", 2.0 * out.numel() * 9 * Cin,
+           lambda: _lib.call("vgpa_conv3x3_f32", x, w_packed, bias, res, res2, out, N, H, W, Cin, Cout, stride,
+                             (1 if relu_in else 0) | (2 if relu_res else 0), _stream()))
+    return out
+
+
+def conv1x1_f32(x, w_packed, bias=None):
+    """x [..., Cin] -> x . w_packed [Cin, Cout] + bias? as [..., Cout]"""
+    _heads_in(x, w_packed, bias)
+    Cin, Cout = w_packed.shape
+    if x.shape[-1] != Cin or Cin % 16 or Cout % 16:
+        raise RuntimeError(f"conv1x1_f32: weight {tuple(w_packed.shape)} does not fit input {tuple(x.shape)} (channels in multiples of 16)")
+    out = torch.empty(*x.shape[:-1], Cout, device=x.device, dtype=torch.float32)
+    M = out.numel() // Cout
+    _timed("conv1x1_f32", 2.0 * M * Cin * Cout, lambda: _lib.call("vgpa_conv1x1_f32", x, w_packed, bias, out, M, Cin, Cout, _stream()))
+    return out
+
+
+def uv_embed_tables(width, height, channels, aspect_ratio, device, ratio=0.1):
+    """The two halves of `position_grid_to_embed(create_uv_grid(width, height, aspect_ratio), channels) * ratio` (vggt/heads/utils.py:11-109,
+    dpt_head.py:249-259): the embedding concatenates an x half and a y half, so it is two tables, xtab [width, channels/2] and
+    ytab [height, channels/2] (fp32: sin | cos of coordinate * 100^(-i / (channels/4)), angles in float64 as upstream)."""
+    if channels % 8:
+        raise RuntimeError("uv_embed_tables: channels must be a multiple of 8")
+    diag = (aspect_ratio ** 2 + 1.0) ** 0.5
+    span_x, span_y = aspect_ratio / diag, 1.0 / diag
+    xs = torch.linspace(-span_x * (width - 1) / width, span_x * (width - 1) / width, steps=width, dtype=torch.float32)
+    ys = torch.linspace(-span_y * (height - 1) / height, span_y * (height - 1) / height, steps=height, dtype=torch.float32)
+    half = channels // 2
+    omega = torch.arange(half // 2, dtype=torch.float64)
+    omega /= half / 2.0
+    omega = 1.0 / 100 ** omega
+
+    def table(pos):
+        ang = torch.einsum("m,d->md", pos.double(), omega)
+        return (torch.cat([ang.sin(), ang.cos()], dim=1).float() * ratio).contiguous().to(device)
+    return table(xs), table(ys)
+
+
+def upsample_bilinear_ac_f32(x, H, W, tabs=None):
+    """F.interpolate(bilinear, align_corners=True) of x [N,h,w,C] to [N,H,W,C], plus the separable embedding tabs = (xtab [W,C/2], ytab [H,C/2])"""
+    xt, yt = tabs if tabs is not None else (None, None)
+    _heads_in(x, xt, yt)
+    N, h, w, C = x.shape
+    if xt is not None and (tuple(xt.shape) != (W, C // 2) or tuple(yt.shape) != (H, C // 2)):
+        raise RuntimeError("upsample_bilinear_ac_f32: embedding tables do not fit the output")
+    out = torch.empty(N, H, W, C, device=x.device, dtype=torch.float32)
+    _timed("upsample_bilinear_ac_f32", 4.0 * out.numel(), lambda: _lib.call("vgpa_upsample_bilinear_ac_f32", x, xt, yt, out, N, h, w, C, H, W, _stream()),
+           unit="byte")
+    return out
+
+
+_DPT_ACT = {"exp": 0, "inv_log": 1}
+
+
+def dpt_tail_f32(x, H, W, w1_packed, b1, w2, b2, activation="exp", tabs=None):
+    """The end of DPTHead._forward_impl in one launch: x [N,h,w,C] -> (preds [N,H,W,output_dim-1], conf [N,H,W]); w1_packed [3,3,C,32],
+    w2 [output_dim,32]; confidence activation expp1"""
+    xt, yt = tabs if tabs is not None else (None, None)
+    _heads_in(x, xt, yt, w1_packed, b1, w2, b2)
+    if activation not in _DPT_ACT:
+        raise NotImplementedError(f"dpt_tail_f32: activation {activation!r} (exp and inv_log are built)")
+    N, h, w, C = x.shape
+    od = w2.shape[0]
+    if tuple(w1_packed.shape) != (3, 3, C, 32) or w2.shape[1] != 32 or C % 16:
+        raise RuntimeError("dpt_tail_f32: weights do not fit the input")
+    if xt is not None and (tuple(xt.shape) != (W, C // 2) or tuple(yt.shape) != (H, C // 2)):
+        raise RuntimeError("dpt_tail_f32: embedding tables do not fit the output")
+    preds = torch.empty(N, H, W, od - 1, device=x.device, dtype=torch.float32)
+    conf = torch.empty(N, H, W, device=x.device, dtype=torch.float32)
+    _timed("dpt_tail_f32", 2.0 * N * H * W * (9 * C * 32 + 32 * od),
+           lambda: _lib.call("vgpa_dpt_tail_f32", x, xt, yt, w1_packed, b1, w2, b2, preds, conf, N, h, w, C, H, W, od, _DPT_ACT[activation], _stream()))
+    return preds, conf
+
+
+def attn_small_f32(qkv, scale=None):
+    """qkv [B,S,3,H,D] fp32 (a Linear's output, read in place) -> softmax(scale q k^T) v as [B,S,H*D]; S <= 128, D a multiple of 32"""
+    _heads_in(qkv)
+    B, S, three, H, D = qkv.shape
+    if three != 3 or S > 128 or D % 32 or D > 256:
+        raise RuntimeError(f"attn_small_f32: qkv {tuple(qkv.shape)} outside S <= 128, D in multiples of 32 up to 256")
+    o = torch.empty(B, S, H * D, device=qkv.device, dtype=torch.float32)
+    q, k, v = qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2]
+    _timed("attn_small_f32", 4.0 * B * H * S * S * D,
+           lambda: _lib.call("vgpa_attn_small_f32", q, k, v, S * 3 * H * D, D, 3 * H * D, o, B, H, S, D, float(scale if scale is not None else D ** -0.5),
+                             _stream()))
+    return o

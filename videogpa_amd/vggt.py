@@ -15,7 +15,15 @@ Unlike the CogVideoX attention (un-vendored diffusers), this code is IN the refe
 against reference outputs: tests/golden/vggt_attention.pt, tests/test_gpu_vggt.py.  The backbone is frozen in the reference's use
 (metrics only): gradients flow to the input and to the Linear layers (torch autograd around the kernels); LayerNorm / LayerScale
 parameters get none.  head_dim must be 64 and qk_norm on (what VGGT-1B's aggregator uses: dim 1024, 16 heads).  Patch embedding
-(DINOv2), camera / depth heads and checkpoint loading stay the caller's (third-party networks, outside the path)."""
+(DINOv2) and checkpoint loading stay the caller's (third-party networks, outside the path).
+
+The prediction heads are reference-held too and sit below the aggregator (fp32, forward only, csrc/vggt_heads.hip; pinned on
+tests/golden/vggt_heads.pt, tests/test_gpu_vggt_heads.py):
+
+    CameraHead               vggt/heads/camera_head.py:19-149 (trunk of head_dim-128 blocks without QK-norm on the small fp32 attention)
+    DPTHead                  vggt/heads/dpt_head.py:21-484    (channels-last; every convolution is the fp32-MFMA implicit GEMM, the full-resolution
+                                                                end of the head is one fused launch)
+    VGGT                     vggt/models/vggt.py:17-96        (aggregator + camera / depth / point heads; no track head)"""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -241,3 +249,319 @@ class Aggregator(nn.Module):
                 inter[kind] = got
             out += [torch.cat([f, g], dim=-1) for f, g in zip(inter["frame"], inter["global"])]
         return out, self.patch_start_idx
+
+
+# ---------------------------------------------------------------------------------------------------------------- prediction heads
+def _forward_only(module, *tensors):
+    if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(t.requires_grad for t in tensors)):
+        raise RuntimeError(f"{type(module).__name__} is forward only (no backward kernels): call it under torch.no_grad()")
+
+
+class _PackedCache:
+    """fp32 kernel-layout copies of parameters, rebuilt when a parameter's `_version`, storage or device changes"""
+
+    def __init__(self):
+        self._c = {}
+
+    def get(self, key, params, make):
+        tag = tuple((p._version, p.data_ptr(), str(p.device), p.dtype) for p in params)
+        hit = self._c.get(key)
+        if hit is None or hit[0] != tag:
+            with torch.no_grad():
+                hit = (tag, make())
+            self._c[key] = hit
+        return hit[1]
+
+
+class TrunkAttention(nn.Module):
+    """vggt/layers/attention.py:21-72 as the camera trunk builds it: no QK-norm, no RoPE, any head_dim in multiples of 32, a few tokens (one per frame)"""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=True, proj_bias=True):
+        super().__init__()
+        if dim % num_heads or (dim // num_heads) % 32:
+            raise NotImplementedError("the small fp32 attention covers head_dim in multiples of 32")
+        self.num_heads, self.head_dim = num_heads, dim // num_heads
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.proj = nn.Linear(dim, dim, bias=proj_bias)
+
+    def forward(self, x):
+        B, N, C = x.shape
+        qkv = self.qkv(x).reshape(B, N, 3, self.num_heads, self.head_dim).contiguous()
+        return self.proj(ops.attn_small_f32(qkv, self.head_dim ** -0.5))
+
+
+class HeadMlp(nn.Module):
+    """vggt/layers/mlp.py:16-40 with out_features"""
+
+    def __init__(self, in_features, hidden_features=None, out_features=None, bias=True):
+        super().__init__()
+        self.fc1 = nn.Linear(in_features, hidden_features or in_features, bias=bias)
+        self.fc2 = nn.Linear(hidden_features or in_features, out_features or in_features, bias=bias)
+
+    def forward(self, x):
+        return self.fc2(F.gelu(self.fc1(x)))
+
+
+class TrunkBlock(nn.Module):
+    """vggt/layers/block.py:27-98 at the camera head's settings (LayerScale on, qk_norm off, no rope), fp32"""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, init_values=None):
+        super().__init__()
+        if not init_values:
+            raise NotImplementedError("blocks without LayerScale are not used by VGGT's camera head")
+        self.norm1 = nn.LayerNorm(dim)
+        self.attn = TrunkAttention(dim, num_heads=num_heads)
+        self.ls1 = LayerScale(dim, init_values)
+        self.norm2 = nn.LayerNorm(dim)
+        self.mlp = HeadMlp(dim, int(dim * mlp_ratio))
+        self.ls2 = LayerScale(dim, init_values)
+
+    def forward(self, x):
+        x = x + self.attn(self.norm1(x)) * self.ls1.gamma
+        return x + self.mlp(self.norm2(x)) * self.ls2.gamma
+
+
+class CameraHead(nn.Module):
+    """vggt/heads/camera_head.py:19-149: iterative refinement of the 9-number pose encoding from the camera tokens of the last aggregator
+    output.  The Linear / LayerNorm layers are torch (a handful of tokens); the trunk's attention is ops.attn_small_f32.  fp32 whatever
+    autocast says, forward only."""
+
+    def __init__(self, dim_in=2048, trunk_depth=4, pose_encoding_type="absT_quaR_FoV", num_heads=16, mlp_ratio=4, init_values=0.01,
+                 trans_act="linear", quat_act="linear", fl_act="relu"):
+        super().__init__()
+        if pose_encoding_type != "absT_quaR_FoV":
+            raise ValueError(f"Unsupported camera encoding type: {pose_encoding_type}")
+        self.target_dim = 9
+        self.trans_act, self.quat_act, self.fl_act, self.trunk_depth = trans_act, quat_act, fl_act, trunk_depth
+        self.trunk = nn.Sequential(*[TrunkBlock(dim=dim_in, num_heads=num_heads, mlp_ratio=mlp_ratio, init_values=init_values)
+                                     for _ in range(trunk_depth)])
+        self.token_norm = nn.LayerNorm(dim_in)
+        self.trunk_norm = nn.LayerNorm(dim_in)
+        self.empty_pose_tokens = nn.Parameter(torch.zeros(1, 1, self.target_dim))
+        self.embed_pose = nn.Linear(self.target_dim, dim_in)
+        self.poseLN_modulation = nn.Sequential(nn.SiLU(), nn.Linear(dim_in, 3 * dim_in, bias=True))
+        self.adaln_norm = nn.LayerNorm(dim_in, elementwise_affine=False, eps=1e-6)
+        self.pose_branch = HeadMlp(in_features=dim_in, hidden_features=dim_in // 2, out_features=self.target_dim)
+
+    @staticmethod
+    def _act(x, kind):
+        if kind == "linear":
+            return x
+        if kind == "relu":
+            return F.relu(x)
+        if kind == "exp":
+            return torch.exp(x)
+        if kind == "inv_log":
+            return torch.sign(x) * torch.expm1(torch.abs(x))
+        raise ValueError(f"Unknown act_type: {kind}")
+
+    def forward(self, aggregated_tokens_list, num_iterations=4):
+        tokens = aggregated_tokens_list[-1]
+        _forward_only(self, tokens)
+        with torch.autocast(tokens.device.type, enabled=False):
+            pose_tokens = self.token_norm(tokens[:, :, 0].float())
+            B, S, C = pose_tokens.shape
+            pred, out = None, []
+            for _ in range(num_iterations):
+                module_input = self.embed_pose(self.empty_pose_tokens.expand(B, S, -1) if pred is None else pred)
+                shift, scale, gate = self.poseLN_modulation(module_input).chunk(3, dim=-1)
+                x = gate * (self.adaln_norm(pose_tokens) * (1 + scale) + shift) + pose_tokens
+                delta = self.pose_branch(self.trunk_norm(self.trunk(x)))
+                pred = delta if pred is None else pred + delta
+                out.append(torch.cat([self._act(pred[..., :3], self.trans_act), self._act(pred[..., 3:7], self.quat_act),
+                                      self._act(pred[..., 7:], self.fl_act)], dim=-1))
+        return out
+
+
+class _ResidualConvUnit(nn.Module):
+    def __init__(self, features):
+        super().__init__()
+        self.conv1 = nn.Conv2d(features, features, kernel_size=3, stride=1, padding=1, bias=True)
+        self.conv2 = nn.Conv2d(features, features, kernel_size=3, stride=1, padding=1, bias=True)
+
+
+class _FeatureFusionBlock(nn.Module):
+    def __init__(self, features, has_residual=True):
+        super().__init__()
+        self.out_conv = nn.Conv2d(features, features, kernel_size=1, stride=1, padding=0, bias=True)
+        if has_residual:
+            self.resConfUnit1 = _ResidualConvUnit(features)
+        self.has_residual = has_residual
+        self.resConfUnit2 = _ResidualConvUnit(features)
+
+
+class DPTHead(nn.Module):
+    """vggt/heads/dpt_head.py:21-484 on the HIP kernels, channels-last from the tokens to the predictions: `forward(aggregated_tokens_list,
+    images [B,S,3,H,W], patch_start_idx, frames_chunk_size=8) -> (preds [B,S,H,W,output_dim-1], conf [B,S,H,W])`.  The modules below only
+    hold the parameters under the reference's names and shapes (a reference state dict loads by name); the arithmetic is
+
+        LayerNorm (torch) -> projects.N, resize_layers.{0,1} as 1x1 convolutions (+ pixel shuffle) -> resize_layers.3 / layerN_rn /
+        ResidualConvUnits / output_conv1 as ops.conv3x3_f32 with ReLU, bias and residual adds fused -> out_conv BEFORE the bilinear
+        upsample (both linear, the interpolation weights sum to 1: a quarter of the pixels) -> ops.dpt_tail_f32.
+
+    A ResidualConvUnit's ReLU is in-place upstream, so the tensor it adds back is relu(x), not x (dpt_head.py:366-386): relu_res.
+    fp32 whatever autocast says; forward only."""
+
+    def __init__(self, dim_in, patch_size=14, output_dim=4, activation="inv_log", conf_activation="expp1", features=256,
+                 out_channels=(256, 512, 1024, 1024), intermediate_layer_idx=(4, 11, 17, 23), pos_embed=True, feature_only=False, down_ratio=1):
+        super().__init__()
+        if feature_only or down_ratio != 1 or conf_activation != "expp1" or activation not in ("exp", "inv_log"):
+            raise NotImplementedError("DPTHead on the HIP path: feature_only=False, down_ratio=1, conf_activation='expp1', activation 'exp' | 'inv_log'")
+        if dim_in % 16 or features % 32 or any(c % 16 for c in out_channels) or len(out_channels) != 4:
+            raise NotImplementedError("DPTHead on the HIP path: four stages, channel counts in multiples of 16")
+        out_channels = list(out_channels)
+        self.patch_size, self.activation, self.conf_activation, self.pos_embed = patch_size, activation, conf_activation, pos_embed
+        self.feature_only, self.down_ratio, self.intermediate_layer_idx = feature_only, down_ratio, list(intermediate_layer_idx)
+        self.norm = nn.LayerNorm(dim_in)
+        self.projects = nn.ModuleList([nn.Conv2d(dim_in, oc, kernel_size=1, stride=1, padding=0) for oc in out_channels])
+        self.resize_layers = nn.ModuleList([
+            nn.ConvTranspose2d(out_channels[0], out_channels[0], kernel_size=4, stride=4, padding=0),
+            nn.ConvTranspose2d(out_channels[1], out_channels[1], kernel_size=2, stride=2, padding=0),
+            nn.Identity(),
+            nn.Conv2d(out_channels[3], out_channels[3], kernel_size=3, stride=2, padding=1)])
+        self.scratch = nn.Module()
+        for i, c in enumerate(out_channels):
+            setattr(self.scratch, f"layer{i + 1}_rn", nn.Conv2d(c, features, kernel_size=3, stride=1, padding=1, bias=False))
+        self.scratch.refinenet1 = _FeatureFusionBlock(features)
+        self.scratch.refinenet2 = _FeatureFusionBlock(features)
+        self.scratch.refinenet3 = _FeatureFusionBlock(features)
+        self.scratch.refinenet4 = _FeatureFusionBlock(features, has_residual=False)
+        self.scratch.output_conv1 = nn.Conv2d(features, features // 2, kernel_size=3, stride=1, padding=1)
+        self.scratch.output_conv2 = nn.Sequential(nn.Conv2d(features // 2, 32, kernel_size=3, stride=1, padding=1), nn.ReLU(inplace=True),
+                                                  nn.Conv2d(32, output_dim, kernel_size=1, stride=1, padding=0))
+        self._packed = _PackedCache()
+        self._tabs = {}
+
+    # ---- kernel-layout parameters
+    def _conv(self, name, conv):
+        """-> (weight [kh][kw][Cin][Cout] (a 1x1 as [Cin][Cout]), bias fp32 | None)"""
+        def make():
+            w = ops.pack_conv_weight(conv.weight)
+            return (w[0, 0].contiguous() if w.shape[0] == 1 else w), (None if conv.bias is None else conv.bias.detach().float().contiguous())
+        return self._packed.get(name, [conv.weight] + ([] if conv.bias is None else [conv.bias]), make)
+
+    def _deconv(self, name, conv):
+        """ConvTranspose2d with kernel = stride k: weight [Cin, Cout, k, k] -> [Cin][(a, b, Cout)], the bias repeated per (a, b)"""
+        def make():
+            k = conv.kernel_size[0]
+            w = conv.weight.detach().float().permute(0, 2, 3, 1).reshape(conv.in_channels, k * k * conv.out_channels).contiguous()
+            return w, conv.bias.detach().float().repeat(k * k).contiguous()
+        return self._packed.get(name, [conv.weight, conv.bias], make)
+
+    def _embed(self, width, height, channels, aspect, device):
+        key = (width, height, channels, aspect, str(device))
+        if key not in self._tabs:
+            if len(self._tabs) > 64:
+                self._tabs.clear()
+            self._tabs[key] = ops.uv_embed_tables(width, height, channels, aspect, device)
+        return self._tabs[key]
+
+    # ---- forward
+    def forward(self, aggregated_tokens_list, images, patch_start_idx, frames_chunk_size=8):
+        _forward_only(self, images, *[aggregated_tokens_list[i] for i in self.intermediate_layer_idx])
+        B, S, _, H, W = images.shape
+        with torch.autocast(images.device.type, enabled=False):
+            if frames_chunk_size is None or frames_chunk_size >= S:
+                return self._forward_impl(aggregated_tokens_list, (H, W), patch_start_idx, 0, S)
+            assert frames_chunk_size > 0
+            parts = [self._forward_impl(aggregated_tokens_list, (H, W), patch_start_idx, s0, min(s0 + frames_chunk_size, S))
+                     for s0 in range(0, S, frames_chunk_size)]
+            return torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1)
+
+    def _rcu(self, name, unit, x, extra=None):
+        """conv2(relu(conv1(relu(x)))) + relu(x) (+ extra): two launches"""
+        w1, b1 = self._conv(name + ".conv1", unit.conv1)
+        w2, b2 = self._conv(name + ".conv2", unit.conv2)
+        t = ops.conv3x3_f32(x, w1, b1, relu_in=True)
+        return ops.conv3x3_f32(t, w2, b2, res=x, res2=extra, relu_in=True, relu_res=True)
+
+    def _fuse(self, name, block, x0, x1, size):
+        out = self._rcu(name + ".resConfUnit1", block.resConfUnit1, x1, extra=x0) if block.has_residual else x0
+        out = self._rcu(name + ".resConfUnit2", block.resConfUnit2, out)
+        out = ops.conv1x1_f32(out, *self._conv(name + ".out_conv", block.out_conv))
+        return ops.upsample_bilinear_ac_f32(out, size[0], size[1])
+
+    def _forward_impl(self, aggregated_tokens_list, hw, patch_start_idx, s0, s1):
+        H, W = hw
+        ph, pw = H // self.patch_size, W // self.patch_size
+        feats = []
+        for i, layer_idx in enumerate(self.intermediate_layer_idx):
+            x = aggregated_tokens_list[layer_idx][:, s0:s1, patch_start_idx:].float()
+            B, S = x.shape[:2]
+            x = F.layer_norm(x.reshape(B * S, ph * pw, x.shape[-1]), self.norm.normalized_shape, self.norm.weight.float(), self.norm.bias.float(),
+                             self.norm.eps).contiguous()
+            x = ops.conv1x1_f32(x, *self._conv(f"projects.{i}", self.projects[i])).reshape(B * S, ph, pw, -1)
+            if self.pos_embed:
+                x = ops.upsample_bilinear_ac_f32(x, ph, pw, self._embed(pw, ph, x.shape[-1], W / H, x.device))
+            layer = self.resize_layers[i]
+            if isinstance(layer, nn.ConvTranspose2d):
+                k, oc = layer.kernel_size[0], layer.out_channels
+                x = ops.conv1x1_f32(x, *self._deconv(f"resize_layers.{i}", layer)).reshape(B * S, ph, pw, k, k, oc)
+                x = x.permute(0, 1, 3, 2, 4, 5).reshape(B * S, ph * k, pw * k, oc).contiguous()
+            elif isinstance(layer, nn.Conv2d):
+                x = ops.conv3x3_f32(x, *self._conv(f"resize_layers.{i}", layer), stride=2)
+            feats.append(x)
+        sc = self.scratch
+        rn = [ops.conv3x3_f32(f, self._conv(f"layer{i + 1}_rn", getattr(sc, f"layer{i + 1}_rn"))[0]) for i, f in enumerate(feats)]
+        del feats
+        out = self._fuse("refinenet4", sc.refinenet4, rn[3], None, rn[2].shape[1:3])
+        out = self._fuse("refinenet3", sc.refinenet3, out, rn[2], rn[1].shape[1:3])
+        out = self._fuse("refinenet2", sc.refinenet2, out, rn[1], rn[0].shape[1:3])
+        out = self._fuse("refinenet1", sc.refinenet1, out, rn[0], (2 * rn[0].shape[1], 2 * rn[0].shape[2]))
+        del rn
+        out = ops.conv3x3_f32(out, *self._conv("output_conv1", sc.output_conv1))
+        Ho, Wo = ph * self.patch_size, pw * self.patch_size
+        w1, b1 = self._conv("output_conv2.0", sc.output_conv2[0])
+        w2, b2 = self._packed.get("output_conv2.2", [sc.output_conv2[2].weight, sc.output_conv2[2].bias],
+                                  lambda: (sc.output_conv2[2].weight.detach().float().reshape(-1, 32).contiguous(),
+                                           sc.output_conv2[2].bias.detach().float().contiguous()))
+        tabs = self._embed(Wo, Ho, out.shape[-1], W / H, out.device) if self.pos_embed else None
+        preds, conf = ops.dpt_tail_f32(out, Ho, Wo, w1, b1, w2, b2, activation=self.activation, tabs=tabs)
+        return preds.view(B, S, Ho, Wo, -1), conf.view(B, S, Ho, Wo)
+
+
+class VGGT(nn.Module):
+    """vggt/models/vggt.py:17-96 without the track head: `forward(images [S,3,H,W] | [B,S,3,H,W] in [0,1]) -> {pose_enc, pose_enc_list, depth,
+    depth_conf, world_points, world_points_conf, images (eval mode)}`.  The aggregator runs in whatever precision the caller set (bf16
+    autocast in the scorer); the heads compute in fp32 as upstream (autocast off, :65).  `patch_embed` as the Aggregator takes it;
+    aggregator_kwargs / camera_kwargs / dpt_kwargs reach the three constructors (reduced configurations; VGGT-1B needs none).  `track_head.*` keys of a reference checkpoint are dropped on load."""
+
+    def __init__(self, img_size=518, patch_size=14, embed_dim=1024, enable_camera=True, enable_point=True, enable_depth=True, enable_track=False,
+                 patch_embed="dinov2_vitl14_reg", aggregator_kwargs=None, camera_kwargs=None, dpt_kwargs=None):
+        super().__init__()
+        if enable_track:
+            raise NotImplementedError("the track head is not built (the scorer never queries tracks)")
+        self.aggregator = Aggregator(img_size=img_size, patch_size=patch_size, embed_dim=embed_dim, patch_embed=patch_embed, **(aggregator_kwargs or {}))
+        ck, dk = camera_kwargs or {}, dpt_kwargs or {}
+        self.camera_head = CameraHead(dim_in=2 * embed_dim, **ck) if enable_camera else None
+        self.point_head = DPTHead(dim_in=2 * embed_dim, patch_size=patch_size, output_dim=4, activation="inv_log", conf_activation="expp1", **dk) \
+            if enable_point else None
+        self.depth_head = DPTHead(dim_in=2 * embed_dim, patch_size=patch_size, output_dim=2, activation="exp", conf_activation="expp1", **dk) \
+            if enable_depth else None
+        self.track_head = None
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("track_head.")}, strict=strict, **kw)
+
+    def run_heads(self, aggregated_tokens_list, images, patch_start_idx):
+        predictions = {}
+        if self.camera_head is not None:
+            pose_enc_list = self.camera_head(aggregated_tokens_list)
+            predictions["pose_enc"], predictions["pose_enc_list"] = pose_enc_list[-1], pose_enc_list
+        if self.depth_head is not None:
+            predictions["depth"], predictions["depth_conf"] = self.depth_head(aggregated_tokens_list, images=images, patch_start_idx=patch_start_idx)
+        if self.point_head is not None:
+            predictions["world_points"], predictions["world_points_conf"] = self.point_head(aggregated_tokens_list, images=images,
+                                                                                            patch_start_idx=patch_start_idx)
+        return predictions
+
+    def forward(self, images, query_points=None):
+        if query_points is not None:
+            raise NotImplementedError("query_points need the track head, which is not built")
+        if images.ndim == 4:
+            images = images.unsqueeze(0)
+        aggregated_tokens_list, patch_start_idx = self.aggregator(images)
+        predictions = self.run_heads(aggregated_tokens_list, images, patch_start_idx)
+        if not self.training:
+            predictions["images"] = images
+        return predictions

@@ -108,36 +108,20 @@ int32_t vgpa_qknorm_rope_bwd(const void* dq_out, const void* dk_out, const void*
 /* ---- 3D full attention, non-causal, head_dim 64 (F.scaled_dot_product_attention in the same processor) ----------
  * CONTRACT: q is PRE-MULTIPLIED by scale*log2(e) in every entry point below; dq is the gradient w.r.t. the unscaled q.
  * lse2 = log2 sum_k exp2(q.k), fp32 [B,H,S]; delta = rowsum(dO * O), fp32 [B,H,S]. */
-int32_t vgpa_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
-                      const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H,
-                      int64_t S, int64_t head_dim, float scale, vgpa_stream_t stream);
-/* The same with a caller-owned workspace (>= vgpa_attn_fwd_workspace_bytes): when the number of (head, 256-row strip)
- * tasks leaves a mostly empty last scheduling round on the device, those leftover tasks are cut into key-range chunks
- * (second small launch + merge) instead.  split_mode: -1 automatic, 0 never, k >= 2 force k chunks for every task. */
+/* The forward.  workspace: NULL (a single launch), or caller-owned with >= vgpa_attn_fwd_workspace_bytes: when the number of
+ * (head, 256-row strip) tasks leaves a mostly empty last scheduling round on the device, those leftover tasks are cut into
+ * key-range chunks (second small launch + merge) instead.  split_mode: -1 automatic, 0 never, k >= 2 force k chunks for every task. */
 size_t vgpa_attn_fwd_workspace_bytes(int64_t B, int64_t H, int64_t S);
 int32_t vgpa_attn_fwd_ws(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
                          const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H,
                          int64_t S, int64_t head_dim, float scale, int32_t split_mode, void* workspace, size_t ws_bytes,
                          vgpa_stream_t stream);
-size_t vgpa_attn_bwd_workspace_bytes(int64_t B, int64_t H, int64_t S);
-int32_t vgpa_attn_bwd_delta(const void* o, const void* d_o, const int64_t* o_strides, const int64_t* do_strides, float* delta,
-                            int64_t B, int64_t H, int64_t S, int64_t head_dim, vgpa_stream_t stream);
-/* The same from the output as the forward's residual tensor completes it (o_res / res_kind as vgpa_attn_fwd_w1_res wrote them; o_res may be
- * NULL).  delta stands for rowsum(P o dP), which equals rowsum(dO o O) for the UNROUNDED O only; from the bf16 O alone (what flash-attention
+/* Backward, step 1: delta = rowsum(dO o O), of the output as the forward's residual tensor completes it (o_res / res_kind as
+ * vgpa_attn_fwd_w1_res wrote them; o_res may be NULL: from o alone).  delta stands for rowsum(P o dP), which equals rowsum(dO o O) for the UNROUNDED O only; from the bf16 O alone (what flash-attention
  * backwards, torch's included, do) every row's dS stops summing to zero and dQ picks up a coherent error. */
 int32_t vgpa_attn_bwd_delta_res(const void* o, const void* o_res, int32_t res_kind, const void* d_o, const int64_t* o_strides, const int64_t* ores_strides,
                                 const int64_t* do_strides, float* delta, int64_t B, int64_t H, int64_t S, int64_t head_dim,
                                 vgpa_stream_t stream);
-int32_t vgpa_attn_bwd_dkv(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
-                          void* dk, void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                          const int64_t* do_strides, const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H,
-                          int64_t S, int64_t head_dim, float scale, vgpa_stream_t stream);
-int32_t vgpa_attn_bwd_dq(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
-                         void* dq, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                         const int64_t* do_strides, const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim,
-                         float scale, vgpa_stream_t stream);
-/* fused alternative to bwd_dkv + bwd_dq (5 instead of 7 matrix products per score block): dK, dV as above, dQ added with
- * fp32 atomics into dq_f32 = fp32 [B,H,S,64] contiguous, which the CALLER MUST ZERO first. */
 /* dQ on the "w1" structure (attention_w1.hip: one wave per SIMD, 512-register waves, LDS-DMA ring, hand-scheduled main
  * loop); arguments and results as vgpa_attn_bwd_dq_ws (workspace >= vgpa_attn_bwd_split_workspace_bytes, may be NULL). */
 int32_t vgpa_attn_bwd_dq_w1(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
@@ -151,11 +135,8 @@ int32_t vgpa_attn_bwd_dq_w1(const void* q, const void* k, const void* v, const v
  * weights (the ones the PV product multiplies: O is an exact convex combination of V rows); it differs from the exact value by a row's weighted mean rounding error
  * (<= 2^-8 relative, i.e. 5.6e-3 in log2 units, on a one-hot row; ~ 2e-3 / sqrt(n) on a row spread over n keys: tests/attn_tol.py). */
 size_t vgpa_attn_fwd_w1_workspace_bytes(int64_t B, int64_t H, int64_t S);
-int32_t vgpa_attn_fwd_w1(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
-                         const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H, int64_t S,
-                         int64_t head_dim, float scale, int32_t split_mode, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
-/* vgpa_attn_fwd_w1 that also writes what the bf16 rounding of the output dropped ([B,H,S,64] view o_res with its own ELEMENT strides; NULL = plain
- * vgpa_attn_fwd_w1), for the backward's delta (vgpa_attn_bwd_prep_w1_res / vgpa_attn_bwd_delta_res).  res_kind:
+/* It also writes what the bf16 rounding of the output dropped ([B,H,S,64] view o_res with its own ELEMENT strides; NULL = not
+ * written), for the backward's delta (vgpa_attn_bwd_prep_w1_res / vgpa_attn_bwd_delta_res).  res_kind:
  *   VGPA_RES_BF16 (1)  bf16 elements: O_fp32 - bf16(O);
  *   VGPA_RES_8    (2)  uint8 elements: eight further mantissa bits, 128 + clamp(rint((O_fp32 - bf16(O)) * 2^8 / ulp(bf16(O))), -128, 127).
  * Either way (o, o_res) carries the output to 2^-17 relative; the 8-bit form costs half the bytes (1 per output element). */
@@ -166,18 +147,16 @@ int32_t vgpa_attn_fwd_w1_res(const void* q, const void* k, const void* v, void* 
                              const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, const int64_t* ores_strides,
                              int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode, void* workspace,
                              size_t ws_bytes, vgpa_stream_t stream);
-/* Redo accounting of vgpa_attn_fwd_w1 / _w1_res: after the call the workspace holds, behind its first B*H uint32 words (max_k |k|^2 per head), one int32 per
- * (batch, head, 256-row strip): non-zero = the strip held a row outside what the shifted loop represents (see vgpa_attn_fwd_w1) and it was redone by the online-softmax kernel inside the same call.  Results never depend on it; time does.
+/* Redo accounting of vgpa_attn_fwd_w1_res: after the call the workspace holds, behind its first B*H uint32 words (max_k |k|^2 per head), one int32 per
+ * (batch, head, 256-row strip): non-zero = the strip held a row outside what the shifted loop represents (see above) and it was redone by the online-softmax kernel inside the same call.  Results never depend on it; time does.
  * vgpa_attn_fwd_online_res: same arguments, results and workspace, EVERY strip on the online-softmax kernel -- the faster call when most strips would be flagged
  * (one sweep instead of two).  The host side (transformer.AttentionCore) reads the count on a layer's first calls and switches that layer. */
 int32_t vgpa_attn_fwd_online_res(const void* q, const void* k, const void* v, void* o, void* o_res, int32_t res_kind, float* lse2, const int64_t* q_strides,
                                  const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, const int64_t* ores_strides,
                                  int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode, void* workspace,
                                  size_t ws_bytes, vgpa_stream_t stream);
-/* w1 backward, step 1 and step 2: vgpa_attn_bwd_prep_w1 writes delta (fp32 [B,H,S], as vgpa_attn_bwd_delta) and the statistics
- * planes stats = fp32 [B,H,2,S] = {-lse2, -delta}; vgpa_attn_bwd_dkv_w1 = vgpa_attn_bwd_dkv_ws on the w1 structure, reading `stats`. */
-int32_t vgpa_attn_bwd_prep_w1(const void* o, const void* d_o, const float* lse2, const int64_t* o_strides, const int64_t* do_strides,
-                              float* delta, float* stats, int64_t B, int64_t H, int64_t S, int64_t head_dim, vgpa_stream_t stream);
+/* w1 backward, step 1 and step 2: vgpa_attn_bwd_prep_w1_res writes delta (fp32 [B,H,S], as vgpa_attn_bwd_delta_res; o_res may be NULL) and the
+ * statistics planes stats = fp32 [B,H,2,S] = {-lse2, -delta}; vgpa_attn_bwd_dkv_w1 = vgpa_attn_bwd_dkv_ws on the w1 structure, reading `stats`. */
 int32_t vgpa_attn_bwd_prep_w1_res(const void* o, const void* o_res, int32_t res_kind, const void* d_o, const float* lse2, const int64_t* o_strides,
                                   const int64_t* ores_strides, const int64_t* do_strides, float* delta, float* stats, int64_t B, int64_t H,
                                   int64_t S, int64_t head_dim, vgpa_stream_t stream);
@@ -185,8 +164,8 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
                              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
                              const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim,
                              float scale, int32_t split_mode, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
-/* vgpa_attn_bwd_dkv / _dq with a caller-owned workspace (>= vgpa_attn_bwd_split_workspace_bytes, may be shared by the two
- * calls): the leftover tasks of a mostly empty last scheduling round are cut into chunks along the streamed axis (second
+/* Backward, step 2 (dK, dV from lse2 / delta) and step 3 (dQ).  workspace: NULL (a single launch each), or caller-owned with
+ * >= vgpa_attn_bwd_split_workspace_bytes (may be shared by the two calls): the leftover tasks of a mostly empty last scheduling round are cut into chunks along the streamed axis (second
  * small launch + fp32 merge), as in vgpa_attn_fwd_ws.  split_mode: -1 automatic, 0 never, k >= 2 force k chunks. */
 size_t vgpa_attn_bwd_split_workspace_bytes(int64_t B, int64_t H, int64_t S);
 int32_t vgpa_attn_bwd_dkv_ws(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
@@ -206,24 +185,17 @@ int32_t vgpa_attn_bwd_fused(const void* q, const void* k, const void* v, const v
                             const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
                             vgpa_stream_t stream);
 #endif
-int32_t vgpa_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse2, void* dq,
-                      void* dk, void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                      const int64_t* o_strides, const int64_t* do_strides, const int64_t* dq_strides, const int64_t* dk_strides,
-                      const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, void* workspace,
-                      size_t ws_bytes, vgpa_stream_t stream);
 
 /* ---- LoRA A.B contractions (peft Linear.forward `lora_B(lora_A(x)) * scaling` and its backward for the adapters of
  * train/CogVideoX-5B/03_train.py:102-106).  bf16 row-major operands with explicit row strides (elements).
  *   down  : T[M,R]  = X[M,K] A[R,K]^T                     K % 64 == 0, R <= 256
  *   up_add: Y[M,N]  = (accumulate ? Y : 0) + s * T[M,rp] Bw[N,rp]^T   rp in {16,32,48,64,96,128,192}, N % 8 == 0
- *   grad  : G[P,Q] += s * U[M,P]^T V[M,Q]                 G fp32, caller-zeroed (fp32 atomics) */
+ *   grad  : G[P,Q]  = s * U[M,P]^T V[M,Q]                 G fp32, overwritten; P % 8 == 0, Q % 8 == 0 */
 int32_t vgpa_lora_down(const void* X, int64_t ldx, const void* A, void* T, int64_t ldt, int64_t M, int64_t K, int64_t R,
                        vgpa_stream_t stream);
 int32_t vgpa_lora_up_add(void* Y, int64_t ldy, const void* T, int64_t ldt, const void* Bw, int64_t ldb, float s, int64_t M,
                          int64_t N, int64_t rp, int32_t accumulate, vgpa_stream_t stream);
-int32_t vgpa_lora_grad(const void* U, int64_t ldu, const void* V, int64_t ldv, float* G, int64_t ldg, float s, int64_t M,
-                       int64_t P, int64_t Q, vgpa_stream_t stream);
-/* the same product, bit-reproducible: per-row-range partials in the caller's workspace + an ordered merge; G is overwritten */
+/* grad is bit-reproducible: per-row-range partials in the caller's workspace (>= vgpa_lora_grad_workspace_bytes) + an ordered merge */
 size_t vgpa_lora_grad_workspace_bytes(int64_t M, int64_t P, int64_t Q);
 int32_t vgpa_lora_grad_ws(const void* U, int64_t ldu, const void* V, int64_t ldv, float* G, int64_t ldg, float s, int64_t M,
                           int64_t P, int64_t Q, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
@@ -260,7 +232,7 @@ int32_t vgpa_attn128_fwd(const void* q, const void* k, const void* v, void* o, f
  * with the scales -- and a per-tile, per-row power of two for the softmax weights -- on the instruction's E8M0 operands; row sums and lse2 stay fp32.
  * Arguments and results as vgpa_attn128_fwd; the workspace (>= vgpa_attn128_fwd_f8_workspace_bytes, 256-byte aligned) is REQUIRED and is scratch.
  * The softmax shift of a row is M' = b - n, b = |q8 row| max|k8 row| and n = floor(max(0, b - (m_s + 64))) with m_s the row's maximum over 64 keys spread evenly
- * over the sweep (as vgpa_attn_fwd_w1; an INTEGER step off the bound, so the e4m3 bits of the weights do not depend on it); 256-row strips with a row it cannot
+ * over the sweep (as vgpa_attn_fwd_w1_res; an INTEGER step off the bound, so the e4m3 bits of the weights do not depend on it); 256-row strips with a row it cannot
  * represent (row sum outside [2^-100, 2^118), M' > 1024, a non-finite accumulator) are redone by the bf16 running-max kernel inside the call.
  * Forward only.  q_deq / k_deq / v_deq (optional, all three or none; bf16 [B,H,S,128] views with their stride triples): the operands the products really ran
  * on, dequantised EXACTLY (an e4m3 value times a power of two is a bf16 number): k8 2^ek, v8 2^ev and q8 2^eq -- the query PRE-SCALED by scale * log2 e.
@@ -367,12 +339,6 @@ int32_t vgpa_project_points(const float* pc, const float* colors, const float* c
                             const float* conf_thr_dev /* device fp32[1] or NULL: overrides conf_thr */, const float* K,
                             const float* E, int32_t e_rows, int64_t N, int64_t T, int64_t H, int64_t W, uint8_t* canvas,
                             float* out_f, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
-/* MSEMetric.compute, metrics/mse.py:14-54.  dtype 0 f32 / 2 u8; layout 0 [T,C,H,W] / 1 [T,H,W,C]; is_tensor selects
- * the torch.Tensor vs numpy range heuristics. */
-size_t vgpa_frame_mse_workspace_bytes(void);
-int32_t vgpa_frame_mse(const void* gt, int32_t gt_dtype, int32_t gt_layout, int32_t gt_is_tensor, const void* rep,
-                       int32_t rep_dtype, int32_t rep_layout, int32_t rep_is_tensor, int64_t T, int64_t C, int64_t H,
-                       int64_t W, float* out, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
 /* compute_motion_score_vectorized, metrics/consistency_score.py:8-40 */
 int32_t vgpa_motion_score(const float* E, int32_t e_rows, int64_t T, float* out, vgpa_stream_t stream);
 /* kornia find_fundamental (8-point) + sampson_epipolar_distance as used by metrics/epipolar.py:197-213 */
@@ -386,7 +352,9 @@ size_t vgpa_conf_threshold_workspace_bytes(void);
 int32_t vgpa_conf_threshold(const float* conf, int64_t N, float conf_thres, float* thr_out, void* workspace, size_t ws_bytes,
                             vgpa_stream_t stream);
 /* MSEMetric / PSNRMetric.compute incl. the bilinear-resize branch, metrics/mse.py:14-29,56-80: rep [T,C,H2,W2] is resized to
- * gt's [H,W] (F.interpolate bilinear, align_corners=False).  psnr 0: mse; 1: 10 log10(1/mse), 100 when mse == 0. */
+ * gt's [H,W] (F.interpolate bilinear, align_corners=False).  psnr 0: mse; 1: 10 log10(1/mse), 100 when mse == 0.
+ * dtype 0 f32 / 2 u8; layout 0 [T,C,H,W] / 1 [T,H,W,C]; is_tensor selects the torch.Tensor vs numpy range heuristics
+ * (metrics/mse.py:31-54). */
 size_t vgpa_frame_metric_workspace_bytes(void);
 int32_t vgpa_frame_metric(const void* gt, int32_t gt_dtype, int32_t gt_layout, int32_t gt_is_tensor, const void* rep,
                           int32_t rep_dtype, int32_t rep_layout, int32_t rep_is_tensor, int64_t T, int64_t C, int64_t H,

@@ -54,7 +54,9 @@ def test_library_reads_no_environment_and_product_sources_hold_no_variant_code()
 def test_pure_host_queries():
     from videogpa_amd import _lib
     assert _lib.query("vgpa_dpo_loss_workspace_bytes", 3) == 3 * 256 * 4 * 8
-    assert _lib.query("vgpa_attn_bwd_workspace_bytes", 2, 48, 17776) == 2 * 48 * 17776 * 4
+    # kmax word per (batch, head) + one redo flag per 256-row strip, at the cfg5 self-attention shape (2 x 24 heads, 18 480 tokens -> 73 strips)
+    assert _lib.query("vgpa_attn128_fwd_workspace_bytes", 2, 24, 18480) == 4 * 2 * 24 + 4 * 2 * 24 * 73
+    assert _lib.query("vgpa_attn128_fwd_workspace_bytes", 0, 24, -1) == 0
     assert _lib.query("vgpa_grad_norm_workspace_bytes") == 1024 * 8
 
 

@@ -452,7 +452,7 @@ def test_attention_fwd_key_range_split_matches_single_launch(ops, S, split):
     assert (o1.float() - o0.float()).abs().max().item() < 0.02          # both round the same value to bf16: <= 1 ulp apart
     w = torch.softmax(q.double() @ k.double().transpose(-1, -2) / 8.0, -1)
     tol = lse2_tol(w, lse0.double().cpu())
-    assert ((lse1 - lse0).abs().double().cpu() <= 2.0 * tol + 1e-3).all()      # each launch rounds its own weights (the chunks shift by their own M')
+    assert ((lse1 - lse0).abs().double().cpu() <= 2.0 * tol + 1e-3).all()      # each launch rounds its own weights (every chunk of a row shifts by the same sampled M')
 
 
 @pytest.mark.parametrize("S,split", [(1000, 4), (1100, 7), (641, 3)])
@@ -487,9 +487,9 @@ def test_cabi_rejects_bad_arguments(ops):
     import ctypes
     s3 = (ctypes.c_int64 * 3)(64, 64, 64)
     f = torch.zeros(8, dtype=torch.float32, device="cuda")
-    assert lib.vgpa_attn_fwd(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), f.data_ptr(), s3, s3, s3, s3, 1, 1, 1, 128, 0.1, st) == -1   # head_dim
+    assert lib.vgpa_attn_fwd_ws(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), f.data_ptr(), s3, s3, s3, s3, 1, 1, 1, 128, 0.1, 0, None, 0, st) == -1   # head_dim
     bad = (ctypes.c_int64 * 3)(64, 64, 60)
-    assert lib.vgpa_attn_fwd(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), f.data_ptr(), bad, s3, s3, s3, 1, 1, 1, 64, 0.1, st) == -1   # stride
+    assert lib.vgpa_attn_fwd_ws(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), f.data_ptr(), bad, s3, s3, s3, 1, 1, 1, 64, 0.1, 0, None, 0, st) == -1   # stride
     ws = torch.zeros(16, dtype=torch.uint8, device="cuda")
     assert lib.vgpa_dpo_loss_fwd(*([x.data_ptr()] * 6), 1, 64, 64, 64, 64, 1, 1.0, 0.0, 0, 0, f.data_ptr(), f.data_ptr(), None, ws.data_ptr(), 16, st) == -3
     with pytest.raises(ValueError, match="Unknown loss type"):

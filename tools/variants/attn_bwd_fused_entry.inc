@@ -6,8 +6,8 @@ int32_t vgpa_attn_bwd_fused(const void* q, const void* k, const void* v, const v
                             const int64_t* v_strides, const int64_t* do_strides, const int64_t* dk_strides, const int64_t* dv_strides,
                             int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, hipStream_t stream) {
     if (!q || !k || !v || !d_o || !lse2 || !delta || !dq_f32 || !dk || !dv || !bwd_common_ok(B, H, S, head_dim)) return VGPA_ERR_INVALID;
-    if (!SOK(q_strides) || !SOK(k_strides) || !SOK(v_strides) || !SOK(do_strides) || !SOK(dk_strides) || !SOK(dv_strides) || !al16(q) ||
-        !al16(k) || !al16(v) || !al16(d_o) || !al16(dk) || !al16(dv))
+    if (!view_ok(q_strides, B, H, S, HD) || !view_ok(k_strides, B, H, S, HD) || !view_ok(v_strides, B, H, S, HD) || !view_ok(do_strides, B, H, S, HD) ||
+        !view_ok(dk_strides, B, H, S, HD) || !view_ok(dv_strides, B, H, S, HD) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dk) || !al16(dv))
         return VGPA_ERR_INVALID;
     const int n_t = (int)((S + FUSED_KEYS - 1) / FUSED_KEYS);
     VGPA_LAUNCH(attn_bwd_fused_kernel, dim3((unsigned)((int64_t)n_t * B * H)), dim3(512), 0, stream, (const bf16_t*)q, (const bf16_t*)k,

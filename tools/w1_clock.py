@@ -24,7 +24,7 @@ for split in (0,):
     for it in range(3):
         a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         a.record()
-        _lib.call("vgpa_attn_fwd_w1", q, k, v, o, lse, st(q), st(k), st(v), st(ov), B, H, S, 64, 0.125, split, ws, wsb, torch.cuda.current_stream().cuda_stream)
+        _lib.call("vgpa_attn_fwd_w1_res", q, k, v, o, None, 0, lse, st(q), st(k), st(v), st(ov), None, B, H, S, 64, 0.125, split, ws, wsb, torch.cuda.current_stream().cuda_stream)
         b.record()
         torch.cuda.synchronize()
     ntask = (S + 255) // 256 * B * H

@@ -33,21 +33,14 @@ SIGNATURES = {
     "vgpa_gelu_tanh_bwd": (I32, [P, P, I64, P, P]),
     "vgpa_qknorm_rope_fwd": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, F32, I32, P]),
     "vgpa_qknorm_rope_bwd": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, I32, P]),
-    "vgpa_attn_fwd": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, P]),
     "vgpa_attn_fwd_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_attn_fwd_ws": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
-    "vgpa_attn_bwd_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_grad_norm_workspace_bytes": (SZ, []),
     "vgpa_grad_norm": (I32, [P, I64, F32, P, P, SZ, P]),
     "vgpa_adamw_step": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, F32, P, P]),
-    "vgpa_attn_bwd_delta": (I32, [P, P, P, P, P, I64, I64, I64, I64, P]),
     "vgpa_attn_bwd_delta_res": (I32, [P, P, I32, P, P, P, P, P, I64, I64, I64, I64, P]),
-    "vgpa_attn_bwd_dkv": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, P]),
-    "vgpa_attn_bwd_dq": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, P]),
     "vgpa_attn_bwd_dq_w1": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_attn_fwd_w1_workspace_bytes": (SZ, [I64, I64, I64]),
-    "vgpa_attn_fwd_w1": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
-    "vgpa_attn_bwd_prep_w1": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, P]),
     "vgpa_attn_bwd_prep_w1_res": (I32, [P, P, I32, P, P, P, P, P, P, P, I64, I64, I64, I64, P]),
     "vgpa_attn_fwd_w1_res": (I32, [P, P, P, P, P, I32, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_attn_fwd_online_res": (I32, [P, P, P, P, P, I32, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
@@ -55,10 +48,8 @@ SIGNATURES = {
     "vgpa_attn_bwd_split_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_attn_bwd_dkv_ws": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_attn_bwd_dq_ws": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
-    "vgpa_attn_bwd": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, P, SZ, P]),
     "vgpa_lora_down": (I32, [P, I64, P, P, I64, I64, I64, I64, P]),
     "vgpa_lora_up_add": (I32, [P, I64, P, I64, P, I64, F32, I64, I64, I64, I32, P]),
-    "vgpa_lora_grad": (I32, [P, I64, P, I64, P, I64, F32, I64, I64, I64, P]),
     "vgpa_lora_grad_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_lora_grad_ws": (I32, [P, I64, P, I64, P, I64, F32, I64, I64, I64, P, SZ, P]),
     "vgpa_lora_ext_refresh": (I32, [P, P, F32, I64, I64, I64, P, P, I64, P, I64, P, P]),
@@ -99,8 +90,6 @@ SIGNATURES = {
     "vgpa_mvcs": (I32, [P, P, I32, P, I32, I64, I64, I64, P, P, SZ, P]),
     "vgpa_unproject_depth": (I32, [P, P, P, I32, I64, I64, I64, P, P]),
     "vgpa_pose_decode": (I32, [P, I64, F32, F32, P, P, P]),
-    "vgpa_frame_mse_workspace_bytes": (SZ, []),
-    "vgpa_frame_mse": (I32, [P, I32, I32, I32, P, I32, I32, I32, I64, I64, I64, I64, P, P, SZ, P]),
     "vgpa_motion_score": (I32, [P, I32, I64, P, P]),
     "vgpa_epipolar_sampson": (I32, [P, P, P, I64, P, P, P]),
     "vgpa_conv3x3_f32": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),

@@ -56,7 +56,7 @@
 #endif  // VGPA_VARIANTS
 
 // =====================================================================================================
-// Forward, software-pipelined (what vgpa_attn_fwd launches; the kernel above is kept as -DFWD_V1 for the phase-stamp
+// Forward, software-pipelined (what vgpa_attn_fwd_ws launches; the kernel above is kept as -DFWD_V1 for the phase-stamp
 // diagnostics and as the reference point of DESIGN.md 4.1).  The tile loop body is ONE basic block in which independent work of
 // neighbouring half-tiles (32 keys) can overlap inside a wave:
 //     sB = QK^T(t, keys 32..63)   ||  pA = exp2(sA)            sA = scores of (t, keys 0..31), made one step earlier
@@ -834,7 +834,10 @@ __global__ __launch_bounds__(256) void attn_dkv_merge_kernel(const float* __rest
 #ifndef FWD_QB
 #define FWD_QB 2   // query blocks (of 32 rows) per wave in the forward kernel
 #endif
-#define SOK(st) (stride_ok(st) && range_ok(st, B, H, S))
+#define FWD_MAX_SPLIT 16
+#define BWD_MAX_SPLIT 16
+#define DKV_PART_FLOATS (2 * WG_ROWS * HD)
+#define DQ_PART_FLOATS (DQ_QB * WG_ROWS * HD)
 
 // Redo pass behind the w1 forward (attention_w1.hip): the online-softmax kernel over every 256-row strip whose flag is set.
 int32_t vgpa_internal_attn_fwd_redo(const void* q, const void* k, const void* v, void* o, float* lse2, TStride sq, TStride sk, TStride sv, TStride so,
@@ -845,28 +848,34 @@ int32_t vgpa_internal_attn_fwd_redo(const void* q, const void* k, const void* v,
     return VGPA_OK;
 }
 
+static inline bool bwd_common_ok(int64_t B, int64_t H, int64_t S, int64_t head_dim) {
+    return head_dim == HD && B > 0 && H > 0 && S > 0 && S <= (1 << 24) && (int64_t)((S + WG_ROWS - 1) / WG_ROWS) * B * H <= 0x7fffffff;
+}
+
 extern "C" {
 
 // All tensors are bf16 views [B, H, S, 64] given by element strides {batch, head, token} (last dim contiguous,
 // strides multiples of 8, base pointers 16-byte aligned).  lse2 / delta are fp32 [B, H, S] contiguous.
 // CONTRACT: q holds the queries PRE-MULTIPLIED by scale*log2(e) (vgpa_qknorm_rope_fwd writes them that way through
-// q_out_scale), in all four entry points; `scale` is still the softmax scale (used for the dQ / dK multipliers).
+// q_out_scale), in all entry points; `scale` is still the softmax scale (used for the dQ / dK multipliers).
 // dq is the gradient w.r.t. the UNscaled query.
-#define FWD_MAX_SPLIT 16
 
 size_t vgpa_attn_fwd_workspace_bytes(int64_t B, int64_t H, int64_t S) {
-    // worst case of split_plan: (leftover tasks) x (chunks) <= slots in automatic mode; forced mode (tests) splits every task
     const int64_t n_qt = (S + 255) / 256, tasks = n_qt * B * H;
-    int64_t parts = wg_slots();
-    if (tasks * FWD_MAX_SPLIT < parts) parts = tasks * FWD_MAX_SPLIT;
-    return (size_t)parts * FWD_PART_FLOATS * sizeof(float);
+    return (size_t)max_split_parts(tasks, FWD_MAX_SPLIT, wg_slots()) * FWD_PART_FLOATS * sizeof(float);
 }
 
-static int32_t attn_fwd_impl(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
-                             const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H, int64_t S,
-                             int64_t head_dim, int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
+// The forward.  With a workspace (vgpa_attn_fwd_workspace_bytes; NULL: a single launch) the launcher cuts the leftover tasks of a
+// partially filled last scheduling round into key-range chunks (a second small launch + a merge).  split_mode: -1 automatic, 0 never,
+// k >= 2 force k chunks for every task.
+int32_t vgpa_attn_fwd_ws(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
+                         const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H, int64_t S,
+                         int64_t head_dim, float scale, int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
+    (void)scale;
+    if (workspace && !al16(workspace)) return VGPA_ERR_INVALID;
     if (!q || !k || !v || !o || !lse2 || head_dim != HD || B <= 0 || H <= 0 || S <= 0 || S > (1 << 24)) return VGPA_ERR_INVALID;
-    if (!SOK(q_strides) || !SOK(k_strides) || !SOK(v_strides) || !SOK(o_strides)) return VGPA_ERR_INVALID;
+    if (!view_ok(q_strides, B, H, S, HD) || !view_ok(k_strides, B, H, S, HD) || !view_ok(v_strides, B, H, S, HD) || !view_ok(o_strides, B, H, S, HD))
+        return VGPA_ERR_INVALID;
     if (!al16(q) || !al16(k) || !al16(v) || !al16(o)) return VGPA_ERR_INVALID;
 #ifdef VGPA_VARIANTS   // measured-slower experiments / diagnostics live in tools/variants/ (variant builds only)
 #include "attn_fwd_pp_dispatch.inc"
@@ -876,26 +885,22 @@ static int32_t attn_fwd_impl(const void* q, const void* k, const void* v, void* 
     if (nblk > 0x7fffffff) return VGPA_ERR_INVALID;
 #ifndef FWD_V1   // product path: the software-pipelined kernel; -DFWD_V1 builds the three-block kernel (diagnostic hooks live there)
     if (FWD_NW * FWD_QB == 8) {   // 256 query rows per task either way
-        int64_t n_main = nblk;
-        int nsplit = 1;
-        if (workspace) split_plan(nblk, (int)((S + TILE - 1) / TILE), split_mode, FWD_MAX_SPLIT, &n_main, &nsplit);
-        const int64_t n_tail = nblk - n_main;
-        if (n_tail > 0 && ws_bytes < (size_t)n_tail * nsplit * FWD_PART_FLOATS * sizeof(float)) {
-            if (split_mode >= 2) return VGPA_ERR_WORKSPACE;
-            n_main = nblk;   // automatic mode: fall back to the single launch
-        }
-        if (n_main > 0) {
-            VGPA_LAUNCH((attn_fwd_pipe_kernel<FWD_QB, FWD_NW, false>), dim3((unsigned)n_main), dim3(64 * FWD_NW), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
-                        (const bf16_t*)v, (bf16_t*)o, lse2, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)S, (int)H, n_qt, 0, 1,
-                        (float*)nullptr);
+        TailSplit p;
+        const int32_t rc = plan_tail_split(nblk, (int)((S + TILE - 1) / TILE), split_mode, FWD_MAX_SPLIT, 0, FWD_PART_FLOATS * sizeof(float), workspace,
+                                           ws_bytes, 0, &p);
+        if (rc) return rc;
+        if (p.n_main > 0) {
+            VGPA_LAUNCH((attn_fwd_pipe_kernel<FWD_QB, FWD_NW, false>), dim3((unsigned)p.n_main), dim3(64 * FWD_NW), 0, stream, (const bf16_t*)q,
+                        (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse2, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)S, (int)H,
+                        n_qt, 0, 1, (float*)nullptr);
             VGPA_CHECK_LAUNCH();
         }
-        if (n_main < nblk) {
-            VGPA_LAUNCH((attn_fwd_pipe_kernel<FWD_QB, FWD_NW, true>), dim3((unsigned)(n_tail * nsplit)), dim3(64 * FWD_NW), 0, stream, (const bf16_t*)q,
+        if (p.n_tail > 0) {
+            VGPA_LAUNCH((attn_fwd_pipe_kernel<FWD_QB, FWD_NW, true>), dim3((unsigned)(p.n_tail * p.nsplit)), dim3(64 * FWD_NW), 0, stream, (const bf16_t*)q,
                         (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse2, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)S,
-                        (int)H, n_qt, (int)n_main, nsplit, (float*)workspace);
+                        (int)H, n_qt, (int)p.n_main, p.nsplit, (float*)workspace);
             VGPA_CHECK_LAUNCH();
-            VGPA_LAUNCH(attn_fwd_merge_kernel, dim3((unsigned)(n_tail * 64)), dim3(256), 0, stream, (const float*)workspace, nsplit, (int)n_main, n_qt,
+            VGPA_LAUNCH(attn_fwd_merge_kernel, dim3((unsigned)(p.n_tail * 64)), dim3(256), 0, stream, (const float*)workspace, p.nsplit, (int)p.n_main, n_qt,
                         (bf16_t*)o, mk(o_strides), lse2, (int)S, (int)H);
             VGPA_CHECK_LAUNCH();
         }
@@ -909,38 +914,14 @@ static int32_t attn_fwd_impl(const void* q, const void* k, const void* v, void* 
 #endif
 }
 
-int32_t vgpa_attn_fwd(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
-                      const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H, int64_t S,
-                      int64_t head_dim, float scale, hipStream_t stream) {
-    (void)scale;
-    return attn_fwd_impl(q, k, v, o, lse2, q_strides, k_strides, v_strides, o_strides, B, H, S, head_dim, 0, nullptr, 0, stream);
-}
-
-// Same, with a workspace (vgpa_attn_fwd_workspace_bytes) that lets the launcher cut the leftover tasks of a partially filled
-// last scheduling round into key-range chunks (a second small launch + a merge).  split_mode: -1 automatic, 0 never, k >= 2
-// force k chunks for every task.
-int32_t vgpa_attn_fwd_ws(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
-                         const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H, int64_t S,
-                         int64_t head_dim, float scale, int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
-    (void)scale;
-    if (workspace && !al16(workspace)) return VGPA_ERR_INVALID;
-    return attn_fwd_impl(q, k, v, o, lse2, q_strides, k_strides, v_strides, o_strides, B, H, S, head_dim, split_mode, workspace, ws_bytes, stream);
-}
-
-// workspace: fp32 delta [B,H,S]  (vgpa_attn_bwd_workspace_bytes)
-size_t vgpa_attn_bwd_workspace_bytes(int64_t B, int64_t H, int64_t S) { return (size_t)B * H * S * sizeof(float); }
-
-static inline bool bwd_common_ok(int64_t B, int64_t H, int64_t S, int64_t head_dim) {
-    return head_dim == HD && B > 0 && H > 0 && S > 0 && S <= (1 << 24) && (int64_t)((S + WG_ROWS - 1) / WG_ROWS) * B * H <= 0x7fffffff;
-}
-
-// step 1 of the backward: delta[b,h,q] = sum_d dO * O  (_res: of the output as the forward's residual tensor completes it -- vgpa_attn_fwd_w1_res,
-// res_kind VGPA_RES_BF16 / VGPA_RES_8; o_res may be NULL)
+// step 1 of the backward: delta[b,h,q] = sum_d dO * O  -- of the output as the forward's residual tensor completes it when o_res is given
+// (vgpa_attn_fwd_w1_res, res_kind VGPA_RES_BF16 / VGPA_RES_8); o_res may be NULL
 int32_t vgpa_attn_bwd_delta_res(const void* o, const void* o_res, int32_t res_kind, const void* d_o, const int64_t* o_strides, const int64_t* ores_strides,
                                 const int64_t* do_strides, float* delta, int64_t B, int64_t H, int64_t S, int64_t head_dim, hipStream_t stream) {
-    if (!o || !d_o || !delta || !bwd_common_ok(B, H, S, head_dim) || !SOK(o_strides) || !SOK(do_strides) || !al16(o) || !al16(d_o))
+    if (!o || !d_o || !delta || !bwd_common_ok(B, H, S, head_dim) || !view_ok(o_strides, B, H, S, HD) || !view_ok(do_strides, B, H, S, HD) || !al16(o) ||
+        !al16(d_o))
         return VGPA_ERR_INVALID;
-    if (o_res && (!SOK(ores_strides) || !al16(o_res) || (res_kind != VGPA_RES_BF16 && res_kind != VGPA_RES_8))) return VGPA_ERR_INVALID;
+    if (o_res && (!view_ok(ores_strides, B, H, S, HD) || !al16(o_res) || (res_kind != VGPA_RES_BF16 && res_kind != VGPA_RES_8))) return VGPA_ERR_INVALID;
     const int64_t total = B * H * S;
     VGPA_LAUNCH(attn_delta_kernel, dim3((unsigned)((total * 8 + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)d_o, (const bf16_t*)o,
                        mk(do_strides), mk(o_strides), (int)S, (int)H, total, delta, o_res, o_res ? mk(ores_strides) : mk(o_strides),
@@ -948,150 +929,87 @@ int32_t vgpa_attn_bwd_delta_res(const void* o, const void* o_res, int32_t res_ki
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }
-int32_t vgpa_attn_bwd_delta(const void* o, const void* d_o, const int64_t* o_strides, const int64_t* do_strides, float* delta, int64_t B,
-                            int64_t H, int64_t S, int64_t head_dim, hipStream_t stream) {
-    return vgpa_attn_bwd_delta_res(o, nullptr, VGPA_RES_NONE, d_o, o_strides, nullptr, do_strides, delta, B, H, S, head_dim, stream);
+
+// Workspace of the two split steps below (shared by the two; they run one after the other on a stream).
+size_t vgpa_attn_bwd_split_workspace_bytes(int64_t B, int64_t H, int64_t S) {
+    const int64_t t_dkv = (S + WG_ROWS - 1) / WG_ROWS * B * H, t_dq = (S + DQ_QB * WG_ROWS - 1) / (DQ_QB * WG_ROWS) * B * H;
+    const size_t a = (size_t)max_split_parts(t_dkv, BWD_MAX_SPLIT, wg_slots()) * DKV_PART_FLOATS * sizeof(float);
+    const size_t b = (size_t)max_split_parts(t_dq, BWD_MAX_SPLIT, wg_slots()) * DQ_PART_FLOATS * sizeof(float);
+    return a > b ? a : b;
 }
 
-// step 2: dK, dV (workgroup per 128 keys).  With a workspace the leftover tasks of a mostly empty last scheduling round are
-// cut into query-range chunks (split_plan); split_mode as in vgpa_attn_fwd_ws.
-#define BWD_MAX_SPLIT 16
-#define DKV_PART_FLOATS (2 * WG_ROWS * HD)
-#define DQ_PART_FLOATS (DQ_QB * WG_ROWS * HD)
-static int32_t attn_bwd_dkv_impl(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dk,
-                                 void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                                 const int64_t* do_strides, const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S,
-                                 int64_t head_dim, int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
+// step 2: dK, dV (workgroup per 128 keys).  With a workspace (NULL: a single launch) the leftover tasks of a mostly empty last
+// scheduling round are cut into query-range chunks (split_plan); split_mode as in vgpa_attn_fwd_ws.
+int32_t vgpa_attn_bwd_dkv_ws(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dk,
+                             void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
+                             const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
+                             int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
+    (void)scale;
     if (!q || !k || !v || !d_o || !lse2 || !delta || !dk || !dv || !bwd_common_ok(B, H, S, head_dim)) return VGPA_ERR_INVALID;
-    if (!SOK(q_strides) || !SOK(k_strides) || !SOK(v_strides) || !SOK(do_strides) || !SOK(dk_strides) ||
-        !SOK(dv_strides) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dk) || !al16(dv) || (workspace && !al16(workspace)))
+    if (!view_ok(q_strides, B, H, S, HD) || !view_ok(k_strides, B, H, S, HD) || !view_ok(v_strides, B, H, S, HD) || !view_ok(do_strides, B, H, S, HD) ||
+        !view_ok(dk_strides, B, H, S, HD) || !view_ok(dv_strides, B, H, S, HD) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dk) ||
+        !al16(dv) || (workspace && !al16(workspace)))
         return VGPA_ERR_INVALID;
     const int n_t = (int)((S + WG_ROWS - 1) / WG_ROWS);
     const int64_t tasks = (int64_t)n_t * B * H;
     const float kscale = 0.6931471805599453f;
-    int64_t n_main = tasks;
-    int nsplit = 1;
-    if (workspace) split_plan(tasks, (int)((S + TILE - 1) / TILE), split_mode, BWD_MAX_SPLIT, &n_main, &nsplit);
-    const int64_t n_tail = tasks - n_main;
-    if (n_tail > 0 && ws_bytes < (size_t)n_tail * nsplit * DKV_PART_FLOATS * sizeof(float)) {
-        if (split_mode >= 2) return VGPA_ERR_WORKSPACE;
-        n_main = tasks;
-    }
-    if (n_main > 0) {
-        VGPA_LAUNCH(attn_bwd_dkv_kernel<false>, dim3((unsigned)n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
+    TailSplit p;
+    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, BWD_MAX_SPLIT, 0, DKV_PART_FLOATS * sizeof(float), workspace,
+                                       ws_bytes, 0, &p);
+    if (rc) return rc;
+    if (p.n_main > 0) {
+        VGPA_LAUNCH(attn_bwd_dkv_kernel<false>, dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
                     (const bf16_t*)d_o, lse2, delta, (bf16_t*)dk, (bf16_t*)dv, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
                     mk(dk_strides), mk(dv_strides), (int)S, (int)H, n_t, kscale, 0, 1, (float*)nullptr);
         VGPA_CHECK_LAUNCH();
     }
-    if (n_main < tasks) {
-        VGPA_LAUNCH(attn_bwd_dkv_kernel<true>, dim3((unsigned)(n_tail * nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+    if (p.n_tail > 0) {
+        VGPA_LAUNCH(attn_bwd_dkv_kernel<true>, dim3((unsigned)(p.n_tail * p.nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (const bf16_t*)d_o, lse2, delta, (bf16_t*)dk, (bf16_t*)dv, mk(q_strides), mk(k_strides), mk(v_strides),
-                    mk(do_strides), mk(dk_strides), mk(dv_strides), (int)S, (int)H, n_t, kscale, (int)n_main, nsplit, (float*)workspace);
+                    mk(do_strides), mk(dk_strides), mk(dv_strides), (int)S, (int)H, n_t, kscale, (int)p.n_main, p.nsplit, (float*)workspace);
         VGPA_CHECK_LAUNCH();
-        VGPA_LAUNCH(attn_dkv_merge_kernel, dim3((unsigned)(n_tail * (WG_ROWS / 4))), dim3(256), 0, stream, (const float*)workspace, nsplit, (int)n_main,
-                    n_t, (bf16_t*)dk, (bf16_t*)dv, mk(dk_strides), mk(dv_strides), (int)S, (int)H, kscale);
+        VGPA_LAUNCH(attn_dkv_merge_kernel, dim3((unsigned)(p.n_tail * (WG_ROWS / 4))), dim3(256), 0, stream, (const float*)workspace, p.nsplit,
+                    (int)p.n_main, n_t, (bf16_t*)dk, (bf16_t*)dv, mk(dk_strides), mk(dv_strides), (int)S, (int)H, kscale);
         VGPA_CHECK_LAUNCH();
     }
     return VGPA_OK;
 }
 
 // step 3: dQ (workgroup per 128 * DQ_QB queries); split as above, along the key tiles
-static int32_t attn_bwd_dq_impl(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dq,
-                                const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
-                                const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode,
-                                void* workspace, size_t ws_bytes, hipStream_t stream) {
+int32_t vgpa_attn_bwd_dq_ws(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dq,
+                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
+                            const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode,
+                            void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (!q || !k || !v || !d_o || !lse2 || !delta || !dq || !bwd_common_ok(B, H, S, head_dim)) return VGPA_ERR_INVALID;
-    if (!SOK(q_strides) || !SOK(k_strides) || !SOK(v_strides) || !SOK(do_strides) || !SOK(dq_strides) ||
-        !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dq) || (workspace && !al16(workspace)))
+    if (!view_ok(q_strides, B, H, S, HD) || !view_ok(k_strides, B, H, S, HD) || !view_ok(v_strides, B, H, S, HD) || !view_ok(do_strides, B, H, S, HD) ||
+        !view_ok(dq_strides, B, H, S, HD) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dq) || (workspace && !al16(workspace)))
         return VGPA_ERR_INVALID;
     const int n_t = (int)((S + DQ_QB * WG_ROWS - 1) / (DQ_QB * WG_ROWS));
     const int64_t tasks = (int64_t)n_t * B * H;
-    int64_t n_main = tasks;
-    int nsplit = 1;
-    if (workspace) split_plan(tasks, (int)((S + TILE - 1) / TILE), split_mode, BWD_MAX_SPLIT, &n_main, &nsplit);
-    const int64_t n_tail = tasks - n_main;
-    if (n_tail > 0 && ws_bytes < (size_t)n_tail * nsplit * DQ_PART_FLOATS * sizeof(float)) {
-        if (split_mode >= 2) return VGPA_ERR_WORKSPACE;
-        n_main = tasks;
-    }
-    if (n_main > 0) {
-        VGPA_LAUNCH((attn_bwd_dq_kernel<DQ_QB, false>), dim3((unsigned)n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+    TailSplit p;
+    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, BWD_MAX_SPLIT, 0, DQ_PART_FLOATS * sizeof(float), workspace,
+                                       ws_bytes, 0, &p);
+    if (rc) return rc;
+    if (p.n_main > 0) {
+        VGPA_LAUNCH((attn_bwd_dq_kernel<DQ_QB, false>), dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (const bf16_t*)d_o, lse2, delta, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
                     mk(dq_strides), (int)S, (int)H, n_t, scale, 0, 1, (float*)nullptr);
         VGPA_CHECK_LAUNCH();
     }
-    if (n_main < tasks) {
-        VGPA_LAUNCH((attn_bwd_dq_kernel<DQ_QB, true>), dim3((unsigned)(n_tail * nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+    if (p.n_tail > 0) {
+        VGPA_LAUNCH((attn_bwd_dq_kernel<DQ_QB, true>), dim3((unsigned)(p.n_tail * p.nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (const bf16_t*)d_o, lse2, delta, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
-                    mk(dq_strides), (int)S, (int)H, n_t, scale, (int)n_main, nsplit, (float*)workspace);
+                    mk(dq_strides), (int)S, (int)H, n_t, scale, (int)p.n_main, p.nsplit, (float*)workspace);
         VGPA_CHECK_LAUNCH();
-        VGPA_LAUNCH(attn_dq_merge_kernel, dim3((unsigned)(n_tail * (DQ_QB * WG_ROWS / 4))), dim3(256), 0, stream, (const float*)workspace, nsplit,
-                    (int)n_main, n_t, DQ_QB * WG_ROWS, (bf16_t*)dq, mk(dq_strides), (int)S, (int)H, scale);
+        VGPA_LAUNCH(attn_dq_merge_kernel, dim3((unsigned)(p.n_tail * (DQ_QB * WG_ROWS / 4))), dim3(256), 0, stream, (const float*)workspace, p.nsplit,
+                    (int)p.n_main, n_t, DQ_QB * WG_ROWS, (bf16_t*)dq, mk(dq_strides), (int)S, (int)H, scale);
         VGPA_CHECK_LAUNCH();
     }
     return VGPA_OK;
 }
 
-int32_t vgpa_attn_bwd_dkv(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dk,
-                          void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
-                          const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
-                          hipStream_t stream) {
-    (void)scale;
-    return attn_bwd_dkv_impl(q, k, v, d_o, lse2, delta, dk, dv, q_strides, k_strides, v_strides, do_strides, dk_strides, dv_strides, B, H, S,
-                             head_dim, 0, nullptr, 0, stream);
-}
-int32_t vgpa_attn_bwd_dq(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dq,
-                         const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
-                         const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, hipStream_t stream) {
-    return attn_bwd_dq_impl(q, k, v, d_o, lse2, delta, dq, q_strides, k_strides, v_strides, do_strides, dq_strides, B, H, S, head_dim, scale, 0,
-                            nullptr, 0, stream);
-}
-
-// Workspace for the split forms below (shared by the two; they run one after the other on a stream).
-size_t vgpa_attn_bwd_split_workspace_bytes(int64_t B, int64_t H, int64_t S) {
-    const int64_t t_dkv = (S + WG_ROWS - 1) / WG_ROWS * B * H, t_dq = (S + DQ_QB * WG_ROWS - 1) / (DQ_QB * WG_ROWS) * B * H;
-    int64_t p_dkv = wg_slots(), p_dq = wg_slots();
-    if (t_dkv * BWD_MAX_SPLIT < p_dkv) p_dkv = t_dkv * BWD_MAX_SPLIT;
-    if (t_dq * BWD_MAX_SPLIT < p_dq) p_dq = t_dq * BWD_MAX_SPLIT;
-    const size_t a = (size_t)p_dkv * DKV_PART_FLOATS * sizeof(float), b = (size_t)p_dq * DQ_PART_FLOATS * sizeof(float);
-    return a > b ? a : b;
-}
-int32_t vgpa_attn_bwd_dkv_ws(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dk,
-                             void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
-                             const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
-                             int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
-    (void)scale;
-    return attn_bwd_dkv_impl(q, k, v, d_o, lse2, delta, dk, dv, q_strides, k_strides, v_strides, do_strides, dk_strides, dv_strides, B, H, S,
-                             head_dim, split_mode, workspace, ws_bytes, stream);
-}
-int32_t vgpa_attn_bwd_dq_ws(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dq,
-                            const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
-                            const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode,
-                            void* workspace, size_t ws_bytes, hipStream_t stream) {
-    return attn_bwd_dq_impl(q, k, v, d_o, lse2, delta, dq, q_strides, k_strides, v_strides, do_strides, dq_strides, B, H, S, head_dim, scale,
-                            split_mode, workspace, ws_bytes, stream);
-}
-
 #ifdef VGPA_VARIANTS   // measured-slower experiments / diagnostics live in tools/variants/ (variant builds only)
 #include "attn_bwd_fused_entry.inc"
 #endif  // VGPA_VARIANTS
-
-// the whole backward (delta -> dK/dV -> dQ) with a caller-provided workspace for delta
-int32_t vgpa_attn_bwd(const void* q, const void* k, const void* v, const void* o, const void* d_o, const float* lse2, void* dq, void* dk,
-                      void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides,
-                      const int64_t* do_strides, const int64_t* dq_strides, const int64_t* dk_strides, const int64_t* dv_strides, int64_t B,
-                      int64_t H, int64_t S, int64_t head_dim, float scale, void* workspace, size_t ws_bytes, hipStream_t stream) {
-    if (!workspace) return VGPA_ERR_INVALID;
-    if (!bwd_common_ok(B, H, S, head_dim)) return VGPA_ERR_INVALID;
-    if (ws_bytes < vgpa_attn_bwd_workspace_bytes(B, H, S)) return VGPA_ERR_WORKSPACE;
-    float* delta = (float*)workspace;
-    int32_t rc = vgpa_attn_bwd_delta(o, d_o, o_strides, do_strides, delta, B, H, S, head_dim, stream);
-    if (rc) return rc;
-    rc = vgpa_attn_bwd_dkv(q, k, v, d_o, lse2, delta, dk, dv, q_strides, k_strides, v_strides, do_strides, dk_strides, dv_strides, B, H, S,
-                           head_dim, scale, stream);
-    if (rc) return rc;
-    return vgpa_attn_bwd_dq(q, k, v, d_o, lse2, delta, dq, q_strides, k_strides, v_strides, do_strides, dq_strides, B, H, S, head_dim, scale,
-                            stream);
-}
 
 }  // extern "C"

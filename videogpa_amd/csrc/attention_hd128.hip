@@ -13,7 +13,7 @@
 //   dK, dV  :  key on the lanes:  S = Q K^T,  dV^T += dO^T P,  dK^T += Q^T dS          (statistics per row from an LDS tile)
 // Rows past the end of a ragged tile read as zeros through the buffer descriptor; keys past Skv are masked in the forward only
 // (in the backward their K / V rows are zero or their results are not stored).
-#include "mfma_tiles.h"
+#include "attn_common.h"   // the host-side view checks, for both head dims
 
 #define D128 128
 #define P128 136
@@ -910,10 +910,6 @@ __global__ __launch_bounds__(256, 1) void attn128_dq_w1x2_kernel(const bf16_t* _
 }
 
 // ===================================================================================================== host
-static inline bool sok128(const int64_t* st) { return st && st[0] >= 0 && st[1] >= 0 && st[2] >= D128 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0; }
-static inline bool rok128(const int64_t* st, int64_t B, int64_t H, int64_t S) { return (B - 1) * st[0] + (H - 1) * st[1] + (S - 1) * st[2] + D128 < ((int64_t)1 << 31); }
-static inline TStride mk128(const int64_t* st) { TStride t; t.b = (uint32_t)st[0]; t.h = (uint32_t)st[1]; t.s = (uint32_t)st[2]; return t; }
-static inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 #define LOG2E_F 1.4426950408889634f
 
 // workspace of the w1 forward: per (batch, head) max |k|^2 and one redo flag per 256-row strip
@@ -931,17 +927,18 @@ static constexpr int64_t attn128_min_sweep() { return ATTN128_W1_MIN_KEYS; }
 // o_res8 (optional: uint8 [B, H, Sq, 128] view with its own element strides; NULL = not written): eight further mantissa bits of every output value
 // (common.h res8) for the backward's delta -- "precise delta", see vgpa_attn_fwd_w1_res
 static inline bool res8_ok(const void* o_res8, const int64_t* st, int64_t B, int64_t H, int64_t S) {
-    return !o_res8 || (st && st[0] >= 0 && st[1] >= 0 && st[2] >= D128 && st[0] % 8 == 0 && st[1] % 8 == 0 && st[2] % 8 == 0 && ((uintptr_t)o_res8 & 7) == 0 &&
-                       (B - 1) * st[0] + (H - 1) * st[1] + (S - 1) * st[2] + D128 < ((int64_t)1 << 32));
+    // one byte per element: 8-byte (not 16-byte) alignment and byte offsets below 2^32 (not 2^31 elements), unlike the bf16 views; NULL = absent
+    return !o_res8 || (stride_ok(st, D128) && ((uintptr_t)o_res8 & 7) == 0 && range_ok(st, B, H, S, D128, (int64_t)1 << 32));
 }
 extern "C" int32_t vgpa_attn128_fwd(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides, const int64_t* k_strides,
                                     const int64_t* v_strides, const int64_t* o_strides, void* o_res8, const int64_t* ores_strides, int64_t B, int64_t H,
                                     int64_t Sq, int64_t Skv, float scale, void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (!q || !k || !v || !o || !lse2 || B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || !res8_ok(o_res8, ores_strides, B, H, Sq)) return VGPA_ERR_INVALID;
     uint8_t* ores = (uint8_t*)o_res8;
-    const TStride sor = o_res8 ? mk128(ores_strides) : TStride{0, 0, 0};
-    if (!sok128(q_strides) || !sok128(k_strides) || !sok128(v_strides) || !sok128(o_strides) || !a16(q) || !a16(k) || !a16(v) || !a16(o)) return VGPA_ERR_INVALID;
-    if (!rok128(q_strides, B, H, Sq) || !rok128(k_strides, B, H, Skv) || !rok128(v_strides, B, H, Skv) || !rok128(o_strides, B, H, Sq)) return VGPA_ERR_INVALID;
+    const TStride sor = o_res8 ? mk(ores_strides) : TStride{0, 0, 0};
+    if (!view_ok(q_strides, B, H, Sq, D128) || !view_ok(k_strides, B, H, Skv, D128) || !view_ok(v_strides, B, H, Skv, D128) ||
+        !view_ok(o_strides, B, H, Sq, D128) || !al16(q) || !al16(k) || !al16(v) || !al16(o))
+        return VGPA_ERR_INVALID;
     const int64_t n_qt = (Sq + 127) / 128, tasks = B * H * n_qt;
     if (tasks >= ((int64_t)1 << 31)) return VGPA_ERR_INVALID;
     const float c = scale * LOG2E_F;
@@ -951,13 +948,13 @@ extern "C" int32_t vgpa_attn128_fwd(const void* q, const void* k, const void* v,
         unsigned* kmax2 = (unsigned*)workspace;
         int* flags = (int*)workspace + B * H;
         if (hipMemsetAsync(workspace, 0, vgpa_attn128_fwd_workspace_bytes(B, H, Sq), stream) != hipSuccess) return VGPA_ERR_LAUNCH;
-        VGPA_LAUNCH(attn128_kmax_kernel, dim3(16, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)k, mk128(k_strides), (int)Skv, (int)H, kmax2);
+        VGPA_LAUNCH(attn128_kmax_kernel, dim3(16, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)k, mk(k_strides), (int)Skv, (int)H, kmax2);
         VGPA_LAUNCH(attn128_fwd_w1_kernel, dim3((unsigned)tasks256), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse2,
-                    (const unsigned*)kmax2, flags, mk128(q_strides), mk128(k_strides), mk128(v_strides), mk128(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_q256, c,
+                    (const unsigned*)kmax2, flags, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_q256, c,
                     ores, sor);
         // flagged strips again, with the running-max kernel (exits at once for unflagged ones)
         VGPA_LAUNCH(attn128_fwd_kernel, dim3((unsigned)tasks), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse2,
-                    mk128(q_strides), mk128(k_strides), mk128(v_strides), mk128(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, c, (const int*)flags, ores, sor);
+                    mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, c, (const int*)flags, ores, sor);
         VGPA_CHECK_LAUNCH();
         return VGPA_OK;
     }
@@ -967,7 +964,7 @@ extern "C" int32_t vgpa_attn128_fwd(const void* q, const void* k, const void* v,
     // heads: two independent 4-wave workgroups per CU already hide the latencies, and the loop itself (every MFMA behind its own ds_read + lgkmcnt(0))
     // is the limit.  What would help is the generated one-wave-per-SIMD loop made persistent; the ring kernel was removed again.
     VGPA_LAUNCH(attn128_fwd_kernel, dim3((unsigned)tasks), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse2,
-                mk128(q_strides), mk128(k_strides), mk128(v_strides), mk128(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, c, (const int*)nullptr, ores, sor);
+                mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, c, (const int*)nullptr, ores, sor);
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }
@@ -1325,14 +1322,15 @@ extern "C" int32_t vgpa_attn128_fwd_f8(const void* q, const void* k, const void*
     if (!q || !k || !v || !o || !lse2 || !workspace || B <= 0 || H <= 0 || Sq <= 0 || Skv <= 0 || !res8_ok(o_res8, ores_strides, B, H, Sq)) return VGPA_ERR_INVALID;
     // the dequantised operands are all there or all absent; each a bf16 [B, H, S, 128] view like its source
     const bool deq = q_deq || k_deq || v_deq;
-    if (deq && (!q_deq || !k_deq || !v_deq || !qd_strides || !kd_strides || !vd_strides || !sok128(qd_strides) || !sok128(kd_strides) || !sok128(vd_strides) ||
-                !a16(q_deq) || !a16(k_deq) || !a16(v_deq) || !rok128(qd_strides, B, H, Sq) || !rok128(kd_strides, B, H, Skv) || !rok128(vd_strides, B, H, Skv)))
+    if (deq && (!q_deq || !k_deq || !v_deq || !view_ok(qd_strides, B, H, Sq, D128) || !view_ok(kd_strides, B, H, Skv, D128) ||
+                !view_ok(vd_strides, B, H, Skv, D128) || !al16(q_deq) || !al16(k_deq) || !al16(v_deq)))
         return VGPA_ERR_INVALID;
-    const TStride sqd = deq ? mk128(qd_strides) : TStride{0, 0, 0}, skd = deq ? mk128(kd_strides) : TStride{0, 0, 0}, svd = deq ? mk128(vd_strides) : TStride{0, 0, 0};
+    const TStride sqd = deq ? mk(qd_strides) : TStride{0, 0, 0}, skd = deq ? mk(kd_strides) : TStride{0, 0, 0}, svd = deq ? mk(vd_strides) : TStride{0, 0, 0};
     uint8_t* ores = (uint8_t*)o_res8;
-    const TStride sor = o_res8 ? mk128(ores_strides) : TStride{0, 0, 0};
-    if (!sok128(q_strides) || !sok128(k_strides) || !sok128(v_strides) || !sok128(o_strides) || !a16(q) || !a16(k) || !a16(v) || !a16(o)) return VGPA_ERR_INVALID;
-    if (!rok128(q_strides, B, H, Sq) || !rok128(k_strides, B, H, Skv) || !rok128(v_strides, B, H, Skv) || !rok128(o_strides, B, H, Sq)) return VGPA_ERR_INVALID;
+    const TStride sor = o_res8 ? mk(ores_strides) : TStride{0, 0, 0};
+    if (!view_ok(q_strides, B, H, Sq, D128) || !view_ok(k_strides, B, H, Skv, D128) || !view_ok(v_strides, B, H, Skv, D128) ||
+        !view_ok(o_strides, B, H, Sq, D128) || !al16(q) || !al16(k) || !al16(v) || !al16(o))
+        return VGPA_ERR_INVALID;
     if (ws_bytes < vgpa_attn128_fwd_f8_workspace_bytes(B, H, Sq, Skv) || ((uintptr_t)workspace & 255)) return VGPA_ERR_WORKSPACE;
     const int64_t Lp = (Skv + 63) / 64 * 64, n_q256 = (Sq + 255) / 256, tasks256 = B * H * n_q256, n_qt = (Sq + 127) / 128, tasks = B * H * n_qt;
     if (tasks >= ((int64_t)1 << 31) || B * H > 65535 || Skv * 128 >= ((int64_t)1 << 31) || 128 * Lp >= ((int64_t)1 << 31)) return VGPA_ERR_INVALID;
@@ -1347,20 +1345,20 @@ extern "C" int32_t vgpa_attn128_fwd_f8(const void* q, const void* k, const void*
     uint8_t* k8 = q8 + f8_align((size_t)(B * H * Sq) * 128);
     uint8_t* v8t = k8 + f8_align((size_t)(B * H * Skv) * 128);
     if (hipMemsetAsync(workspace, 0, head, stream) != hipSuccess) return VGPA_ERR_LAUNCH;
-    VGPA_LAUNCH(attn128_f8_amax_kernel, dim3(32, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, mk128(q_strides),
-                mk128(k_strides), mk128(v_strides), (int)Sq, (int)Skv, (int)H, stats);
+    VGPA_LAUNCH(attn128_f8_amax_kernel, dim3(32, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, mk(q_strides),
+                mk(k_strides), mk(v_strides), (int)Sq, (int)Skv, (int)H, stats);
     const int64_t nblk = (Sq > Lp ? (Sq + 63) / 64 : Lp / 64);
     VGPA_LAUNCH(attn128_f8_quant_kernel, dim3((unsigned)nblk, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                mk128(q_strides), mk128(k_strides), mk128(v_strides), (int)Sq, (int)Skv, (int)Lp, (int)H, c, (const unsigned*)stats, q8, k8, v8t, qn2, kmax2,
+                mk(q_strides), mk(k_strides), mk(v_strides), (int)Sq, (int)Skv, (int)Lp, (int)H, c, (const unsigned*)stats, q8, k8, v8t, qn2, kmax2,
                 (bf16_t*)q_deq, (bf16_t*)k_deq, (bf16_t*)v_deq, sqd, skd, svd);
     VGPA_LAUNCH(attn128_fwd_f8_kernel, dim3((unsigned)tasks256), dim3(256), 0, stream, (const uint8_t*)q8, (const uint8_t*)k8, (const uint8_t*)v8t, (const float*)qn2,
-                (const unsigned*)kmax2, (const unsigned*)stats, (bf16_t*)o, lse2, flags, mk128(o_strides), (int)Sq, (int)Skv, (int)Lp, (int)H, (int)n_q256, c, ores, sor);
+                (const unsigned*)kmax2, (const unsigned*)stats, (bf16_t*)o, lse2, flags, mk(o_strides), (int)Sq, (int)Skv, (int)Lp, (int)H, (int)n_q256, c, ores, sor);
     // redo pass over the flagged strips (bf16 running-max kernel).  With dequantised operands supplied it runs on THEM: the rows it rewrites (o, lse2, res8) are then
     // the softmax of exactly the q / k / v the backward will be handed, as everywhere else (round 5 redid from the original bf16 operands, which left those rows'
     // recomputed P = exp2(c q_deq k_deq - lse2) summing to 1 +- several %: ADVICE r5)
     VGPA_LAUNCH(attn128_fwd_kernel, dim3((unsigned)tasks), dim3(256), 0, stream, (const bf16_t*)(deq ? q_deq : q), (const bf16_t*)(deq ? k_deq : k),
-                (const bf16_t*)(deq ? v_deq : v), (bf16_t*)o, lse2, deq ? sqd : mk128(q_strides), deq ? skd : mk128(k_strides), deq ? svd : mk128(v_strides),
-                mk128(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, deq ? 1.f : c, (const int*)flags, ores, sor);      // q_deq carries c already
+                (const bf16_t*)(deq ? v_deq : v), (bf16_t*)o, lse2, deq ? sqd : mk(q_strides), deq ? skd : mk(k_strides), deq ? svd : mk(v_strides),
+                mk(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, deq ? 1.f : c, (const int*)flags, ores, sor);      // q_deq carries c already
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }
@@ -1388,9 +1386,9 @@ static int32_t attn128_bwd_impl(const void* q, const void* k, const void* v, con
         return VGPA_ERR_INVALID;
     const int64_t* qs[] = {q_strides, o_strides, do_strides, dq_strides};
     const int64_t* ks[] = {k_strides, v_strides, dk_strides, dv_strides};
-    for (const int64_t* s : qs) if (!sok128(s) || !rok128(s, B, H, Sq)) return VGPA_ERR_INVALID;
-    for (const int64_t* s : ks) if (!sok128(s) || !rok128(s, B, H, Skv)) return VGPA_ERR_INVALID;
-    if (!a16(q) || !a16(k) || !a16(v) || !a16(o) || !a16(d_o) || !a16(dq) || !a16(dk) || !a16(dv)) return VGPA_ERR_INVALID;
+    for (const int64_t* s : qs) if (!view_ok(s, B, H, Sq, D128)) return VGPA_ERR_INVALID;
+    for (const int64_t* s : ks) if (!view_ok(s, B, H, Skv, D128)) return VGPA_ERR_INVALID;
+    if (!al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(d_o) || !al16(dq) || !al16(dk) || !al16(dv)) return VGPA_ERR_INVALID;
     if (!workspace || ((uintptr_t)workspace & 15) || ws_bytes < vgpa_attn128_bwd_workspace_bytes(B, H, Sq)) return VGPA_ERR_WORKSPACE;
     const int64_t n_qt = (Sq + 127) / 128, n_kt = (Skv + 127) / 128, total = B * H * Sq;
     if (B * H * n_qt >= ((int64_t)1 << 31) || B * H * n_kt >= ((int64_t)1 << 31) || total * 16 >= ((int64_t)1 << 39) || 2 * Sq * 4 >= ((int64_t)1 << 31))
@@ -1399,30 +1397,30 @@ static int32_t attn128_bwd_impl(const void* q, const void* k, const void* v, con
     float* stats = delta + total;
     const bool w1 = dkv_mode == 1 || (dkv_mode < 0 && Sq >= attn128_min_sweep());
     const bool w1q = dkv_mode == 1 || (dkv_mode < 0 && Skv >= attn128_min_sweep());     // the dQ kernel sweeps the keys
-    VGPA_LAUNCH(attn128_delta_kernel, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)d_o, (const bf16_t*)o, mk128(do_strides),
-                mk128(o_strides), (int)Sq, (int)H, total, delta, lse2, 1.f / c, (w1 || w1q) ? stats : (float*)nullptr, (const uint8_t*)o_res8,
-                o_res8 ? mk128(ores_strides) : TStride{0, 0, 0});
+    VGPA_LAUNCH(attn128_delta_kernel, dim3((unsigned)((total * 16 + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)d_o, (const bf16_t*)o, mk(do_strides),
+                mk(o_strides), (int)Sq, (int)H, total, delta, lse2, 1.f / c, (w1 || w1q) ? stats : (float*)nullptr, (const uint8_t*)o_res8,
+                o_res8 ? mk(ores_strides) : TStride{0, 0, 0});
     if (w1q && attn128_dq_x2()) {
         const int64_t n_q256 = (Sq + 255) / 256;
         VGPA_LAUNCH(attn128_dq_w1x2_kernel, dim3((unsigned)(B * H * n_q256)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                    (const bf16_t*)d_o, (const float*)stats, (bf16_t*)dq, mk128(q_strides), mk128(k_strides), mk128(v_strides), mk128(do_strides),
-                    mk128(dq_strides), (int)Sq, (int)Skv, (int)H, (int)n_q256, c, dq_mul);
+                    (const bf16_t*)d_o, (const float*)stats, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
+                    mk(dq_strides), (int)Sq, (int)Skv, (int)H, (int)n_q256, c, dq_mul);
     } else if (w1q)
         VGPA_LAUNCH(attn128_dq_w1_kernel, dim3((unsigned)(B * H * n_qt)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                    (const bf16_t*)d_o, (const float*)stats, (bf16_t*)dq, mk128(q_strides), mk128(k_strides), mk128(v_strides), mk128(do_strides),
-                    mk128(dq_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, c, dq_mul);
+                    (const bf16_t*)d_o, (const float*)stats, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
+                    mk(dq_strides), (int)Sq, (int)Skv, (int)H, (int)n_qt, c, dq_mul);
     else
         VGPA_LAUNCH(attn128_dq_kernel, dim3((unsigned)(B * H * n_qt)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (const bf16_t*)d_o,
-                    lse2, (const float*)delta, (bf16_t*)dq, mk128(q_strides), mk128(k_strides), mk128(v_strides), mk128(do_strides), mk128(dq_strides), (int)Sq,
+                    lse2, (const float*)delta, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides), mk(dq_strides), (int)Sq,
                     (int)Skv, (int)H, (int)n_qt, c, dq_mul);
     if (w1)
         VGPA_LAUNCH(attn128_dkv_w1_kernel, dim3((unsigned)(B * H * n_kt)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                    (const bf16_t*)d_o, (const float*)stats, (bf16_t*)dk, (bf16_t*)dv, mk128(q_strides), mk128(k_strides), mk128(v_strides), mk128(do_strides),
-                    mk128(dk_strides), mk128(dv_strides), (int)Sq, (int)Skv, (int)H, (int)n_kt, c, dk_mul);
+                    (const bf16_t*)d_o, (const float*)stats, (bf16_t*)dk, (bf16_t*)dv, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
+                    mk(dk_strides), mk(dv_strides), (int)Sq, (int)Skv, (int)H, (int)n_kt, c, dk_mul);
     else
         VGPA_LAUNCH(attn128_dkv_kernel, dim3((unsigned)(B * H * n_kt)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
-                    (const bf16_t*)d_o, lse2, (const float*)delta, (bf16_t*)dk, (bf16_t*)dv, mk128(q_strides), mk128(k_strides), mk128(v_strides),
-                    mk128(do_strides), mk128(dk_strides), mk128(dv_strides), (int)Sq, (int)Skv, (int)H, (int)n_kt, c, dk_mul);
+                    (const bf16_t*)d_o, lse2, (const float*)delta, (bf16_t*)dk, (bf16_t*)dv, mk(q_strides), mk(k_strides), mk(v_strides),
+                    mk(do_strides), mk(dk_strides), mk(dv_strides), (int)Sq, (int)Skv, (int)H, (int)n_kt, c, dk_mul);
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }

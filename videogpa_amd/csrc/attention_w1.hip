@@ -166,7 +166,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
 // (flags[task] = 1) and redone by the online-softmax kernel of attention.hip
 // (vgpa_internal_attn_fwd_redo), so the result never depends on the bound being tight.
 // =====================================================================================================
-#include "w1_fwd_knobs.inc"                   // W1_FWD_MFSUM: what the generated loop expects around it (tools/gen_w1_asm.py W1_KNOBS; 0 in the product)
+#include "w1_fwd_knobs.inc"                   // W1_FWD_MFSUM: what the generated loop expects around it (tools/gen_w1_asm.py W1_KNOBS mfsum; 1 in the product)
 #define W1_FWD_PART_FLOATS (256 * (HD + 2))   // per (task, chunk): O[256][64] (un-normalised), M[256], l[256] -- layout of attention.hip's split forward
 #define W1_L_MIN 7.8886e-31f                  // 2^-100: below this the row's sum is too close to underflow -> redo
 // ... and above 2^118 too close to overflow: the O accumulators carry sum_j p_j v_j <= l max|v| (a row whose true maximum lies 112-128 above the shift has a FINITE
@@ -607,7 +607,7 @@ __global__ __launch_bounds__(256) void w1_dkv_merge_kernel(const float* __restri
     dV[(size_t)b * sdv.b + (size_t)h * sdv.h + (size_t)key * sdv.s + lane] = f32_to_bf16(av);
 }
 
-// step 1 of the w1 backward: delta[b,h,q] = sum_d dO * O (as vgpa_attn_bwd_delta) and the statistics planes the dK/dV kernel
+// step 1 of the w1 backward: delta[b,h,q] = sum_d dO * O (as vgpa_attn_bwd_delta_res) and the statistics planes the dK/dV kernel
 // streams: stats[b,h,0,q] = -lse2, stats[b,h,1,q] = -delta
 __global__ __launch_bounds__(256) void w1_bwd_prep_kernel(const bf16_t* __restrict__ dO, const bf16_t* __restrict__ O, const float* __restrict__ LSE2,
                                                             TStride sdo, TStride so, int S, int H, int64_t total /* B*H*S */, float* __restrict__ delta,
@@ -677,35 +677,29 @@ int32_t vgpa_attn_bwd_dq_w1(const void* q, const void* k, const void* v, const v
                             const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode,
                             void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (!q || !k || !v || !d_o || !lse2 || !delta || !dq || head_dim != HD || B <= 0 || H <= 0 || S <= 0 || S > (1 << 24)) return VGPA_ERR_INVALID;
-#define SOK(st) (stride_ok(st) && range_ok(st, B, H, S))
-    if (!SOK(q_strides) || !SOK(k_strides) || !SOK(v_strides) || !SOK(do_strides) || !SOK(dq_strides) || !al16(q) || !al16(k) || !al16(v) ||
-        !al16(d_o) || !al16(dq) || (workspace && !al16(workspace)))
+    if (!view_ok(q_strides, B, H, S, HD) || !view_ok(k_strides, B, H, S, HD) || !view_ok(v_strides, B, H, S, HD) || !view_ok(do_strides, B, H, S, HD) ||
+        !view_ok(dq_strides, B, H, S, HD) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dq) || (workspace && !al16(workspace)))
         return VGPA_ERR_INVALID;
-#undef SOK
     const int rows = 256;
     const int n_t = (int)((S + rows - 1) / rows);
     const int64_t tasks = (int64_t)n_t * B * H;
     if (tasks > 0x7fffffff) return VGPA_ERR_INVALID;
-    int64_t n_main = tasks;
-    int nsplit = 1;
-    if (workspace) split_plan(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, &n_main, &nsplit, w1_slots());
-    const int64_t n_tail = tasks - n_main;
-    if (n_tail > 0 && ws_bytes < (size_t)n_tail * nsplit * rows * HD * sizeof(float)) {
-        if (split_mode >= 2) return VGPA_ERR_WORKSPACE;
-        n_main = tasks;
-    }
-    if (n_main > 0) {
-        VGPA_LAUNCH((attn_bwd_dq_w1_kernel<false>), dim3((unsigned)n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+    TailSplit p;
+    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), rows * HD * sizeof(float), workspace,
+                                       ws_bytes, 0, &p);
+    if (rc) return rc;
+    if (p.n_main > 0) {
+        VGPA_LAUNCH((attn_bwd_dq_w1_kernel<false>), dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (const bf16_t*)d_o, lse2, delta, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
                     mk(dq_strides), (int)S, (int)H, n_t, scale, 0, 1, (float*)nullptr);
         VGPA_CHECK_LAUNCH();
     }
-    if (n_main < tasks) {
-        VGPA_LAUNCH((attn_bwd_dq_w1_kernel<true>), dim3((unsigned)(n_tail * nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+    if (p.n_tail > 0) {
+        VGPA_LAUNCH((attn_bwd_dq_w1_kernel<true>), dim3((unsigned)(p.n_tail * p.nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (const bf16_t*)d_o, lse2, delta, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
-                    mk(dq_strides), (int)S, (int)H, n_t, scale, (int)n_main, nsplit, (float*)workspace);
+                    mk(dq_strides), (int)S, (int)H, n_t, scale, (int)p.n_main, p.nsplit, (float*)workspace);
         VGPA_CHECK_LAUNCH();
-        VGPA_LAUNCH(w1_dq_merge_kernel, dim3((unsigned)(n_tail * (rows / 4))), dim3(256), 0, stream, (const float*)workspace, nsplit, (int)n_main, n_t,
+        VGPA_LAUNCH(w1_dq_merge_kernel, dim3((unsigned)(p.n_tail * (rows / 4))), dim3(256), 0, stream, (const float*)workspace, p.nsplit, (int)p.n_main, n_t,
                     rows, (bf16_t*)dq, mk(dq_strides), (int)S, (int)H, scale);
         VGPA_CHECK_LAUNCH();
     }
@@ -719,9 +713,8 @@ int32_t vgpa_attn_bwd_prep_w1_res(const void* o, const void* o_res, int32_t res_
                                   const int64_t* ores_strides, const int64_t* do_strides, float* delta, float* stats, int64_t B, int64_t H, int64_t S,
                                   int64_t head_dim, hipStream_t stream) {
     if (!o || !d_o || !lse2 || !delta || !stats || head_dim != HD || B <= 0 || H <= 0 || S <= 0 || S > (1 << 24)) return VGPA_ERR_INVALID;
-#define SOK(st) (stride_ok(st) && range_ok(st, B, H, S))
-    if (!SOK(o_strides) || !SOK(do_strides) || !al16(o) || !al16(d_o)) return VGPA_ERR_INVALID;
-    if (o_res && (!SOK(ores_strides) || !al16(o_res) || (res_kind != VGPA_RES_BF16 && res_kind != VGPA_RES_8))) return VGPA_ERR_INVALID;
+    if (!view_ok(o_strides, B, H, S, HD) || !view_ok(do_strides, B, H, S, HD) || !al16(o) || !al16(d_o)) return VGPA_ERR_INVALID;
+    if (o_res && (!view_ok(ores_strides, B, H, S, HD) || !al16(o_res) || (res_kind != VGPA_RES_BF16 && res_kind != VGPA_RES_8))) return VGPA_ERR_INVALID;
     const int64_t total = B * H * S;
     VGPA_LAUNCH(w1_bwd_prep_kernel, dim3((unsigned)((total * 8 + 255) / 256)), dim3(256), 0, stream, (const bf16_t*)d_o, (const bf16_t*)o, lse2,
                 mk(do_strides), mk(o_strides), (int)S, (int)H, total, delta, stats, o_res, o_res ? mk(ores_strides) : mk(o_strides),
@@ -729,46 +722,38 @@ int32_t vgpa_attn_bwd_prep_w1_res(const void* o, const void* o_res, int32_t res_
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }
-int32_t vgpa_attn_bwd_prep_w1(const void* o, const void* d_o, const float* lse2, const int64_t* o_strides, const int64_t* do_strides, float* delta,
-                              float* stats, int64_t B, int64_t H, int64_t S, int64_t head_dim, hipStream_t stream) {
-    return vgpa_attn_bwd_prep_w1_res(o, nullptr, VGPA_RES_NONE, d_o, lse2, o_strides, nullptr, do_strides, delta, stats, B, H, S, head_dim, stream);
-}
 
-// dK, dV on the w1 structure: arguments as vgpa_attn_bwd_dkv_ws, with `stats` (vgpa_attn_bwd_prep_w1) in the place of lse2 / delta
+// dK, dV on the w1 structure: arguments as vgpa_attn_bwd_dkv_ws, with `stats` (vgpa_attn_bwd_prep_w1_res) in the place of lse2 / delta
 int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const void* d_o, const float* stats, void* dk, void* dv,
                              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
                              const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
                              int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
     (void)scale;
     if (!q || !k || !v || !d_o || !stats || !dk || !dv || head_dim != HD || B <= 0 || H <= 0 || S <= 0 || S > (1 << 24)) return VGPA_ERR_INVALID;
-    if (!SOK(q_strides) || !SOK(k_strides) || !SOK(v_strides) || !SOK(do_strides) || !SOK(dk_strides) || !SOK(dv_strides) || !al16(q) || !al16(k) ||
-        !al16(v) || !al16(d_o) || !al16(dk) || !al16(dv) || (workspace && !al16(workspace)))
+    if (!view_ok(q_strides, B, H, S, HD) || !view_ok(k_strides, B, H, S, HD) || !view_ok(v_strides, B, H, S, HD) || !view_ok(do_strides, B, H, S, HD) ||
+        !view_ok(dk_strides, B, H, S, HD) || !view_ok(dv_strides, B, H, S, HD) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dk) ||
+        !al16(dv) || (workspace && !al16(workspace)))
         return VGPA_ERR_INVALID;
-#undef SOK
     const int n_t = (int)((S + 255) / 256);
     const int64_t tasks = (int64_t)n_t * B * H;
     if (tasks > 0x7fffffff) return VGPA_ERR_INVALID;
     const float kscale = 0.6931471805599453f;   // q arrives pre-scaled by scale * log2(e): dK = ln 2 * (dS^T Q)
-    int64_t n_main = tasks;
-    int nsplit = 1;
-    if (workspace) split_plan(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, &n_main, &nsplit, w1_slots());
-    const int64_t n_tail = tasks - n_main;
-    if (n_tail > 0 && ws_bytes < (size_t)n_tail * nsplit * 2 * 256 * HD * sizeof(float)) {
-        if (split_mode >= 2) return VGPA_ERR_WORKSPACE;
-        n_main = tasks;
-    }
-    if (n_main > 0) {
-        VGPA_LAUNCH((attn_bwd_dkv_w1_kernel<false>), dim3((unsigned)n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
+    TailSplit p;
+    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), 2 * 256 * HD * sizeof(float), workspace,
+                                       ws_bytes, 0, &p);
+    if (rc) return rc;
+    if (p.n_main > 0) {
+        VGPA_LAUNCH((attn_bwd_dkv_w1_kernel<false>), dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
                     (const bf16_t*)d_o, stats, (bf16_t*)dk, (bf16_t*)dv, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides), mk(dk_strides),
                     mk(dv_strides), (int)S, (int)H, n_t, kscale, 0, 1, (float*)nullptr);
         VGPA_CHECK_LAUNCH();
     }
-    if (n_main < tasks) {
-        VGPA_LAUNCH((attn_bwd_dkv_w1_kernel<true>), dim3((unsigned)(n_tail * nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+    if (p.n_tail > 0) {
+        VGPA_LAUNCH((attn_bwd_dkv_w1_kernel<true>), dim3((unsigned)(p.n_tail * p.nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (const bf16_t*)d_o, stats, (bf16_t*)dk, (bf16_t*)dv, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
-                    mk(dk_strides), mk(dv_strides), (int)S, (int)H, n_t, kscale, (int)n_main, nsplit, (float*)workspace);
+                    mk(dk_strides), mk(dv_strides), (int)S, (int)H, n_t, kscale, (int)p.n_main, p.nsplit, (float*)workspace);
         VGPA_CHECK_LAUNCH();
-        VGPA_LAUNCH(w1_dkv_merge_kernel, dim3((unsigned)(n_tail * 64)), dim3(256), 0, stream, (const float*)workspace, nsplit, (int)n_main, n_t,
+        VGPA_LAUNCH(w1_dkv_merge_kernel, dim3((unsigned)(p.n_tail * 64)), dim3(256), 0, stream, (const float*)workspace, p.nsplit, (int)p.n_main, n_t,
                     (bf16_t*)dk, (bf16_t*)dv, mk(dk_strides), mk(dv_strides), (int)S, (int)H, kscale);
         VGPA_CHECK_LAUNCH();
     }
@@ -780,12 +765,10 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
 // it holds max_k |k|^2 per (batch, head), one redo flag per 256-row strip and the tail-split partials.
 size_t vgpa_attn_fwd_w1_workspace_bytes(int64_t B, int64_t H, int64_t S) {
     const int64_t n_qt = (S + 255) / 256, tasks = n_qt * B * H;
-    int64_t parts = w1_slots();
-    if (tasks * W1_MAX_SPLIT < parts) parts = tasks * W1_MAX_SPLIT;
     const size_t head = (((size_t)(B * H) + (size_t)tasks) * 4 + 255) / 256 * 256;
-    return head + (size_t)parts * W1_FWD_PART_FLOATS * sizeof(float);
+    return head + (size_t)max_split_parts(tasks, W1_MAX_SPLIT, w1_slots()) * W1_FWD_PART_FLOATS * sizeof(float);
 }
-// vgpa_attn_fwd_w1 that also leaves what the bf16 rounding of the output dropped, for the backward's delta (vgpa_attn_bwd_prep_w1_res /
+// The forward can also leave what the bf16 rounding of the output dropped, for the backward's delta (vgpa_attn_bwd_prep_w1_res /
 // vgpa_attn_bwd_delta_res): o_res = a [B,H,S,64] view with its own element strides (NULL: not written) of
 //   res_kind VGPA_RES_BF16 (1): bf16, O_fp32 - bf16(O);   VGPA_RES_8 (2): uint8, eight further mantissa bits (common.h res8) -- half the bytes, O to 2^-17 either way
 static int32_t fwd_w1_impl(const void* q, const void* k, const void* v, void* o, void* o_res, int32_t res_kind, float* lse2, const int64_t* q_strides,
@@ -794,11 +777,10 @@ static int32_t fwd_w1_impl(const void* q, const void* k, const void* v, void* o,
                            hipStream_t stream, bool force_online) {
     (void)scale;
     if (!q || !k || !v || !o || !lse2 || !workspace || head_dim != HD || B <= 0 || H <= 0 || S <= 0 || S > (1 << 24)) return VGPA_ERR_INVALID;
-#define SOK(st) (stride_ok(st) && range_ok(st, B, H, S))
-    if (!SOK(q_strides) || !SOK(k_strides) || !SOK(v_strides) || !SOK(o_strides) || !al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(workspace))
+    if (!view_ok(q_strides, B, H, S, HD) || !view_ok(k_strides, B, H, S, HD) || !view_ok(v_strides, B, H, S, HD) || !view_ok(o_strides, B, H, S, HD) ||
+        !al16(q) || !al16(k) || !al16(v) || !al16(o) || !al16(workspace))
         return VGPA_ERR_INVALID;
-    if (o_res && (!SOK(ores_strides) || !al16(o_res) || (res_kind != VGPA_RES_BF16 && res_kind != VGPA_RES_8))) return VGPA_ERR_INVALID;
-#undef SOK
+    if (o_res && (!view_ok(ores_strides, B, H, S, HD) || !al16(o_res) || (res_kind != VGPA_RES_BF16 && res_kind != VGPA_RES_8))) return VGPA_ERR_INVALID;
     void* ores = o_res;
     const int rk = o_res ? (int)res_kind : VGPA_RES_NONE;
     const TStride sor = o_res ? mk(ores_strides) : mk(o_strides);
@@ -818,26 +800,22 @@ static int32_t fwd_w1_impl(const void* q, const void* k, const void* v, void* o,
     if (hipMemsetAsync(workspace, 0, head, stream) != hipSuccess) return VGPA_ERR_LAUNCH;
     VGPA_LAUNCH(w1_kmax_kernel, dim3(16, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)k, mk(k_strides), (int)S, (int)H, kmax2);
     VGPA_CHECK_LAUNCH();
-    int64_t n_main = tasks;
-    int nsplit = 1;
-    split_plan(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, &n_main, &nsplit, w1_slots());
-    const int64_t n_tail = tasks - n_main;
-    if (n_tail > 0 && ws_bytes < head + (size_t)n_tail * nsplit * W1_FWD_PART_FLOATS * sizeof(float)) {
-        if (split_mode >= 2) return VGPA_ERR_WORKSPACE;
-        n_main = tasks;
-    }
-    if (n_main > 0) {
-        VGPA_LAUNCH((attn_fwd_w1_kernel<false>), dim3((unsigned)n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
+    TailSplit p;   // the workspace is mandatory here: always planned
+    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), W1_FWD_PART_FLOATS * sizeof(float),
+                                       workspace, ws_bytes, head, &p);
+    if (rc) return rc;
+    if (p.n_main > 0) {
+        VGPA_LAUNCH((attn_fwd_w1_kernel<false>), dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
                     (bf16_t*)o, lse2, (const unsigned*)kmax2, flags, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)S, (int)H, n_qt, 0, 1,
                     (float*)nullptr, ores, sor, rk);
         VGPA_CHECK_LAUNCH();
     }
-    if (n_main < tasks) {
-        VGPA_LAUNCH((attn_fwd_w1_kernel<true>), dim3((unsigned)(n_tail * nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
+    if (p.n_tail > 0) {
+        VGPA_LAUNCH((attn_fwd_w1_kernel<true>), dim3((unsigned)(p.n_tail * p.nsplit)), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (bf16_t*)o, lse2, (const unsigned*)kmax2, flags, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)S,
-                    (int)H, n_qt, (int)n_main, nsplit, part, ores, sor, rk);
+                    (int)H, n_qt, (int)p.n_main, p.nsplit, part, ores, sor, rk);
         VGPA_CHECK_LAUNCH();
-        VGPA_LAUNCH(w1_fwd_merge_kernel, dim3((unsigned)(n_tail * 64)), dim3(256), 0, stream, (const float*)part, nsplit, (int)n_main, n_qt, (bf16_t*)o,
+        VGPA_LAUNCH(w1_fwd_merge_kernel, dim3((unsigned)(p.n_tail * 64)), dim3(256), 0, stream, (const float*)part, p.nsplit, (int)p.n_main, n_qt, (bf16_t*)o,
                     mk(o_strides), lse2, flags, (int)S, (int)H, ores, sor, rk);
         VGPA_CHECK_LAUNCH();
     }
@@ -860,12 +838,6 @@ int32_t vgpa_attn_fwd_online_res(const void* q, const void* k, const void* v, vo
                                  hipStream_t stream) {
     return fwd_w1_impl(q, k, v, o, o_res, res_kind, lse2, q_strides, k_strides, v_strides, o_strides, ores_strides, B, H, S, head_dim, scale, split_mode, workspace,
                        ws_bytes, stream, true);
-}
-int32_t vgpa_attn_fwd_w1(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides, const int64_t* k_strides,
-                         const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
-                         int32_t split_mode, void* workspace, size_t ws_bytes, hipStream_t stream) {
-    return vgpa_attn_fwd_w1_res(q, k, v, o, nullptr, VGPA_RES_NONE, lse2, q_strides, k_strides, v_strides, o_strides, nullptr, B, H, S, head_dim, scale, split_mode,
-                                workspace, ws_bytes, stream);
 }
 
 }  // extern "C"

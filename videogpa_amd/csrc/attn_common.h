@@ -1,4 +1,4 @@
-// Helpers shared by the attention translation units (attention.hip, attention_w1.hip).
+// Helpers shared by the attention translation units (attention.hip, attention_w1.hip, attention_hd128.hip).
 #pragma once
 #include "common.h"
 
@@ -42,12 +42,16 @@ __device__ __forceinline__ bf16x8_t shift_frag(float m, int hi) {
 }
 
 
-// ---- host side ----------------------------------------------------------------------------------------------------
-static inline bool stride_ok(const int64_t* st) { return st && st[0] >= 0 && st[1] >= 0 && st[2] >= HD && (st[0] % 8 == 0) && (st[1] % 8 == 0) && (st[2] % 8 == 0); }
-// every element offset reachable inside one (batch, head) slab and across the tensor must fit 31 bits
-static inline bool range_ok(const int64_t* st, int64_t B, int64_t H, int64_t S) {
-    return (B - 1) * st[0] + (H - 1) * st[1] + (S - 1) * st[2] + HD < ((int64_t)1 << 31);
+// ---- host side (head-dim independent: attention_hd128.hip uses it with hd = 128) ------------------------------------
+static inline bool stride_ok(const int64_t* st, int64_t hd) {
+    return st && st[0] >= 0 && st[1] >= 0 && st[2] >= hd && (st[0] % 8 == 0) && (st[1] % 8 == 0) && (st[2] % 8 == 0);
 }
+// every element offset reachable inside one (batch, head) slab and across the tensor must stay below `limit` (bf16 views: 31 bits)
+static inline bool range_ok(const int64_t* st, int64_t B, int64_t H, int64_t S, int64_t hd, int64_t limit = (int64_t)1 << 31) {
+    return (B - 1) * st[0] + (H - 1) * st[1] + (S - 1) * st[2] + hd < limit;
+}
+// a [B, H, S, hd] bf16 view by element strides: well-formed strides and addressable range
+static inline bool view_ok(const int64_t* st, int64_t B, int64_t H, int64_t S, int64_t hd) { return stride_ok(st, hd) && range_ok(st, B, H, S, hd); }
 static inline TStride mk(const int64_t* st) { TStride t; t.b = (uint32_t)st[0]; t.h = (uint32_t)st[1]; t.s = (uint32_t)st[2]; return t; }
 static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
@@ -84,6 +88,28 @@ static inline void split_plan(int64_t tasks, int nt, int split_mode, int max_spl
     if (k < 2) return;
     *n_main = tasks - rem;
     *nsplit = (int)k;
+}
+
+// Worst case of split_plan's partial sums: (leftover tasks) x (chunks) <= slots in automatic mode; forced mode (tests) splits every task.
+static inline int64_t max_split_parts(int64_t tasks, int max_split, int64_t slots) { return tasks * max_split < slots ? tasks * max_split : slots; }
+
+// The launch plan of one operation: n_main tasks as they are, n_tail tasks cut nsplit ways (n_tail = 0: a single launch).
+struct TailSplit { int64_t n_main, n_tail; int nsplit; };
+// split_plan, then the check of the partial-sum workspace (ws_head bytes of other use, then part_bytes per (tail task, chunk)): without a
+// workspace there is no split, automatic mode falls back to the single launch when it is short, forced mode (split_mode >= 2) returns
+// VGPA_ERR_WORKSPACE.  slots = 0: wg_slots().
+static inline int32_t plan_tail_split(int64_t tasks, int key_tiles, int split_mode, int max_split, int64_t slots, size_t part_bytes, const void* workspace,
+                                      size_t ws_bytes, size_t ws_head, TailSplit* out) {
+    out->n_main = tasks;
+    out->nsplit = 1;
+    if (workspace) split_plan(tasks, key_tiles, split_mode, max_split, &out->n_main, &out->nsplit, slots);
+    out->n_tail = tasks - out->n_main;
+    if (out->n_tail > 0 && ws_bytes < ws_head + (size_t)out->n_tail * out->nsplit * part_bytes) {
+        if (split_mode >= 2) return VGPA_ERR_WORKSPACE;
+        out->n_main = tasks;
+        out->n_tail = 0;
+    }
+    return VGPA_OK;
 }
 
 // attention.hip: the online-softmax forward over the flagged 256-row strips only (redo pass of the w1 forward)

@@ -463,22 +463,9 @@ static void lora_grad_plan(int64_t M, int64_t P, int64_t Q, int* n_pt, int* n_qt
     *splits = (M + r - 1) / r;
 }
 
-// G[P,Q] (fp32, row stride ldg, caller-zeroed) += s * U[M,P]^T V[M,Q]   (bf16 operands, P, Q multiples of 8); fp32 atomics: the
-// result is reproducible only to rounding.  vgpa_lora_grad_ws is the deterministic form.
-int32_t vgpa_lora_grad(const void* U, int64_t ldu, const void* V, int64_t ldv, float* G, int64_t ldg, float s, int64_t M, int64_t P, int64_t Q,
-                       hipStream_t stream) {
-    if (!U || !V || !G || M <= 0 || P <= 0 || Q <= 0 || P % 8 || Q % 8 || ldu % 8 || ldv % 8 || !a16(U) || !a16(V)) return VGPA_ERR_INVALID;
-    int n_pt, n_qt;
-    int64_t rows, splits;
-    lora_grad_plan(M, P, Q, &n_pt, &n_qt, &rows, &splits);
-    VGPA_LAUNCH(lora_grad_kernel, dim3((unsigned)(n_pt * n_qt), (unsigned)splits), dim3(256), 0, stream, (const bf16_t*)U, ldu, (const bf16_t*)V, ldv,
-                G, ldg, s, M, (int)P, (int)Q, rows, n_qt, (float*)nullptr);
-    VGPA_CHECK_LAUNCH();
-    return VGPA_OK;
-}
-
-// The same product, bit-reproducible: every row range writes its partial [P, Q] into the caller's workspace
-// (>= vgpa_lora_grad_workspace_bytes) and a merge kernel adds the partials in a fixed order.  G is overwritten (no zeroing needed).
+// G[P,Q] (fp32, row stride ldg) = s * U[M,P]^T V[M,Q]   (bf16 operands, P, Q multiples of 8), bit-reproducible: every row range writes
+// its partial [P, Q] into the caller's workspace (>= vgpa_lora_grad_workspace_bytes) and a merge kernel adds the partials in a fixed
+// order.  G is overwritten (no zeroing needed).
 size_t vgpa_lora_grad_workspace_bytes(int64_t M, int64_t P, int64_t Q) {
     if (M <= 0 || P <= 0 || Q <= 0) return 0;
     int n_pt, n_qt;

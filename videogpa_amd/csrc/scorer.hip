@@ -108,6 +108,9 @@ __global__ __launch_bounds__(SC_THREADS) void project_resolve_kernel(const unsig
 }
 
 // ---------------------------------------------------------------------------------------------- MSE with range heuristics
+// No entry point launches minmax_kernel / mse_kernel / mean_finish_kernel any more (vgpa_frame_metric in scorer2.hip is the product's MSE / PSNR).  They stay
+// for now because the compiler's inter-procedural passes see f32_unordered's callers together: without mse_kernel the only caller left passes a non-zero
+// word, and project_resolve_kernel below compiles to different (equivalent) code.  Delete them in a change that may alter this file's device code.
 // layout 0: [T,C,H,W]; 1: [T,H,W,C].  dtype 0: f32, 2: u8.
 __device__ __forceinline__ float img_at(const void* p, int dtype, int layout, int64_t t, int c, int64_t hw, int C, int64_t HW) {
     const size_t i = layout ? ((size_t)(t * HW + hw) * C + c) : ((size_t)(t * C + c) * HW + hw);
@@ -357,31 +360,6 @@ int32_t vgpa_project_points(const float* pc, const float* colors, const float* c
     }
     VGPA_LAUNCH(project_resolve_kernel, dim3(sc_grid(H * W, 1024), (unsigned)T), dim3(SC_THREADS), 0, stream, zbuf, colors, cmax, H * W, canvas,
                 out_f);
-    VGPA_CHECK_LAUNCH();
-    return VGPA_OK;
-}
-
-size_t vgpa_frame_mse_workspace_bytes(void) { return 1024 * sizeof(double) + 4 * sizeof(uint32_t); }
-
-// mean((gt01 - rep01)^2) with the reference's range heuristics.  dtype: 0 f32, 2 u8; layout: 0 [T,C,H,W], 1 [T,H,W,C];
-// is_tensor: 1 = torch.Tensor rules (min<0 -> [-1,1]; max>1 -> [0,255]), 0 = numpy rules (max>1 -> [0,255]).
-int32_t vgpa_frame_mse(const void* gt, int32_t gt_dtype, int32_t gt_layout, int32_t gt_is_tensor, const void* rep, int32_t rep_dtype,
-                       int32_t rep_layout, int32_t rep_is_tensor, int64_t T, int64_t C, int64_t H, int64_t W, float* out, void* workspace,
-                       size_t ws_bytes, hipStream_t stream) {
-    if (!gt || !rep || !out || !workspace || T <= 0 || C <= 0 || H <= 0 || W <= 0) return VGPA_ERR_INVALID;
-    if ((gt_dtype != 0 && gt_dtype != 2) || (rep_dtype != 0 && rep_dtype != 2)) return VGPA_ERR_INVALID;
-    if (ws_bytes < vgpa_frame_mse_workspace_bytes()) return VGPA_ERR_WORKSPACE;
-    double* partial = (double*)workspace;
-    uint32_t* mm = (uint32_t*)((char*)workspace + 1024 * sizeof(double));
-    const int64_t n = T * C * H * W;
-    if (hipMemsetAsync(mm, 0, 4 * sizeof(uint32_t), stream) != hipSuccess) return VGPA_ERR_LAUNCH;
-    const unsigned nb = sc_grid(n, 1024);
-    VGPA_LAUNCH(minmax_kernel, dim3(nb), dim3(SC_THREADS), 0, stream, gt, gt_dtype, rep, rep_dtype, n, mm);
-    VGPA_CHECK_LAUNCH();
-    VGPA_LAUNCH(mse_kernel, dim3(nb), dim3(SC_THREADS), 0, stream, gt, gt_dtype, gt_layout, gt_is_tensor, rep, rep_dtype, rep_layout,
-                rep_is_tensor, T, (int)C, H * W, mm, partial);
-    VGPA_CHECK_LAUNCH();
-    VGPA_LAUNCH(mean_finish_kernel, dim3(1), dim3(SC_THREADS), 0, stream, partial, (int)nb, 1.0 / (double)n, out);
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }

@@ -411,7 +411,8 @@ size_t vgpa_frame_metric_workspace_bytes(void) { return 1024 * sizeof(double) + 
 
 // MSEMetric / PSNRMetric.compute incl. the size-mismatch branch (metrics/mse.py:14-29,61-74): rep [T,C,H2,W2] is resized
 // bilinearly (align_corners=False) to gt's [H,W] after the range heuristics.  psnr = 0: out = mse; 1: out = 10 log10(1/mse),
-// 100 when mse == 0.  dtype / layout / is_tensor as vgpa_frame_mse.
+// 100 when mse == 0.  dtype: 0 f32, 2 u8; layout: 0 [T,C,H,W], 1 [T,H,W,C]; is_tensor: 1 = torch.Tensor rules (min<0 -> [-1,1];
+// max>1 -> [0,255]), 0 = numpy rules (max>1 -> [0,255]).
 int32_t vgpa_frame_metric(const void* gt, int32_t gt_dtype, int32_t gt_layout, int32_t gt_is_tensor, const void* rep, int32_t rep_dtype,
                           int32_t rep_layout, int32_t rep_is_tensor, int64_t T, int64_t C, int64_t H, int64_t W, int64_t H2, int64_t W2,
                           int32_t psnr, float* out, void* workspace, size_t ws_bytes, hipStream_t stream) {

@@ -998,11 +998,16 @@ class AttnFwdPolicy:
             self.mode, self.switched_at = "online", self.calls
 
 
+def _strip_flags(ws, head_words, B, H, Sq):
+    """the int32 redo flags [B, H, strips of 256 rows] a forward left in its workspace `ws` (uint8), behind `head_words` 32-bit words of other use:
+    B*H (max |k|^2 per head) for vgpa_attn_fwd_w1_res / vgpa_attn_fwd_online_res, 5*B*H (amax statistics + max |k|^2) for vgpa_attn128_fwd_f8"""
+    strips = (Sq + 255) // 256
+    return ws[:4 * (head_words + B * H * strips)].view(torch.int32)[head_words:].view(B, H, strips)
+
+
 def attention_redo_fraction(ws, B, H, S):
-    """fraction of the (batch, head, 256-row strip) tasks the last vgpa_attn_fwd_w1* call on workspace `ws` flagged and redid (synchronises)"""
-    tasks = B * H * ((S + 255) // 256)
-    flags = ws[:4 * (B * H + tasks)].view(torch.int32)[B * H:]
-    return float((flags != 0).float().mean())
+    """fraction of the (batch, head, 256-row strip) tasks the last vgpa_attn_fwd_w1_res call on workspace `ws` flagged and redid (synchronises)"""
+    return float((_strip_flags(ws, B * H, B, H, S) != 0).float().mean())
 
 
 def attention_fwd_raw(q, k, v, scale=None, q_prescaled=False, split_mode=None, o_pad=0, o_res=None, policy=None):
@@ -1136,9 +1141,7 @@ class F8AttnPolicy:
 
 def attention128_f8_redo_fraction(ws, B, H, Sq):
     """fraction of the (batch, head, 256-row strip) tasks the last vgpa_attn128_fwd_f8 call on workspace `ws` flagged and redid in bf16 (synchronises)"""
-    tasks = B * H * ((Sq + 255) // 256)
-    flags = ws[:4 * (5 * B * H + tasks)].view(torch.int32)[5 * B * H:]
-    return float((flags != 0).float().mean())
+    return float((_strip_flags(ws, 5 * B * H, B, H, Sq) != 0).float().mean())
 
 
 def attention128_fwd_raw(q, k, v, scale, o_pad=0, f8=False, o_res8=None, deq=None, report=None):
@@ -1179,7 +1182,7 @@ def attention128_fwd_raw(q, k, v, scale, o_pad=0, f8=False, o_res8=None, deq=Non
             ds_[0], ds_[1], ds_[2], B, H, Sq, Skv, float(scale), ws, ws_bytes, _stream()))
         if report is not None:          # tools / tests: what fraction of the strips the e4m3 kernel handed to the bf16 redo pass
             report["redo_fraction"] = attention128_f8_redo_fraction(ws, B, H, Sq)
-            report["strip_flags"] = (ws[:4 * (5 * B * H + B * H * ((Sq + 255) // 256))].view(torch.int32)[5 * B * H:] != 0).view(B, H, -1).clone()
+            report["strip_flags"] = _strip_flags(ws, 5 * B * H, B, H, Sq) != 0
         return o, lse
     if deq is not None:
         raise ValueError("attention128_fwd_raw: deq buffers are written by the e4m3 forward only (f8=True and at least ATTN128_F8_MIN_KEYS keys)")

@@ -416,6 +416,23 @@ int32_t vgpa_upsample_bilinear_ac_f32(const float* x, const float* xtab, const f
 int32_t vgpa_attn_small_f32(const float* q, const float* k, const float* v, int64_t stride_b, int64_t stride_h, int64_t stride_s,
                             float* o, int64_t B, int64_t H, int64_t S, int64_t D, float scale, vgpa_stream_t stream);
 
+/* ---- DINOv2 token embedding: DinoVisionTransformer.prepare_tokens_with_masks(x, masks=None), vggt/layers/vision_transformer.py:214-226
+ * (PatchEmbed.forward, vggt/layers/patch_embed.py:63-78; interpolate_pos_encoding's RESULT is the `pos` argument) (csrc/dino_embed.hip) ----
+ * images [N,3,H,W] NCHW contiguous, in_dtype 0 fp32 | 1 bf16, H and W multiples of `patch`; out [N, 1+R+P, C], P = (H/patch)(W/patch),
+ * out_dtype 0 | 1:  row 0 = cls_token + pos[0];  rows 1..R = register_tokens (no position);  row 1+R+j = W . patch_j + bias + pos[1+j].
+ * w_packed fp32 [k_packed][C] = the Conv2d weight [C,3,patch,patch] flattened to [C, 3 patch^2], transposed, zero-padded to k_packed =
+ * 3 patch^2 rounded up to 16 rows; bias, cls_token [C], register_tokens [R][C] (NULL when R = 0), pos [1+P][C] fp32.  C a multiple of 32;
+ * images, w_packed, pos and out 16-byte aligned.  One launch, an implicit GEMM on the exact-fp32 MFMA: every output element is one fp32
+ * chain in k order, so results are bit-identical for any split of the N frames over calls. */
+int32_t vgpa_dino_embed(const void* images, int32_t in_dtype, const float* w_packed, int64_t k_packed, const float* bias,
+                        const float* cls_token, const float* register_tokens, const float* pos, void* out, int32_t out_dtype, int64_t N,
+                        int64_t H, int64_t W, int64_t patch, int64_t C, int64_t R, vgpa_stream_t stream);
+/* The DINOv2 residual stream in fp32 (vggt/layers/block.py:77-98 as bf16 autocast evaluates it; csrc/dino_stream.hip), forward only, rows [M][D]:
+ * x_new = x + gamma * y (y bf16, gamma fp32 [D] = LayerScale; y, gamma and x_new all NULL skips the add), n = LayerNorm(x_new or x) * ln_w + ln_b in
+ * n_dtype 0 fp32 | 1 bf16 (ln_w, ln_b and n all NULL skips the norm).  x_new must not alias x. */
+int32_t vgpa_stream_ln_f32(const float* x, const void* y, const float* gamma, const float* ln_w, const float* ln_b, float* x_new, void* n,
+                           int32_t n_dtype, int64_t M, int64_t D, float eps, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -97,6 +97,8 @@ SIGNATURES = {
     "vgpa_dpt_tail_f32": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, P]),
     "vgpa_upsample_bilinear_ac_f32": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, P]),
     "vgpa_attn_small_f32": (I32, [P, P, P, I64, I64, I64, P, I64, I64, I64, I64, F32, P]),
+    "vgpa_dino_embed": (I32, [P, I32, P, I64, P, P, P, P, P, I32, I64, I64, I64, I64, I64, I64, P]),
+    "vgpa_stream_ln_f32": (I32, [P, P, P, P, P, P, P, I32, I64, I64, F32, P]),
 }
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library

@@ -1444,3 +1444,68 @@ def attn_small_f32(qkv, scale=None):
            lambda: _lib.call("vgpa_attn_small_f32", q, k, v, S * 3 * H * D, D, 3 * H * D, o, B, H, S, D, float(scale if scale is not None else D ** -0.5),
                              _stream()))
     return o
+
+
+# ---- DINOv2 token embedding (csrc/dino_embed.hip): forward only ----------------------------------------------------------------------------
+def pack_patch_weight(conv_weight):
+    """Conv2d weight [C, 3, p, p] of a kernel = stride patch projection -> [Kpad, C] fp32 contiguous: k = (channel, ky, kx) as the weight is laid
+    out, zero rows up to the next multiple of 16 (the kernel walks K in 16-wide chunks)"""
+    C = conv_weight.shape[0]
+    w = conv_weight.detach().float().reshape(C, -1).t()
+    K = w.shape[0]
+    out = torch.zeros((K + 15) // 16 * 16, C, device=w.device, dtype=torch.float32)
+    out[:K] = w
+    return out
+
+
+def dino_embed(images, w_packed, bias, cls, reg, pos, out_dtype=torch.bfloat16):
+    """DinoVisionTransformer.prepare_tokens_with_masks(x, masks=None) in one launch.  images [N,3,H,W] fp32 | bf16; w_packed from pack_patch_weight;
+    bias [C], cls [C] (or [1,1,C]), reg [R,C] | None, pos [1+P,C] (or [1,1+P,C]): fp32 -> tokens [N, 1+R+P, C] in out_dtype (fp32 | bf16):
+    row 0 = cls + pos[0], rows 1..R = reg, row 1+R+j = W . patch_j + bias + pos[1+j]."""
+    _req(images)
+    for t in (w_packed, bias, cls, reg, pos):
+        if t is not None:
+            _req(t, torch.float32)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (images, w_packed, bias, cls, reg, pos)):
+        raise RuntimeError("dino_embed is forward only: call it under torch.no_grad()")
+    if images.dtype not in _DT or out_dtype not in _DT:
+        raise RuntimeError(f"dino_embed: fp32 or bf16 images and output, got {images.dtype} -> {out_dtype}")
+    N, three, H, W = images.shape
+    Kpad, C = w_packed.shape
+    if three != 3 or (Kpad // 3) < 1:
+        raise RuntimeError(f"dino_embed: images {tuple(images.shape)} are not [N,3,H,W]")
+    R = 0 if reg is None else reg.shape[-2]
+    cls, pos = cls.reshape(-1), pos.reshape(-1, C)
+    reg = None if reg is None else reg.reshape(R, C)
+    p = next((c for c in range(1, 65) if (3 * c * c + 15) // 16 * 16 == Kpad and H % c == 0 and pos.shape[0] == 1 + (H // c) * (W // c)), None) \
+        if W > 0 and H > 0 else None
+    if p is None or W % p or bias.numel() != C or cls.numel() != C or C % 32:
+        raise RuntimeError(f"dino_embed: weight {tuple(w_packed.shape)}, position table {tuple(pos.shape)} and images {tuple(images.shape)} do not "
+                           "fit one patch size (H, W multiples of it; channels a multiple of 32)")
+    P = (H // p) * (W // p)
+    out = torch.empty(N, 1 + R + P, C, device=images.device, dtype=out_dtype)
+    _timed("dino_embed", 2.0 * N * P * C * 3 * p * p,
+           lambda: _lib.call("vgpa_dino_embed", images, _DT[images.dtype], w_packed, Kpad, bias, cls, reg, pos, out, _DT[out_dtype], N, H, W, p, C, R,
+                             _stream()))
+    return out
+
+
+def stream_ln(x, y=None, gamma=None, ln_w=None, ln_b=None, eps=1e-6, n_dtype=torch.bfloat16):
+    """The fp32 residual stream of the DINOv2 blocks: x fp32 [..., D]; with y (bf16) and gamma (fp32 [D]) x_new = x + gamma * y; with ln_w / ln_b
+    n = LayerNorm(x_new or x) in n_dtype -> (x_new | None, n | None).  Forward only."""
+    _req(x, torch.float32)
+    for t, dt in ((y, torch.bfloat16), (gamma, torch.float32), (ln_w, torch.float32), (ln_b, torch.float32)):
+        if t is not None:
+            _req(t, dt)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, y, gamma, ln_w, ln_b)):
+        raise RuntimeError("stream_ln is forward only: call it under torch.no_grad()")
+    D = x.shape[-1]
+    if (y is not None and y.shape != x.shape) or any(t is not None and t.numel() != D for t in (gamma, ln_w, ln_b)) or n_dtype not in _DT:
+        raise RuntimeError("stream_ln: shapes of x, y, gamma and the LayerNorm parameters do not fit")
+    x_new = torch.empty_like(x) if y is not None else None
+    n = torch.empty(x.shape, device=x.device, dtype=n_dtype) if ln_w is not None else None
+    M = x.numel() // D
+    nbytes = 4.0 + (6.0 if y is not None else 0.0) + (0.0 if n is None else n.element_size())          # per element: x (+ y, x_new) (+ n)
+    _timed("stream_ln_f32", nbytes * M * D,
+           lambda: _lib.call("vgpa_stream_ln_f32", x, y, gamma, ln_w, ln_b, x_new, n, _DT[n_dtype], M, D, float(eps), _stream()), "byte")
+    return x_new, n

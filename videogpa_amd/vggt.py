@@ -14,8 +14,16 @@ checkpoints load by name:
 Unlike the CogVideoX attention (un-vendored diffusers), this code is IN the reference tree, so the kernels behind it are pinned
 against reference outputs: tests/golden/vggt_attention.pt, tests/test_gpu_vggt.py.  The backbone is frozen in the reference's use
 (metrics only): gradients flow to the input and to the Linear layers (torch autograd around the kernels); LayerNorm / LayerScale
-parameters get none.  head_dim must be 64 and qk_norm on (what VGGT-1B's aggregator uses: dim 1024, 16 heads).  Patch embedding
-(DINOv2) and checkpoint loading stay the caller's (third-party networks, outside the path).
+parameters get none.  head_dim must be 64 and qk_norm on (what VGGT-1B's aggregator uses: dim 1024, 16 heads).
+
+The aggregator's patch embedding is reference-held as well (forward only, bf16 GEMMs and attention around an fp32 residual stream; pinned on
+tests/golden/vggt_dinov2*.pt, tests/test_gpu_dinov2.py):
+
+    DinoVisionTransformer    vggt/layers/vision_transformer.py:42-331 (block_chunks=0, ffn_layer="mlp"; patch projection + class / register tokens +
+                                                                position table in ONE launch, csrc/dino_embed.hip; blocks without QK-norm / RoPE:
+                                                                stream_ln -> qkv -> attention -> proj -> stream_ln -> mlp -> stream_ln, csrc/dino_stream.hip)
+    vit_small / vit_base / vit_large / vit_giant2             :341-397; Aggregator(patch_embed="dinov2_vit{s,b,l}14_reg" | "dinov2_vitg2_reg")
+                                                                builds them as vggt/models/aggregator.py:143-182 does
 
 The prediction heads are reference-held too and sit below the aggregator (fp32, forward only, csrc/vggt_heads.hip; pinned on
 tests/golden/vggt_heads.pt, tests/test_gpu_vggt_heads.py):
@@ -24,6 +32,9 @@ tests/golden/vggt_heads.pt, tests/test_gpu_vggt_heads.py):
     DPTHead                  vggt/heads/dpt_head.py:21-484    (channels-last; every convolution is the fp32-MFMA implicit GEMM, the full-resolution
                                                                 end of the head is one fused launch)
     VGGT                     vggt/models/vggt.py:17-96        (aggregator + camera / depth / point heads; no track head)"""
+import math
+import os
+
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -168,12 +179,257 @@ def slice_expand_and_flatten(token_tensor, B, S):
     return torch.cat([first, rest], dim=1).reshape(B * S, *token_tensor.shape[2:])
 
 
+# ---------------------------------------------------------------------------------------------------------------- DINOv2 patch embedding
+def _forward_only(module, *tensors):
+    if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(t.requires_grad for t in tensors)):
+        raise RuntimeError(f"{type(module).__name__} is forward only (no backward kernels): call it under torch.no_grad()")
+
+
+class _PackedCache:
+    """fp32 kernel-layout copies of parameters, rebuilt when a parameter's `_version`, storage or device changes"""
+
+    def __init__(self):
+        self._c = {}
+
+    def get(self, key, params, make):
+        tag = tuple((p._version, p.data_ptr(), str(p.device), p.dtype) for p in params)
+        hit = self._c.get(key)
+        if hit is None or hit[0] != tag:
+            with torch.no_grad():
+                hit = (tag, make())
+            self._c[key] = hit
+        return hit[1]
+
+
+class DinoAttention(nn.Module):
+    """vggt/layers/attention.py:21-93 as DINOv2 builds it (MemEffAttention without xFormers = Attention): no QK-norm, no RoPE, head_dim 64.  The
+    parameters only live here; DinoBlock runs them."""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=True, proj_bias=True):
+        super().__init__()
+        if dim % num_heads or dim // num_heads != 64:
+            raise NotImplementedError("the HIP attention path covers head_dim 64 (every DINOv2 variant: 384/6, 768/12, 1024/16, 1536/24)")
+        self.num_heads, self.head_dim, self.scale = num_heads, 64, 64 ** -0.5
+        self.qkv = nn.Linear(dim, dim * 3, bias=qkv_bias)
+        self.proj = nn.Linear(dim, dim, bias=proj_bias)
+
+
+class DinoBlock(nn.Module):
+    """vggt/layers/block.py:27-98 at DINOv2's settings (LayerScale on, LayerNorm eps 1e-6, erf-GELU Mlp), forward only.  The residual stream is fp32, as
+    bf16 autocast keeps it upstream (ops.stream_ln: LayerNorm, and x + gamma * y with the LayerNorm behind it in one pass); the GEMMs and the head_dim-64
+    flash attention (on the three strided views of the qkv GEMM's output) are bf16: stream_ln (norm1) -> qkv -> attention -> proj -> stream_ln (ls1.gamma,
+    norm2) -> fc1, GELU, fc2 -> stream_ln (ls2.gamma).  head_dim**-0.5 * log2(e), which the attention kernel wants on q, is folded into the q rows of a cached bf16
+    copy of qkv.weight / qkv.bias (one bf16 rounding, as ops.prescale_q costs): no permute, no prescale pass."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, proj_bias=True, ffn_bias=True, init_values=None, eps=1e-6):
+        super().__init__()
+        if not init_values:
+            raise NotImplementedError("DINOv2 blocks without LayerScale are not used by VGGT's aggregator (init_values=1.0)")
+        self.norm1 = nn.LayerNorm(dim, eps=eps)
+        self.attn = DinoAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, proj_bias=proj_bias)
+        self.ls1 = LayerScale(dim, init_values)
+        self.norm2 = nn.LayerNorm(dim, eps=eps)
+        self.mlp = Mlp(dim, int(dim * mlp_ratio), bias=ffn_bias)
+        self.ls2 = LayerScale(dim, init_values)
+        self._packed = _PackedCache()
+
+    def _qkv(self):
+        w, b = self.attn.qkv.weight, self.attn.qkv.bias
+
+        def make():
+            C = w.shape[1]
+            f = torch.ones(3 * C, device=w.device, dtype=torch.float32)
+            f[:C] = self.attn.scale * ops.LOG2E
+            return (w.detach().float() * f[:, None]).to(torch.bfloat16).contiguous(), \
+                (None if b is None else (b.detach().float() * f).to(torch.bfloat16).contiguous())
+        return self._packed.get("qkv", [w] + ([] if b is None else [b]), make)
+
+    def forward(self, x):
+        """x fp32 [B,N,C] (the residual stream stays fp32, as bf16 autocast keeps it upstream) -> fp32 [B,N,C]"""
+        B, N, C = x.shape
+        H = self.attn.num_heads
+        _, n1 = ops.stream_ln(x, None, None, _f32(self.norm1.weight), _f32(self.norm1.bias), self.norm1.eps)
+        qkv = F.linear(n1, *self._qkv()).view(B, N, 3, H, 64)          # q already carries scale * log2(e)
+        q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))   # [B,H,N,64] views of the GEMM output, read in place
+        o, _ = ops.attention_fwd_raw(q, k, v, scale=self.attn.scale, q_prescaled=True)
+        a = self.attn.proj(o)
+        x, n2 = ops.stream_ln(x, a.contiguous(), _f32(self.ls1.gamma), _f32(self.norm2.weight), _f32(self.norm2.bias), self.norm2.eps)
+        return ops.stream_ln(x, self.mlp(n2).contiguous(), _f32(self.ls2.gamma))[0]
+
+
+class DinoVisionTransformer(nn.Module):
+    """vggt/layers/vision_transformer.py:42-331 on the HIP kernels: the reference's constructor arguments and, with block_chunks=0, its state-dict
+    names (patch_embed.proj.*, cls_token, pos_embed, register_tokens, mask_token, blocks.N.*, norm.*), so the `aggregator.patch_embed.*` part of a
+    VGGT checkpoint loads by name.  `forward(x [N,3,H,W], already normalised) -> {x_norm_clstoken, x_norm_regtokens, x_norm_patchtokens, x_prenorm,
+    masks: None}` in fp32 (what bf16 autocast returns upstream).  Forward only; bf16 parameters, or fp32 parameters under bf16 autocast (the contract of the
+    aggregator's blocks).  What the
+    aggregator never builds raises: block_chunks > 0, ffn_layer other than "mlp", masks, list inputs, qk_norm, stochastic depth in training."""
+
+    def __init__(self, img_size=224, patch_size=16, in_chans=3, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4.0, qkv_bias=True, ffn_bias=True,
+                 proj_bias=True, drop_path_rate=0.0, drop_path_uniform=False, init_values=None, embed_layer=PatchEmbed, act_layer=nn.GELU,
+                 block_fn=DinoBlock, ffn_layer="mlp", block_chunks=1, num_register_tokens=0, interpolate_antialias=False, interpolate_offset=0.1,
+                 qk_norm=False):
+        super().__init__()
+        if block_chunks > 0:
+            raise NotImplementedError("block_chunks > 0 (FSDP wrapping; renames the blocks): the aggregator builds block_chunks=0")
+        if ffn_layer != "mlp":
+            raise NotImplementedError(f"ffn_layer={ffn_layer!r}: the aggregator's DINOv2 uses 'mlp'")
+        if qk_norm:
+            raise NotImplementedError("qk_norm=True: DINOv2 has no QK-norm (the aggregator's own blocks do: vggt.Block)")
+        if in_chans != 3 or act_layer is not nn.GELU or embed_layer is not PatchEmbed or isinstance(patch_size, (tuple, list)):
+            raise NotImplementedError("DinoVisionTransformer on the HIP path: 3 input channels, square patches, PatchEmbed, nn.GELU")
+        if embed_dim % num_heads or embed_dim // num_heads != 64:
+            raise NotImplementedError("the HIP attention path covers head_dim 64")
+        if num_register_tokens < 0:
+            raise ValueError("num_register_tokens must be >= 0")
+        self.num_features = self.embed_dim = embed_dim
+        self.num_tokens, self.n_blocks, self.num_heads, self.patch_size = 1, depth, num_heads, patch_size
+        self.num_register_tokens, self.interpolate_antialias, self.interpolate_offset = num_register_tokens, interpolate_antialias, interpolate_offset
+        self.drop_path_rate, self.chunked_blocks = drop_path_rate, False
+        self.patch_embed = embed_layer(img_size=img_size, patch_size=patch_size, in_chans=in_chans, embed_dim=embed_dim)
+        grid = (img_size // patch_size, img_size // patch_size) if isinstance(img_size, int) else (img_size[0] // patch_size, img_size[1] // patch_size)
+        num_patches = grid[0] * grid[1]
+        self.cls_token = nn.Parameter(torch.zeros(1, 1, embed_dim))
+        self.pos_embed = nn.Parameter(torch.zeros(1, num_patches + self.num_tokens, embed_dim))
+        self.register_tokens = nn.Parameter(torch.zeros(1, num_register_tokens, embed_dim)) if num_register_tokens else None
+        self.blocks = nn.ModuleList([block_fn(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, proj_bias=proj_bias,
+                                              ffn_bias=ffn_bias, init_values=init_values) for _ in range(depth)])
+        self.norm = nn.LayerNorm(embed_dim, eps=1e-6)
+        self.head = nn.Identity()
+        self.mask_token = nn.Parameter(torch.zeros(1, embed_dim))
+        self._packed = _PackedCache()
+        self.init_weights()
+
+    def init_weights(self):
+        nn.init.trunc_normal_(self.pos_embed, std=0.02)
+        nn.init.normal_(self.cls_token, std=1e-6)
+        if self.register_tokens is not None:
+            nn.init.normal_(self.register_tokens, std=1e-6)
+        for m in self.modules():                                 # init_weights_vit_timm
+            if isinstance(m, nn.Linear):
+                nn.init.trunc_normal_(m.weight, std=0.02)
+                if m.bias is not None:
+                    nn.init.zeros_(m.bias)
+
+    # ---- position table: a function of the parameter and the grid only
+    def _interpolated(self, w0, h0):
+        """fp32 [1, 1 + w0 * h0, C]; `w0` counts patches along the image's FIRST spatial axis, as the reference names it (:180-212)"""
+        pos = self.pos_embed.detach().float()
+        N = pos.shape[1] - 1
+        M = int(math.sqrt(N))
+        assert N == M * M
+        kwargs = {}
+        if self.interpolate_offset:
+            kwargs["scale_factor"] = (float(w0 + self.interpolate_offset) / M, float(h0 + self.interpolate_offset) / M)
+        else:
+            kwargs["size"] = (w0, h0)
+        patch = F.interpolate(pos[:, 1:].reshape(1, M, M, -1).permute(0, 3, 1, 2), mode="bicubic", antialias=self.interpolate_antialias, **kwargs)
+        assert (w0, h0) == tuple(patch.shape[-2:])
+        return torch.cat((pos[:, :1], patch.permute(0, 2, 3, 1).reshape(1, w0 * h0, -1)), dim=1).contiguous()
+
+    def pos_table(self, w, h):
+        """interpolate_pos_encoding for an image of w x h pixels (first, second spatial axis): the parameter itself when the grid is the trained
+        square one, else the bicubic resample in fp32, cached per (grid, device, pos_embed._version)"""
+        w0, h0 = w // self.patch_size, h // self.patch_size
+        if w0 * h0 == self.pos_embed.shape[1] - 1 and w == h:
+            return self.pos_embed
+        return self._packed.get(("pos", w0, h0), [self.pos_embed], lambda: self._interpolated(w0, h0))
+
+    def interpolate_pos_encoding(self, x, w, h):
+        assert x.shape[1] - 1 == (w // self.patch_size) * (h // self.patch_size)
+        t = self.pos_table(w, h)
+        return t if t is self.pos_embed else t.to(x.dtype)
+
+    def _embed_params(self):
+        pe = self.patch_embed.proj
+        ps = [pe.weight, pe.bias, self.cls_token] + ([] if self.register_tokens is None else [self.register_tokens])
+        return self._packed.get("embed", ps, lambda: (ops.pack_patch_weight(pe.weight), pe.bias.detach().float().contiguous(),
+                                                      self.cls_token.detach().float().reshape(-1).contiguous(),
+                                                      None if self.register_tokens is None else self.register_tokens.detach().float()[0].contiguous()))
+
+    def prepare_tokens_with_masks(self, x, masks=None, out_dtype=torch.float32):
+        """:214-226 in one launch (ops.dino_embed); x [N,3,w,h] fp32 | bf16 -> [N, 1 + R + P, C]"""
+        if masks is not None:
+            raise NotImplementedError("masks (iBOT training) are not used by VGGT")
+        _forward_only(self, x)
+        _, _, w, h = x.shape
+        if w % self.patch_size or h % self.patch_size:
+            raise AssertionError(f"input image size {(w, h)} is not a multiple of the patch size {self.patch_size}")
+        pos = self.pos_table(w, h)
+        if pos is self.pos_embed:
+            pos = _f32(pos)
+        wp, bias, cls, reg = self._embed_params()
+        return ops.dino_embed(x.contiguous(), wp, bias, cls, reg, pos[0], out_dtype)
+
+    def _tokens(self, x, masks=None):
+        if isinstance(x, (list, tuple)):
+            raise NotImplementedError("list inputs (nested tensors, xFormers) are not used by VGGT")
+        if self.training and self.drop_path_rate > 0:
+            raise NotImplementedError("stochastic depth (drop_path_rate > 0 in training mode): the backbone is forward only")
+        if next(self.blocks.parameters()).dtype != torch.bfloat16 and not torch.is_autocast_enabled():
+            raise RuntimeError("DinoVisionTransformer computes in bf16: bf16 parameters, or fp32 parameters under torch.autocast(dtype=torch.bfloat16)")
+        return self.prepare_tokens_with_masks(x, masks)
+
+    def _norm(self, x):
+        return ops.stream_ln(x, None, None, _f32(self.norm.weight), _f32(self.norm.bias), self.norm.eps, n_dtype=torch.float32)[1]
+
+    def forward_features(self, x, masks=None):
+        x = self._tokens(x, masks)
+        for blk in self.blocks:
+            x = blk(x)
+        x_norm, R = self._norm(x), self.num_register_tokens
+        return {"x_norm_clstoken": x_norm[:, 0], "x_norm_regtokens": x_norm[:, 1:R + 1], "x_norm_patchtokens": x_norm[:, R + 1:], "x_prenorm": x,
+                "masks": masks}
+
+    def get_intermediate_layers(self, x, n=1, reshape=False, return_class_token=False, norm=True):
+        t = self._tokens(x)
+        take = range(len(self.blocks) - n, len(self.blocks)) if isinstance(n, int) else n
+        outputs = []
+        for i, blk in enumerate(self.blocks):
+            t = blk(t)
+            if i in take:
+                outputs.append(t)
+        assert len(outputs) == len(take), f"only {len(outputs)} / {len(take)} blocks found"
+        if norm:
+            outputs = [self._norm(o) for o in outputs]
+        class_tokens = [o[:, 0] for o in outputs]
+        outputs = [o[:, 1 + self.num_register_tokens:] for o in outputs]
+        if reshape:
+            B, _, w, h = x.shape
+            outputs = [o.reshape(B, w // self.patch_size, h // self.patch_size, -1).permute(0, 3, 1, 2).contiguous() for o in outputs]
+        return tuple(zip(outputs, class_tokens)) if return_class_token else tuple(outputs)
+
+    def forward(self, *args, is_training=True, **kwargs):
+        ret = self.forward_features(*args, **kwargs)
+        return ret if is_training else self.head(ret["x_norm_clstoken"])
+
+
+def vit_small(patch_size=16, num_register_tokens=0, **kwargs):
+    return DinoVisionTransformer(patch_size=patch_size, embed_dim=384, depth=12, num_heads=6, mlp_ratio=4, num_register_tokens=num_register_tokens, **kwargs)
+
+
+def vit_base(patch_size=16, num_register_tokens=0, **kwargs):
+    return DinoVisionTransformer(patch_size=patch_size, embed_dim=768, depth=12, num_heads=12, mlp_ratio=4, num_register_tokens=num_register_tokens, **kwargs)
+
+
+def vit_large(patch_size=16, num_register_tokens=0, **kwargs):
+    return DinoVisionTransformer(patch_size=patch_size, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4, num_register_tokens=num_register_tokens, **kwargs)
+
+
+def vit_giant2(patch_size=16, num_register_tokens=0, **kwargs):
+    return DinoVisionTransformer(patch_size=patch_size, embed_dim=1536, depth=40, num_heads=24, mlp_ratio=4, num_register_tokens=num_register_tokens, **kwargs)
+
+
+DINOV2_MODELS = {"dinov2_vitl14_reg": vit_large, "dinov2_vitb14_reg": vit_base, "dinov2_vits14_reg": vit_small, "dinov2_vitg2_reg": vit_giant2}
+
+
 class Aggregator(nn.Module):
     """vggt/models/aggregator.py:25-258 on the HIP attention path: `forward(images [B, S, 3, H, W] in [0, 1]) -> (list of [B, S, P, 2C] per depth,
     patch_start_idx)`.  Constructor arguments, parameter names and the order of operations are the reference's, so an aggregator state dict loads with
-    load_state_dict.  patch_embed: "conv" builds the reference's PatchEmbed; the DINOv2 backbones ("dinov2_vitl14_reg", ...) are third-party networks
-    outside this path -- pass the constructed module instead (anything mapping [B*S, 3, H, W] to patch tokens [B*S, N, C] or to a dict carrying
-    "x_norm_patchtokens"), it is registered under the same name `patch_embed`."""
+    load_state_dict.  patch_embed: "conv" builds the reference's PatchEmbed; "dinov2_vitl14_reg" (the default), "dinov2_vitb14_reg",
+    "dinov2_vits14_reg" and "dinov2_vitg2_reg" build the DinoVisionTransformer below with the reference's arguments (aggregator.py:147-178); a
+    constructed module (anything mapping [B*S, 3, H, W] to patch tokens [B*S, N, C] or to a dict carrying "x_norm_patchtokens") is registered as
+    it is under the same name `patch_embed`."""
 
     def __init__(self, img_size=518, patch_size=14, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4.0, num_register_tokens=4, block_fn=Block,
                  qkv_bias=True, proj_bias=True, ffn_bias=True, patch_embed="dinov2_vitl14_reg", aa_order=("frame", "global"), aa_block_size=1,
@@ -184,8 +440,13 @@ class Aggregator(nn.Module):
         elif "conv" in patch_embed:
             self.patch_embed = PatchEmbed(img_size=img_size, patch_size=patch_size, in_chans=3, embed_dim=embed_dim)
         else:
-            raise NotImplementedError(f"patch_embed={patch_embed!r}: the DINOv2 backbone is a third-party network outside this path; construct it and pass "
-                                      "the module as patch_embed=")
+            if patch_embed not in DINOV2_MODELS:
+                raise KeyError(f"patch_embed={patch_embed!r}: 'conv', one of {sorted(DINOV2_MODELS)}, or a module")
+            self.patch_embed = DINOV2_MODELS[patch_embed](img_size=img_size, patch_size=patch_size, num_register_tokens=num_register_tokens,
+                                                          interpolate_antialias=True, interpolate_offset=0.0, block_chunks=0, init_values=1.0)
+            if self.patch_embed.embed_dim != embed_dim:
+                raise ValueError(f"patch_embed={patch_embed!r} is {self.patch_embed.embed_dim} wide, the aggregator {embed_dim}")
+            self.patch_embed.mask_token.requires_grad_(False)
         self.rope = RotaryPositionEmbedding2D(frequency=rope_freq) if rope_freq > 0 else None
         self.position_getter = PositionGetter() if self.rope is not None else None
         mk = lambda: block_fn(dim=embed_dim, num_heads=num_heads, mlp_ratio=mlp_ratio, qkv_bias=qkv_bias, proj_bias=proj_bias, ffn_bias=ffn_bias,
@@ -220,6 +481,8 @@ class Aggregator(nn.Module):
         patch_tokens = self.patch_embed(images.to(next(self.frame_blocks.parameters()).dtype))
         if isinstance(patch_tokens, dict):
             patch_tokens = patch_tokens["x_norm_patchtokens"]
+        if isinstance(self.patch_embed, DinoVisionTransformer):
+            patch_tokens = patch_tokens.to(torch.bfloat16)       # the backbone returns fp32 (its stream is fp32); the blocks below run a bf16 stream
         tokens = torch.cat([slice_expand_and_flatten(self.camera_token, B, S).to(patch_tokens.dtype),
                             slice_expand_and_flatten(self.register_token, B, S).to(patch_tokens.dtype), patch_tokens], dim=1)
         pos = None
@@ -252,27 +515,6 @@ class Aggregator(nn.Module):
 
 
 # ---------------------------------------------------------------------------------------------------------------- prediction heads
-def _forward_only(module, *tensors):
-    if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(t.requires_grad for t in tensors)):
-        raise RuntimeError(f"{type(module).__name__} is forward only (no backward kernels): call it under torch.no_grad()")
-
-
-class _PackedCache:
-    """fp32 kernel-layout copies of parameters, rebuilt when a parameter's `_version`, storage or device changes"""
-
-    def __init__(self):
-        self._c = {}
-
-    def get(self, key, params, make):
-        tag = tuple((p._version, p.data_ptr(), str(p.device), p.dtype) for p in params)
-        hit = self._c.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                hit = (tag, make())
-            self._c[key] = hit
-        return hit[1]
-
-
 class TrunkAttention(nn.Module):
     """vggt/layers/attention.py:21-72 as the camera trunk builds it: no QK-norm, no RoPE, any head_dim in multiples of 32, a few tokens (one per frame)"""
 
@@ -523,7 +765,8 @@ class DPTHead(nn.Module):
 class VGGT(nn.Module):
     """vggt/models/vggt.py:17-96 without the track head: `forward(images [S,3,H,W] | [B,S,3,H,W] in [0,1]) -> {pose_enc, pose_enc_list, depth,
     depth_conf, world_points, world_points_conf, images (eval mode)}`.  The aggregator runs in whatever precision the caller set (bf16
-    autocast in the scorer); the heads compute in fp32 as upstream (autocast off, :65).  `patch_embed` as the Aggregator takes it;
+    autocast in the scorer); the heads compute in fp32 as upstream (autocast off, :65).  `patch_embed` as the Aggregator takes it (default: the DINOv2
+    ViT-L/14-reg built here, so VGGT() matches a VGGT-1B checkpoint; from_pretrained(dir) loads one from local files);
     aggregator_kwargs / camera_kwargs / dpt_kwargs reach the three constructors (reduced configurations; VGGT-1B needs none).  `track_head.*` keys of a reference checkpoint are dropped on load."""
 
     def __init__(self, img_size=518, patch_size=14, embed_dim=1024, enable_camera=True, enable_point=True, enable_depth=True, enable_track=False,
@@ -542,6 +785,27 @@ class VGGT(nn.Module):
 
     def load_state_dict(self, state_dict, strict=True, **kw):
         return super().load_state_dict({k: v for k, v in state_dict.items() if not k.startswith("track_head.")}, strict=strict, **kw)
+
+    @classmethod
+    def from_pretrained(cls, path, **kwargs):
+        """A VGGT checkpoint from the LOCAL file system (never the network): `path` is a directory holding model.safetensors or model.pt, or such a
+        file; **kwargs reach the constructor (none for VGGT-1B).  `track_head.*` keys are dropped; everything else must match by name."""
+        path = os.fspath(path)
+        if os.path.isdir(path):
+            found = [f for f in ("model.safetensors", "model.pt") if os.path.isfile(os.path.join(path, f))]
+            if not found:
+                raise FileNotFoundError(f"{path}: neither model.safetensors nor model.pt (from_pretrained reads local checkpoints only)")
+            path = os.path.join(path, found[0])
+        elif not os.path.isfile(path):
+            raise FileNotFoundError(f"{path}: no such checkpoint file or directory (from_pretrained reads local checkpoints only)")
+        if path.endswith(".safetensors"):
+            from safetensors.torch import load_file
+            state = load_file(path)
+        else:
+            state = torch.load(path, map_location="cpu", weights_only=True)
+        model = cls(**kwargs)
+        model.load_state_dict(state, strict=True)
+        return model.eval()
 
     def run_heads(self, aggregated_tokens_list, images, patch_start_idx):
         predictions = {}

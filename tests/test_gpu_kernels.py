@@ -9,6 +9,8 @@ import torch.nn.functional as F
 
 pytestmark = pytest.mark.gpu
 
+import attn_tol
+from attn_ref64 import attn_ref64
 from attn_tol import lse2_tol
 from oracle import cogvideox as ocv
 from oracle import dpo as odpo
@@ -189,6 +191,14 @@ def test_attention_fwd_bwd_raw(ops, B, H, S):
     for name, a, r in (("dq", dq, dq_ref), ("dk", dk, dk_ref), ("dv", dv, dv_ref)):
         e = (a.double().cpu() - r).abs().max().item()
         assert e < 0.03 * r.abs().max().item() + 2e-3, f"{name} max err {e} (ref max {r.abs().max().item()})"
+    # per element, inside the derived bounds of tests/attn_tol.py (w1 forward: row sum of the rounded weights; no residual handed over: the textbook delta)
+    problems, dod = [], dev(do)
+    for b in range(B):
+        for h in range(H):
+            qs = (qd[b, h].float() * (64 ** -0.5 * attn_tol.LOG2E)).to(torch.bfloat16)          # the kernels' contract: one bf16 rounding of q * scale * log2 e
+            R = attn_ref64(qs, kd[b, h], vd[b, h], dod[b, h], smul=1.0, dq_mul=64 ** -0.5, dk_mul=attn_tol.LN2, rounded_rowsum=True)
+            problems += attn_tol.judge({"o": ov[b, h], "lse2": lse[b, h], "dq": dq[b, h], "dk": dk[b, h], "dv": dv[b, h]}, R, delta=None, where=f"[S {S} b{b} h{h}]")[0]
+    assert not problems, "\n".join(problems)
 
 
 def test_attention_online_softmax_rescale(ops):

@@ -4,6 +4,9 @@ bf16 outputs: within 2 % of the tensor's range and cosine >= 0.9995 for the outp
 import pytest
 import torch
 
+import attn_tol
+from attn_ref64 import attn_ref64
+
 pytestmark = pytest.mark.gpu
 
 
@@ -44,6 +47,14 @@ def test_attention128_forward_backward_vs_fp64(B, H, Sq, Skv):
     _close(qg.grad, rq, "dq")
     _close(kg.grad, rk, "dk")
     _close(vg.grad, rv, "dv")
+    # per element, inside the derived bounds of tests/attn_tol.py (bf16 weights, fp32 row sum of the unrounded ones, delta from the completed output)
+    problems = []
+    for b in range(B):
+        for h in range(H):
+            R = attn_ref64(q[b, h], k[b, h], v[b, h], do[b, h], smul=scale * attn_tol.LOG2E, dq_mul=scale, dk_mul=scale, rounded_rowsum=False)
+            got = {"o": o[b, h].detach(), "dq": qg.grad[b, h], "dk": kg.grad[b, h], "dv": vg.grad[b, h]}
+            problems += attn_tol.judge(got, R, where=f"[{Sq} x {Skv} b{b} h{h}]")[0]
+    assert not problems, "\n".join(problems)
 
 
 @pytest.mark.parametrize("B,H,Sq,Skv", [(1, 2, 256, 1024), (1, 3, 700, 1500), (2, 2, 1030, 1091), (1, 1, 64, 4096), (1, 2, 1500, 1024), (1, 1, 2048, 130)])

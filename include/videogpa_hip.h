@@ -108,28 +108,26 @@ int32_t vgpa_qknorm_rope_bwd(const void* dq_out, const void* dk_out, const void*
 /* ---- 3D full attention, non-causal, head_dim 64 (F.scaled_dot_product_attention in the same processor) ----------
  * CONTRACT: q is PRE-MULTIPLIED by scale*log2(e) in every entry point below; dq is the gradient w.r.t. the unscaled q.
  * lse2 = log2 sum_k exp2(q.k), fp32 [B,H,S]; delta = rowsum(dO * O), fp32 [B,H,S]. */
-/* The forward.  workspace: NULL (a single launch), or caller-owned with >= vgpa_attn_fwd_workspace_bytes: when the number of
- * (head, 256-row strip) tasks leaves a mostly empty last scheduling round on the device, those leftover tasks are cut into
- * key-range chunks (second small launch + merge) instead.  split_mode: -1 automatic, 0 never, k >= 2 force k chunks for every task. */
-size_t vgpa_attn_fwd_workspace_bytes(int64_t B, int64_t H, int64_t S);
-int32_t vgpa_attn_fwd_ws(const void* q, const void* k, const void* v, void* o, float* lse2, const int64_t* q_strides,
-                         const int64_t* k_strides, const int64_t* v_strides, const int64_t* o_strides, int64_t B, int64_t H,
-                         int64_t S, int64_t head_dim, float scale, int32_t split_mode, void* workspace, size_t ws_bytes,
-                         vgpa_stream_t stream);
+/* All tensors are bf16 views [B,H,S,64] given by ELEMENT strides {batch, head, token} (last dim contiguous, strides multiples of 8, base
+ * pointers 16-byte aligned); `scale` is the softmax scale (dQ / dK multipliers).  The kernels are the "w1" structure of attention_w1.hip: one wave
+ * per SIMD, 512-register waves, LDS-DMA ring, hand-scheduled main loops.
+ * split_mode, in every call that takes one: when the number of (head, 256-row strip) tasks leaves a mostly empty last scheduling round on the
+ * device, those leftover tasks are cut into chunks along the streamed axis (second small launch + fp32 merge) instead, the partial results going
+ * through the caller-owned workspace.  -1 automatic, 0 never, k >= 2 force k chunks for every task (a short workspace is then VGPA_ERR_WORKSPACE). */
 /* Backward, step 1: delta = rowsum(dO o O), of the output as the forward's residual tensor completes it (o_res / res_kind as
  * vgpa_attn_fwd_w1_res wrote them; o_res may be NULL: from o alone).  delta stands for rowsum(P o dP), which equals rowsum(dO o O) for the UNROUNDED O only; from the bf16 O alone (what flash-attention
  * backwards, torch's included, do) every row's dS stops summing to zero and dQ picks up a coherent error. */
 int32_t vgpa_attn_bwd_delta_res(const void* o, const void* o_res, int32_t res_kind, const void* d_o, const int64_t* o_strides, const int64_t* ores_strides,
                                 const int64_t* do_strides, float* delta, int64_t B, int64_t H, int64_t S, int64_t head_dim,
                                 vgpa_stream_t stream);
-/* dQ on the "w1" structure (attention_w1.hip: one wave per SIMD, 512-register waves, LDS-DMA ring, hand-scheduled main
- * loop); arguments and results as vgpa_attn_bwd_dq_ws (workspace >= vgpa_attn_bwd_split_workspace_bytes, may be NULL). */
+/* Backward, step 3: dQ from lse2 / delta.  workspace: NULL (a single launch), or caller-owned with >= vgpa_attn_bwd_split_workspace_bytes (it may
+ * be the one vgpa_attn_bwd_dkv_w1 used: the two calls run one after the other on a stream). */
+size_t vgpa_attn_bwd_split_workspace_bytes(int64_t B, int64_t H, int64_t S);
 int32_t vgpa_attn_bwd_dq_w1(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
                             void* dq, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
                             const int64_t* do_strides, const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim,
                             float scale, int32_t split_mode, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
-/* Forward on the "w1" structure (attention_w1.hip); arguments and results as vgpa_attn_fwd_ws, the workspace
- * (>= vgpa_attn_fwd_w1_workspace_bytes) is required.  Scores are shifted per row by M' = min(b, m_s + 64), b = the bound |q| max|k|, m_s = the row's maximum
+/* The forward: o = softmax(q k^T) v and lse2.  The workspace (>= vgpa_attn_fwd_w1_workspace_bytes) is required.  Scores are shifted per row by M' = min(b, m_s + 64), b = the bound |q| max|k|, m_s = the row's maximum
  * over 64 keys spread evenly over the sequence, instead of a running maximum; 256-row strips whose sum overflows or comes too close to underflow (a row whose true
  * maximum lies > ~176 log2 units above the sampled one) are redone by the online-softmax kernel in the same call.  lse2 is formed from the sum of the bf16-ROUNDED
  * weights (the ones the PV product multiplies: O is an exact convex combination of V rows); it differs from the exact value by a row's weighted mean rounding error
@@ -156,7 +154,8 @@ int32_t vgpa_attn_fwd_online_res(const void* q, const void* k, const void* v, vo
                                  int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode, void* workspace,
                                  size_t ws_bytes, vgpa_stream_t stream);
 /* w1 backward, step 1 and step 2: vgpa_attn_bwd_prep_w1_res writes delta (fp32 [B,H,S], as vgpa_attn_bwd_delta_res; o_res may be NULL) and the
- * statistics planes stats = fp32 [B,H,2,S] = {-lse2, -delta}; vgpa_attn_bwd_dkv_w1 = vgpa_attn_bwd_dkv_ws on the w1 structure, reading `stats`. */
+ * statistics planes stats = fp32 [B,H,2,S] = {-lse2, -delta}; vgpa_attn_bwd_dkv_w1 writes dK, dV from `stats`; its workspace as in
+ * vgpa_attn_bwd_dq_w1 (NULL: a single launch). */
 int32_t vgpa_attn_bwd_prep_w1_res(const void* o, const void* o_res, int32_t res_kind, const void* d_o, const float* lse2, const int64_t* o_strides,
                                   const int64_t* ores_strides, const int64_t* do_strides, float* delta, float* stats, int64_t B, int64_t H,
                                   int64_t S, int64_t head_dim, vgpa_stream_t stream);
@@ -164,27 +163,6 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
                              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
                              const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim,
                              float scale, int32_t split_mode, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
-/* Backward, step 2 (dK, dV from lse2 / delta) and step 3 (dQ).  workspace: NULL (a single launch each), or caller-owned with
- * >= vgpa_attn_bwd_split_workspace_bytes (may be shared by the two calls): the leftover tasks of a mostly empty last scheduling round are cut into chunks along the streamed axis (second
- * small launch + fp32 merge), as in vgpa_attn_fwd_ws.  split_mode: -1 automatic, 0 never, k >= 2 force k chunks. */
-size_t vgpa_attn_bwd_split_workspace_bytes(int64_t B, int64_t H, int64_t S);
-int32_t vgpa_attn_bwd_dkv_ws(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
-                             void* dk, void* dv, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                             const int64_t* do_strides, const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H,
-                             int64_t S, int64_t head_dim, float scale, int32_t split_mode, void* workspace, size_t ws_bytes,
-                             vgpa_stream_t stream);
-int32_t vgpa_attn_bwd_dq_ws(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
-                            void* dq, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
-                            const int64_t* do_strides, const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim,
-                            float scale, int32_t split_mode, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
-#ifdef VGPA_VARIANTS /* measured-slower experiment (one-kernel backward, dQ by fp32 atomics): exported by variant builds only
-                      * (tools/build_variant.sh); dq_f32 = fp32 [B,H,S,64] contiguous, zeroed by the caller */
-int32_t vgpa_attn_bwd_fused(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta,
-                            float* dq_f32, void* dk, void* dv, const int64_t* q_strides, const int64_t* k_strides,
-                            const int64_t* v_strides, const int64_t* do_strides, const int64_t* dk_strides,
-                            const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
-                            vgpa_stream_t stream);
-#endif
 
 /* ---- LoRA A.B contractions (peft Linear.forward `lora_B(lora_A(x)) * scaling` and its backward for the adapters of
  * train/CogVideoX-5B/03_train.py:102-106).  bf16 row-major operands with explicit row strides (elements).

@@ -58,6 +58,11 @@ def test_pure_host_queries():
     assert _lib.query("vgpa_attn128_fwd_workspace_bytes", 2, 24, 18480) == 4 * 2 * 24 + 4 * 2 * 24 * 73
     assert _lib.query("vgpa_attn128_fwd_workspace_bytes", 0, 24, -1) == 0
     assert _lib.query("vgpa_grad_norm_workspace_bytes") == 1024 * 8
+    # the split backward at the headline shape (2 x 48 heads, 17 776 tokens -> 70 tasks of 256 rows per head): the (task, chunk) pairs saturate at one per
+    # compute unit (256, also the fallback without a device), each with the dK/dV part = 2 x [256 x 64] fp32
+    assert _lib.query("vgpa_attn_bwd_split_workspace_bytes", 2, 48, 17776) == 256 * (2 * 256 * 64 * 4)
+    assert _lib.query("vgpa_attn_bwd_split_workspace_bytes", 0, 48, 17776) == 0
+    assert _lib.query("vgpa_attn_bwd_split_workspace_bytes", 2, 48, -1) == 0
 
 
 def test_ops_fail_loudly_without_gpu():

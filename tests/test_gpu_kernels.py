@@ -331,31 +331,6 @@ def test_linear_lora_function_vs_torch(ops):
     assert Ad[1].grad is None and Bd[1].grad is None
 
 
-def test_attention_bwd_fused_variant_matches_split(ops):
-    """The optional one-kernel backward (dQ through fp32 atomics) against the default split kernels.  The kernel is a measured-slower
-    experiment and lives in variant builds only (tools/build_variant.sh, VGPA_LIB=...): skipped on the product library."""
-    from videogpa_amd import _lib
-    if not _lib.has("vgpa_attn_bwd_fused"):
-        pytest.skip("variant build only")
-    g = torch.Generator().manual_seed(123)
-    B, H, S = 1, 2, 700
-    q, k, v, do = (torch.randn(B, H, S, 64, generator=g).to(torch.bfloat16).cuda() for _ in range(4))
-    o, lse = ops.attention_fwd_raw(q, k, v)
-    ov = o.view(B, S, H, 64).permute(0, 2, 1, 3)
-    res = {}
-    old = ops.ATTN_BWD_FUSED
-    try:
-        for fused in (False, True):
-            ops.ATTN_BWD_FUSED = fused
-            dq, dk, dv = (torch.empty(B, H, S, 64, dtype=torch.bfloat16, device="cuda") for _ in range(3))
-            ops.attention_bwd_raw(q, k, v, ov, do, lse, dq, dk, dv)
-            res[fused] = (dq.float(), dk.float(), dv.float())
-    finally:
-        ops.ATTN_BWD_FUSED = old
-    for a, b, name in zip(res[False], res[True], ("dq", "dk", "dv")):
-        assert (a - b).abs().max().item() <= 0.02 * a.abs().max().item() + 1e-3, name
-
-
 # ------------------------------------------------------------------------------------------ edge cases / error codes
 @pytest.mark.parametrize("S", [1, 7, 63, 64, 65, 129])
 def test_attention_tiny_and_boundary_lengths(ops, S):
@@ -449,7 +424,7 @@ def test_attention_row_between_overflow_of_o_and_overflow_of_l(ops, S, gap, spli
 
 @pytest.mark.parametrize("S,split", [(1000, 4), (1000, 8), (2100, 3), (641, 5)])
 def test_attention_fwd_key_range_split_matches_single_launch(ops, S, split):
-    """The launcher's tail treatment (tasks cut into key-range chunks + merge, vgpa_attn_fwd_ws) against the single launch
+    """The launcher's tail treatment (tasks cut into key-range chunks + merge, vgpa_attn_fwd_w1_res) against the single launch
     and the fp64 reference, incl. a spiked key in a late chunk and a ragged last tile."""
     g = torch.Generator().manual_seed(S + split)
     B, H = 1, 3
@@ -465,12 +440,13 @@ def test_attention_fwd_key_range_split_matches_single_launch(ops, S, split):
     assert ((lse1 - lse0).abs().double().cpu() <= 2.0 * tol + 1e-3).all()      # each launch rounds its own weights (every chunk of a row shifts by the same sampled M')
 
 
-@pytest.mark.parametrize("S,split", [(1000, 4), (1100, 7), (641, 3)])
-def test_attention_bwd_range_split_matches_single_launch(ops, S, split):
+@pytest.mark.parametrize("B,H,S,split", [(1, 2, 1000, 4), (1, 2, 1100, 7), (1, 2, 641, 3), (1, 2, 513, 4), (2, 3, 769, 6)],
+                         ids=["1000-4", "1100-7", "641-3", "513-4", "769-6"])
+def test_attention_bwd_range_split_matches_single_launch(ops, B, H, S, split):
     """dK/dV split along the query tiles and dQ split along the key tiles (fp32 partials + merge) against the single launches
-    and the fp64 reference."""
+    and the fp64 reference.  S = 513 and 769 are one row past a multiple of the 256-row task, where vgpa_attn_bwd_split_workspace_bytes is
+    tightest against what a forced split needs (a short workspace would be VGPA_ERR_WORKSPACE, raised by the call)."""
     g = torch.Generator().manual_seed(S * split)
-    B, H = 1, 2
     q, k, v, do = (torch.randn(B, H, S, 64, generator=g).to(torch.bfloat16) for _ in range(4))
     qd, kd, vd, dod = dev(q), dev(k), dev(v), dev(do)
     o, lse = ops.attention_fwd_raw(qd, kd, vd, split_mode=0)
@@ -497,9 +473,16 @@ def test_cabi_rejects_bad_arguments(ops):
     import ctypes
     s3 = (ctypes.c_int64 * 3)(64, 64, 64)
     f = torch.zeros(8, dtype=torch.float32, device="cuda")
-    assert lib.vgpa_attn_fwd_ws(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), f.data_ptr(), s3, s3, s3, s3, 1, 1, 1, 128, 0.1, 0, None, 0, st) == -1   # head_dim
+    wb = lib.vgpa_attn_fwd_w1_workspace_bytes(1, 1, 1)
+    aws = torch.zeros(wb, dtype=torch.uint8, device="cuda")
+
+    def fwd(strides, head_dim, wsp):
+        return lib.vgpa_attn_fwd_w1_res(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), None, 0, f.data_ptr(), strides, s3, s3, s3, None, 1, 1, 1, head_dim, 0.1, 0,
+                                        wsp, wb, st)
+    assert fwd(s3, 128, aws.data_ptr()) == -1                                          # head_dim
     bad = (ctypes.c_int64 * 3)(64, 64, 60)
-    assert lib.vgpa_attn_fwd_ws(x.data_ptr(), x.data_ptr(), x.data_ptr(), x.data_ptr(), f.data_ptr(), bad, s3, s3, s3, 1, 1, 1, 64, 0.1, 0, None, 0, st) == -1   # stride
+    assert fwd(bad, 64, aws.data_ptr()) == -1                                          # stride
+    assert fwd(s3, 64, None) == -1                                                     # the workspace is mandatory
     ws = torch.zeros(16, dtype=torch.uint8, device="cuda")
     assert lib.vgpa_dpo_loss_fwd(*([x.data_ptr()] * 6), 1, 64, 64, 64, 64, 1, 1.0, 0.0, 0, 0, f.data_ptr(), f.data_ptr(), None, ws.data_ptr(), 16, st) == -3
     with pytest.raises(ValueError, match="Unknown loss type"):

@@ -49,7 +49,7 @@ for _ in range(a.iters):
         ops.attention_bwd_raw(q, k, v, ov, dov, lse, dq, dk, dv, split_mode=a.split)
 torch.cuda.synchronize()
 unit = 2.0 * S * S * 64 * B * H
-hw_units = {"attn_fwd_kernel": 2, "attn_bwd_dkv_kernel": 4, "attn_bwd_dq_kernel": 3, "attn_bwd_fused_kernel": 5}
+hw_units = {"attn_fwd_kernel": 2, "attn_bwd_dkv_kernel": 4, "attn_bwd_dq_kernel": 3}
 for name, s in ops.TIMER.summary().items():
     if name not in hw_units:          # HBM-bound helpers (attn_delta_kernel): bytes, not FLOPs
         print(f"{name:22s} avg {s['avg_ms']:8.3f} ms  {s['work_per_launch'] / s['avg_ms'] / 1e6:7.1f} GB/s")
@@ -62,7 +62,6 @@ if a.energy > 0:
     import time
     from energy import read_joules
     from videogpa_amd import _lib
-    w1 = set(ops.ATTN_W1)
     scale = 64 ** -0.5
     qs = ops.prescale_q(q, scale)
     delta = torch.empty(B, H, S, dtype=torch.float32, device="cuda")
@@ -79,12 +78,10 @@ if a.energy > 0:
         x.fill_(0.0 if a.data == "zeros" else 0.125)
     launches = {
         "attn_fwd": (4.0, lambda: ops.attention_fwd_raw(q, k, v, split_mode=a.split)),
-        "attn_bwd_dkv": (6.0, (lambda: _lib.call("vgpa_attn_bwd_dkv_w1", qs, k, v, dov, stats, dk, dv, sb(qs), sb(k), sb(v), sb(dov), sb(dk), sb(dv), B, H, S, 64, scale,
-                                                   a.split, wsp, ws_bytes, st)) if "dkv" in w1 else
-                         (lambda: _lib.call("vgpa_attn_bwd_dkv_ws", qs, k, v, dov, lse, delta, dk, dv, sb(qs), sb(k), sb(v), sb(dov), sb(dk), sb(dv), B, H, S, 64, scale,
-                                            a.split, wsp, ws_bytes, st))),
-        "attn_bwd_dq": (2.0, lambda: _lib.call("vgpa_attn_bwd_dq_w1" if "dq" in w1 else "vgpa_attn_bwd_dq_ws", qs, k, v, dov, lse, delta, dq, sb(qs), sb(k), sb(v),
-                                                 sb(dov), sb(dq), B, H, S, 64, scale, a.split, wsp, ws_bytes, st)),
+        "attn_bwd_dkv": (6.0, lambda: _lib.call("vgpa_attn_bwd_dkv_w1", qs, k, v, dov, stats, dk, dv, sb(qs), sb(k), sb(v), sb(dov), sb(dk), sb(dv), B, H, S, 64, scale,
+                                                  a.split, wsp, ws_bytes, st)),
+        "attn_bwd_dq": (2.0, lambda: _lib.call("vgpa_attn_bwd_dq_w1", qs, k, v, dov, lse, delta, dq, sb(qs), sb(k), sb(v), sb(dov), sb(dq), B, H, S, 64, scale,
+                                                 a.split, wsp, ws_bytes, st)),
         "hipblaslt FF1 gemm": (None, lambda: torch.matmul(x, wt.t())),
     }
     idle0 = read_joules()

@@ -38,9 +38,8 @@ for stats in (f"{root}/{tag}_attn_kernel_stats.csv", f"{root}/{tag}_attn128_kern
     except OSError as e:
         print("no attention kernel stats:", e)
 # the full-round launches carry the bench names; tail-split (<true>) launches, merges and the redo pass keep their own
-alias = {"attn_fwd_pipe_kernel<2, 4, false>": "attn_fwd_kernel (online-softmax form)", "attn_fwd_w1_kernel<false>": "attn_fwd_kernel",
+alias = {"attn_fwd_pipe_kernel": "attn_fwd_kernel (online-softmax form)", "attn_fwd_w1_kernel<false>": "attn_fwd_kernel",
          "attn_bwd_dkv_w1_kernel<false>": "attn_bwd_dkv_kernel", "attn_bwd_dq_w1_kernel<false>": "attn_bwd_dq_kernel",
-         "attn_bwd_dkv_kernel<false>": "attn_bwd_dkv_kernel (2 waves per SIMD)", "attn_bwd_dq_kernel<2, false>": "attn_bwd_dq_kernel (2 waves per SIMD)",
          "w1_bwd_prep_kernel": "attn_delta_kernel", "attn128_fwd_w1_kernel": "attn128_fwd"}
 out = {}
 for k, cs in acc.items():
@@ -63,7 +62,7 @@ for k, cs in acc.items():
     out[alias.get(k, k)] = e
 # bench.py times the head_dim-128 backward as ONE entry (delta + dK/dV + dQ launches of vgpa_attn128_bwd): bytes add up, occupancy and clock are
 # duration-weighted means of the two matrix kernels
-dq_name = "attn128_dq_w1x2_kernel" if "attn128_dq_w1x2_kernel" in out else "attn128_dq_w1_kernel"      # two q-blocks per wave since round 4
+dq_name = "attn128_dq_w1x2_kernel"
 parts = [out[k] for k in ("attn128_dkv_w1_kernel", dq_name) if k in out]
 if len(parts) == 2:
     e = {"hbm_bytes_per_launch": sum(p["hbm_bytes_per_launch"] for p in parts) + out.get("attn128_delta_kernel", {}).get("hbm_bytes_per_launch", 0.0),

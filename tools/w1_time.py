@@ -1,5 +1,5 @@
-"""Time one attention kernel family at the headline shape with whatever library VGPA_LIB selects (timing only).
-    VGPA_LIB=var/lib_w1_X.so python tools/w1_time.py --which dq [--iters 5]"""
+"""Time the three head_dim-64 attention kernels at the headline shape with whatever library VGPA_LIB selects (timing only).
+    VGPA_LIB=var/lib_w1_X.so python tools/w1_time.py [--iters 5]"""
 import argparse
 import os
 import sys
@@ -10,7 +10,6 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from videogpa_amd import ops  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--which", default="dq")
 ap.add_argument("--iters", type=int, default=5)
 ap.add_argument("--tag", default="")
 a = ap.parse_args()
@@ -22,7 +21,6 @@ k = qkv[:, :, 1].permute(0, 2, 1, 3).contiguous()
 v = qkv[:, :, 2].permute(0, 2, 1, 3)
 do = torch.randn(B, S, H * 64, generator=g, device="cuda").to(torch.bfloat16)
 dov = do.view(B, S, H, 64).permute(0, 2, 1, 3)
-ops.ATTN_W1 = set(a.which.split(","))
 o, lse = ops.attention_fwd_raw(q, k, v)
 ov = o.view(B, S, H, 64).permute(0, 2, 1, 3)
 dq, dk = torch.empty_like(q), torch.empty_like(k)
@@ -31,10 +29,8 @@ ops.attention_bwd_raw(q, k, v, ov, dov, lse, dq, dk, dv)
 torch.cuda.synchronize()
 ops.TIMER = ops.KernelTimer()
 for _ in range(a.iters):
-    if "fwd" in a.which:
-        ops.attention_fwd_raw(q, k, v)
-    if "dq" in a.which or "dkv" in a.which:
-        ops.attention_bwd_raw(q, k, v, ov, dov, lse, dq, dk, dv)
+    ops.attention_fwd_raw(q, k, v)
+    ops.attention_bwd_raw(q, k, v, ov, dov, lse, dq, dk, dv)
 torch.cuda.synchronize()
 tag = a.tag or os.path.basename(os.environ.get("VGPA_LIB", "product"))
 for name, s in ops.TIMER.summary().items():

@@ -33,8 +33,6 @@ SIGNATURES = {
     "vgpa_gelu_tanh_bwd": (I32, [P, P, I64, P, P]),
     "vgpa_qknorm_rope_fwd": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, F32, I32, P]),
     "vgpa_qknorm_rope_bwd": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, I32, P]),
-    "vgpa_attn_fwd_workspace_bytes": (SZ, [I64, I64, I64]),
-    "vgpa_attn_fwd_ws": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_grad_norm_workspace_bytes": (SZ, []),
     "vgpa_grad_norm": (I32, [P, I64, F32, P, P, SZ, P]),
     "vgpa_adamw_step": (I32, [P, P, P, P, I64, F32, F32, F32, F32, F32, I64, F32, F32, P, P]),
@@ -46,8 +44,6 @@ SIGNATURES = {
     "vgpa_attn_fwd_online_res": (I32, [P, P, P, P, P, I32, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_attn_bwd_dkv_w1": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_attn_bwd_split_workspace_bytes": (SZ, [I64, I64, I64]),
-    "vgpa_attn_bwd_dkv_ws": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
-    "vgpa_attn_bwd_dq_ws": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_lora_down": (I32, [P, I64, P, P, I64, I64, I64, I64, P]),
     "vgpa_lora_up_add": (I32, [P, I64, P, I64, P, I64, F32, I64, I64, I64, I32, P]),
     "vgpa_lora_grad_workspace_bytes": (SZ, [I64, I64, I64]),
@@ -103,7 +99,6 @@ SIGNATURES = {
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library
 OPTIONAL_SIGNATURES = {
-    "vgpa_attn_bwd_fused": (I32, [P, P, P, P, P, P, P, P, P, P, P, P, P, P, P, I64, I64, I64, I64, F32, P]),
     "vgpa_gemm_bf16": (I32, [P, I64, P, I64, P, P, I64, P, I64, I32, I32, I32, I32, P]),
 }
 

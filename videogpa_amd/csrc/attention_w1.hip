@@ -1,6 +1,6 @@
 // "w1" attention kernels for gfx950: one wave per SIMD (a 4-wave workgroup owns a CU), the whole 512-entry register file per
-// wave, streamed tiles by LDS-DMA.  Same mathematics, operand conventions and C ABI as attention.hip (see the header there);
-// what changes is the blocking:
+// wave, streamed tiles by LDS-DMA.  Same mathematics and operand conventions as the online-softmax kernel of attention.hip (see the
+// header there); what changes is the blocking:
 //   * __launch_bounds__(256, 1): accumulators and the stationary operand fragments (MFMA-only values) may live in the
 //     accumulator half of the register file, which leaves the 256 architectural VGPRs to a software pipeline that is one
 //     32-row half-tile deep in every stage:   scores(g+1)  ||  exp / multiply / pack (g)  ||  accumulate (g-1),
@@ -13,6 +13,11 @@
 #include <type_traits>
 
 #include "attn_w1.h"
+
+// fp32 partials one (task, chunk) of a split backward task leaves in the workspace: the kernels' SPLIT epilogues, the merge kernels, the
+// launchers' plans and vgpa_attn_bwd_split_workspace_bytes all go by these two
+#define W1_DQ_PART_FLOATS (256 * HD)         // unscaled dQ [256][64]
+#define W1_DKV_PART_FLOATS (2 * 256 * HD)    // unscaled [dK 256 x 64 | dV 256 x 64]
 
 // =====================================================================================================
 // Backward, dQ:  dQ = scale * sum_k dS[q,k] K[k],  dS = P o (dP - delta),  P = exp2(c*s - lse2),  dP = dO V^T
@@ -31,7 +36,7 @@ __device__ __forceinline__ u32x16_t pack4(const bf16x8_t& a, const bf16x8_t& b, 
 }
 
 // SPLIT: workgroup (task0 + blockIdx / nsplit, chunk blockIdx % nsplit) sweeps key tiles [nt*chunk/nsplit, nt*(chunk+1)/nsplit)
-// and leaves its unscaled fp32 dQ [256][64] in `part` (attn_dq_merge_kernel of attention.hip adds the chunks).
+// and leaves its unscaled fp32 dQ [256][64] in `part` (w1_dq_merge_kernel adds the chunks).
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                   const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
@@ -122,7 +127,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
     for (int j = 0; j < QB; ++j) { asm volatile("" : "+v"(dq[j][0])); asm volatile("" : "+v"(dq[j][1])); }
 
     if (SPLIT) {
-        float* pb = part + ((size_t)(vid - task0) * nsplit + chunk) * (128 * QB * HD);
+        float* pb = part + ((size_t)(vid - task0) * nsplit + chunk) * W1_DQ_PART_FLOATS;
 #pragma unroll
         for (int j = 0; j < QB; ++j) {
             const int r = wave * (32 * QB) + 32 * j + (lane & 31);
@@ -167,7 +172,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
 // (vgpa_internal_attn_fwd_redo), so the result never depends on the bound being tight.
 // =====================================================================================================
 #include "w1_fwd_knobs.inc"                   // W1_FWD_MFSUM: what the generated loop expects around it (tools/gen_w1_asm.py W1_KNOBS mfsum; 1 in the product)
-#define W1_FWD_PART_FLOATS (256 * (HD + 2))   // per (task, chunk): O[256][64] (un-normalised), M[256], l[256] -- layout of attention.hip's split forward
+#define W1_FWD_PART_FLOATS (256 * (HD + 2))   // per (task, chunk) of a split forward task: O[256][64] (un-normalised), M[256], l[256]
 #define W1_L_MIN 7.8886e-31f                  // 2^-100: below this the row's sum is too close to underflow -> redo
 // ... and above 2^118 too close to overflow: the O accumulators carry sum_j p_j v_j <= l max|v| (a row whose true maximum lies 112-128 above the shift has a FINITE
 // l next to O = +-inf, and 1 / l flushes to zero from 2^126 on).  Found by `bench.py --weights trained_like` (one row of block 38, true maximum 127.7 above M':
@@ -546,7 +551,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* _
         for (int db = 0; db < 2; ++db) { asm volatile("" : "+v"(dk[j][db])); asm volatile("" : "+v"(dv[j][db])); }
 
     if (SPLIT) {   // unscaled fp32 partials: [dK 256 x 64 | dV 256 x 64] per (task, chunk)
-        float* pb = part + ((size_t)(vid - task0) * nsplit + chunk) * (2 * 256 * HD);
+        float* pb = part + ((size_t)(vid - task0) * nsplit + chunk) * W1_DKV_PART_FLOATS;
 #pragma unroll
         for (int j = 0; j < KB; ++j) {
             const int r = wave * (32 * KB) + 32 * j + (lane & 31);
@@ -596,11 +601,11 @@ __global__ __launch_bounds__(256) void w1_dkv_merge_kernel(const float* __restri
     const int vid = task0 + tl, bh = vid / n_kt, kt = vid % n_kt;
     const int key = kt * 256 + r;
     if (key >= S) return;
-    const float* pb = part + (size_t)tl * nsplit * (2 * 256 * HD) + r * HD + lane;
+    const float* pb = part + (size_t)tl * nsplit * W1_DKV_PART_FLOATS + r * HD + lane;
     float ak = 0.f, av = 0.f;
     for (int c = 0; c < nsplit; ++c) {
-        ak += pb[(size_t)c * (2 * 256 * HD)];
-        av += pb[(size_t)c * (2 * 256 * HD) + 256 * HD];
+        ak += pb[(size_t)c * W1_DKV_PART_FLOATS];
+        av += pb[(size_t)c * W1_DKV_PART_FLOATS + 256 * HD];
     }
     const int b = bh / H, h = bh % H;
     dK[(size_t)b * sdk.b + (size_t)h * sdk.h + (size_t)key * sdk.s + lane] = f32_to_bf16(ak * kscale);
@@ -670,8 +675,25 @@ static inline int64_t w1_slots() { return wg_slots() / 2; }   // one 256-thread 
 
 extern "C" {
 
-// dQ on the w1 structure; arguments as vgpa_attn_bwd_dq_ws (include/videogpa_hip.h): with a workspace
-// (>= vgpa_attn_bwd_split_workspace_bytes) the tasks of a mostly empty last scheduling round are cut into key-range chunks.
+// All tensors are bf16 views [B, H, S, 64] given by element strides {batch, head, token} (last dim contiguous,
+// strides multiples of 8, base pointers 16-byte aligned).  lse2 / delta are fp32 [B, H, S] contiguous.
+// CONTRACT: q holds the queries PRE-MULTIPLIED by scale*log2(e) (vgpa_qknorm_rope_fwd writes them that way through
+// q_out_scale), in all entry points; `scale` is still the softmax scale (used for the dQ / dK multipliers).
+// dq is the gradient w.r.t. the UNscaled query.
+
+// Workspace of the two split steps of the backward, dK/dV and dQ (shared by the two; they run one after the other on a stream): the partials
+// of the most (task, chunk) pairs a plan can have, in the larger of the two part sizes.
+size_t vgpa_attn_bwd_split_workspace_bytes(int64_t B, int64_t H, int64_t S) {
+    if (B <= 0 || H <= 0 || S <= 0) return 0;
+    const int64_t tasks = (S + 255) / 256 * B * H;
+    const size_t part = W1_DKV_PART_FLOATS > W1_DQ_PART_FLOATS ? W1_DKV_PART_FLOATS : W1_DQ_PART_FLOATS;
+    return (size_t)max_split_parts(tasks, W1_MAX_SPLIT, w1_slots()) * part * sizeof(float);
+}
+
+// dQ (workgroup per 256 queries, sweeping the key tiles).  lse2 = the forward's, delta = vgpa_attn_bwd_prep_w1_res's (fp32 [B,H,S]); dq = the
+// gradient w.r.t. the unscaled query.  workspace: NULL (a single launch), or caller-owned with >= vgpa_attn_bwd_split_workspace_bytes: the
+// tasks of a mostly empty last scheduling round are then cut into key-range chunks (a second small launch + an fp32 merge).
+// split_mode: -1 automatic, 0 never, k >= 2 force k chunks for every task (tests); a forced split with a short workspace is VGPA_ERR_WORKSPACE.
 int32_t vgpa_attn_bwd_dq_w1(const void* q, const void* k, const void* v, const void* d_o, const float* lse2, const float* delta, void* dq,
                             const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
                             const int64_t* dq_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale, int32_t split_mode,
@@ -685,7 +707,7 @@ int32_t vgpa_attn_bwd_dq_w1(const void* q, const void* k, const void* v, const v
     const int64_t tasks = (int64_t)n_t * B * H;
     if (tasks > 0x7fffffff) return VGPA_ERR_INVALID;
     TailSplit p;
-    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), rows * HD * sizeof(float), workspace,
+    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), W1_DQ_PART_FLOATS * sizeof(float), workspace,
                                        ws_bytes, 0, &p);
     if (rc) return rc;
     if (p.n_main > 0) {
@@ -723,7 +745,8 @@ int32_t vgpa_attn_bwd_prep_w1_res(const void* o, const void* o_res, int32_t res_
     return VGPA_OK;
 }
 
-// dK, dV on the w1 structure: arguments as vgpa_attn_bwd_dkv_ws, with `stats` (vgpa_attn_bwd_prep_w1_res) in the place of lse2 / delta
+// dK, dV (workgroup per 256 keys, sweeping the query tiles); `stats` = the statistics planes of vgpa_attn_bwd_prep_w1_res.  workspace and
+// split_mode as in vgpa_attn_bwd_dq_w1 (the chunks are query ranges).
 int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const void* d_o, const float* stats, void* dk, void* dv,
                              const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides, const int64_t* do_strides,
                              const int64_t* dk_strides, const int64_t* dv_strides, int64_t B, int64_t H, int64_t S, int64_t head_dim, float scale,
@@ -739,7 +762,7 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
     if (tasks > 0x7fffffff) return VGPA_ERR_INVALID;
     const float kscale = 0.6931471805599453f;   // q arrives pre-scaled by scale * log2(e): dK = ln 2 * (dS^T Q)
     TailSplit p;
-    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), 2 * 256 * HD * sizeof(float), workspace,
+    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), W1_DKV_PART_FLOATS * sizeof(float), workspace,
                                        ws_bytes, 0, &p);
     if (rc) return rc;
     if (p.n_main > 0) {
@@ -761,8 +784,9 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
 }
 
 
-// Forward on the w1 structure: arguments and results as vgpa_attn_fwd_ws; the workspace (>= vgpa_attn_fwd_w1_workspace_bytes) is REQUIRED:
-// it holds max_k |k|^2 per (batch, head), one redo flag per 256-row strip and the tail-split partials.
+// The forward: o = softmax(q k^T) v (bf16), lse2 = log2 sum_k exp2(q.k) per row (fp32 [B,H,S]).  split_mode as in vgpa_attn_bwd_dq_w1, along the
+// keys.  The workspace (>= vgpa_attn_fwd_w1_workspace_bytes) is REQUIRED: it holds max_k |k|^2 per (batch, head), one redo flag per 256-row
+// strip and the tail-split partials.
 size_t vgpa_attn_fwd_w1_workspace_bytes(int64_t B, int64_t H, int64_t S) {
     const int64_t n_qt = (S + 255) / 256, tasks = n_qt * B * H;
     const size_t head = (((size_t)(B * H) + (size_t)tasks) * 4 + 255) / 256 * 256;

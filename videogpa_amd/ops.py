@@ -917,17 +917,12 @@ def _bhs_strides(t):
 
 
 LOG2E = 1.4426950408889634
-# backward attention: "split" (default) = deterministic dK/dV kernel + dQ kernel (7 matrix products per score block);
-# "fused" = one kernel with dQ by fp32 atomics (5 products).  Measured on MI355X at the headline shape the fused form
-# is SLOWER (46.6 ms vs 26.5 ms per layer): its 60 GB of dQ atomics per launch run at ~2.6 TB/s (23.9 ms without them).
-# It lives in tools/variants/ (variant builds export vgpa_attn_bwd_fused; ops.ATTN_BWD_FUSED = True selects it there).
-ATTN_BWD_FUSED = False        # True needs a variant build (tools/build_variant.sh: vgpa_attn_bwd_fused lives in tools/variants/)
-# tail-round treatment of the attention launches (vgpa_attn_*_ws split_mode): -1 automatic (default), 0 off
+# The attention kernels are the "w1" family (csrc/attention_w1.hip: one wave per SIMD, LDS-DMA rings, generated hand-scheduled main loops); the
+# backward is a deterministic dK/dV kernel + a dQ kernel (7 matrix products per score block).  A one-kernel backward with dQ by fp32 atomics
+# (5 products) measured SLOWER on MI355X at the headline shape (46.6 ms vs 26.5 ms per layer: its 60 GB of dQ atomics per launch run at
+# ~2.6 TB/s, 23.9 ms without them) and is gone.
+# tail-round treatment of the attention launches (split_mode of vgpa_attn_fwd_w1_res / vgpa_attn_bwd_*_w1): -1 automatic (default), 0 off
 ATTN_SPLIT_MODE = -1
-# Attention kernels come from the "w1" family (csrc/attention_w1.hip: one wave per SIMD, LDS-DMA rings, generated hand-scheduled
-# main loops).  ATTN_W1 = subset of {fwd, dq, dkv} selects which (default all three; empty = the 2-waves-per-SIMD kernels of attention.hip,
-# which stay in the library as the online-softmax / redo path of the forward and for A/B runs: tools set ops.ATTN_W1).
-ATTN_W1 = {"fwd", "dq", "dkv"}
 # "Precise delta": the attention forward also stores what the bf16 rounding of its output dropped, and the backward forms delta = rowsum(dO o O) from the
 # completed output.  delta stands for rowsum(P o dP); formed from the bf16 O alone (what every flash-attention backward, torch's included, does) each row's dS
 # stops summing to zero and dQ picks up a coherent error -d(delta_i) sum_j P_ij K_j that swamps q / k gradients which are small by cancellation (37-87 % of
@@ -1012,7 +1007,7 @@ def attention_redo_fraction(ws, B, H, S):
 
 def attention_fwd_raw(q, k, v, scale=None, q_prescaled=False, split_mode=None, o_pad=0, o_res=None, policy=None):
     """q,k,v: bf16 [B,H,S,64] views (any batch/head/token strides).  -> o [B,S,H*64] bf16, lse2 [B,H,S] fp32.
-    o_res: optional [B,S,H*64] buffer, bf16 or uint8, that receives what the output's bf16 rounding dropped (w1 forward only; see "Precise delta").
+    o_res: optional [B,S,H*64] buffer, bf16 or uint8, that receives what the output's bf16 rounding dropped (see "Precise delta").
     split_mode: -1 lets the launcher cut the tasks of a mostly empty last scheduling round into key-range chunks,
     0 forbids it, k >= 2 forces k chunks for every task (tests).  o_pad: o is the head of a [B,S,H*64+o_pad] buffer (the
     output projection's LoRA tail, see LoraExt)."""
@@ -1024,26 +1019,17 @@ def attention_fwd_raw(q, k, v, scale=None, q_prescaled=False, split_mode=None, o
     lse = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
     ov = o.unflatten(-1, (H, Dh)).permute(0, 2, 1, 3)
     split_mode = ATTN_SPLIT_MODE if split_mode is None else split_mode
-    if "fwd" in ATTN_W1:
-        ws_bytes = _lib.query("vgpa_attn_fwd_w1_workspace_bytes", B, H, S)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
-        rv = None if o_res is None else o_res.unflatten(-1, (H, Dh)).permute(0, 2, 1, 3)
-        entry = "vgpa_attn_fwd_online_res" if (policy is not None and policy.mode == "online") else "vgpa_attn_fwd_w1_res"
-        _timed("attn_fwd_kernel", 4.0 * S * S * Dh * B * H, lambda: _lib.call(
-            entry, q, k, v, o, o_res, _res_kind(o_res), lse, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(ov), None if rv is None else _bhs_strides(rv),
-            B, H, S, Dh, float(scale), int(split_mode), ws, ws_bytes, _stream()))
-        if policy is not None:
-            if policy.wants_flags() and not torch.cuda.is_current_stream_capturing():
-                policy.observe(attention_redo_fraction(ws, B, H, S))
-            policy.calls += 1
-        return o, lse
-    if o_res is not None:
-        raise RuntimeError("attention_fwd_raw: o_res needs the w1 forward (ops.ATTN_W1 includes \"fwd\")")
-    ws_bytes = _lib.query("vgpa_attn_fwd_workspace_bytes", B, H, S) if split_mode != 0 else 0
-    ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
+    ws_bytes = _lib.query("vgpa_attn_fwd_w1_workspace_bytes", B, H, S)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=q.device)
+    rv = None if o_res is None else o_res.unflatten(-1, (H, Dh)).permute(0, 2, 1, 3)
+    entry = "vgpa_attn_fwd_online_res" if (policy is not None and policy.mode == "online") else "vgpa_attn_fwd_w1_res"
     _timed("attn_fwd_kernel", 4.0 * S * S * Dh * B * H, lambda: _lib.call(
-        "vgpa_attn_fwd_ws", q, k, v, o, lse, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(ov), B, H, S, Dh,
-        float(scale), int(split_mode), ws if ws_bytes else None, ws_bytes, _stream()))
+        entry, q, k, v, o, o_res, _res_kind(o_res), lse, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(ov), None if rv is None else _bhs_strides(rv),
+        B, H, S, Dh, float(scale), int(split_mode), ws, ws_bytes, _stream()))
+    if policy is not None:
+        if policy.wants_flags() and not torch.cuda.is_current_stream_capturing():
+            policy.observe(attention_redo_fraction(ws, B, H, S))
+        policy.calls += 1
     return o, lse
 
 
@@ -1058,37 +1044,19 @@ def attention_bwd_raw(q, k, v, o, do, lse, dq, dk, dv, scale=None, q_prescaled=F
         q = prescale_q(q, scale)
     delta = torch.empty(B, H, S, dtype=torch.float32, device=q.device)
     st = _stream()
-    w1_dkv = "dkv" in ATTN_W1 and not ATTN_BWD_FUSED
-    if w1_dkv:     # one pass: delta + the {-lse2, -delta} planes the w1 dK/dV kernel streams
-        stats = torch.empty(B, H, 2, S, dtype=torch.float32, device=q.device)
-        _timed("attn_delta_kernel", (4.0 + (0 if o_res is None else o_res.element_size())) * B * H * S * Dh, lambda: _lib.call(
-            "vgpa_attn_bwd_prep_w1_res", o, o_res, _res_kind(o_res), do, lse, _bhs_strides(o), None if o_res is None else _bhs_strides(o_res), _bhs_strides(do),
-            delta, stats, B, H, S, Dh, st), "byte")
-    else:
-        _timed("attn_delta_kernel", (4.0 + (0 if o_res is None else o_res.element_size())) * B * H * S * Dh, lambda: _lib.call(
-            "vgpa_attn_bwd_delta_res", o, o_res, _res_kind(o_res), do, _bhs_strides(o), None if o_res is None else _bhs_strides(o_res), _bhs_strides(do), delta,
-            B, H, S, Dh, st), "byte")
-    if ATTN_BWD_FUSED:
-        dq32 = torch.zeros(B, H, S, Dh, dtype=torch.float32, device=q.device)
-        _timed("attn_bwd_fused_kernel", 8.0 * S * S * Dh * B * H, lambda: _lib.call(
-            "vgpa_attn_bwd_fused", q, k, v, do, lse, delta, dq32, dk, dv, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(do),
-            _bhs_strides(dk), _bhs_strides(dv), B, H, S, Dh, float(scale), st))
-        dq.copy_(dq32)
-        return
+    stats = torch.empty(B, H, 2, S, dtype=torch.float32, device=q.device)     # the {-lse2, -delta} planes the dK/dV kernel streams
+    _timed("attn_delta_kernel", (4.0 + (0 if o_res is None else o_res.element_size())) * B * H * S * Dh, lambda: _lib.call(
+        "vgpa_attn_bwd_prep_w1_res", o, o_res, _res_kind(o_res), do, lse, _bhs_strides(o), None if o_res is None else _bhs_strides(o_res), _bhs_strides(do),
+        delta, stats, B, H, S, Dh, st), "byte")
     split_mode = ATTN_SPLIT_MODE if split_mode is None else split_mode
     ws_bytes = _lib.query("vgpa_attn_bwd_split_workspace_bytes", B, H, S) if split_mode != 0 else 0
     ws = torch.empty(max(ws_bytes, 16), dtype=torch.uint8, device=q.device)
     wsp = ws if ws_bytes else None
-    if w1_dkv:
-        _timed("attn_bwd_dkv_kernel", 6.0 * S * S * Dh * B * H, lambda: _lib.call(
-            "vgpa_attn_bwd_dkv_w1", q, k, v, do, stats, dk, dv, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(do),
-            _bhs_strides(dk), _bhs_strides(dv), B, H, S, Dh, float(scale), int(split_mode), wsp, ws_bytes, st))
-    else:
-        _timed("attn_bwd_dkv_kernel", 6.0 * S * S * Dh * B * H, lambda: _lib.call(
-            "vgpa_attn_bwd_dkv_ws", q, k, v, do, lse, delta, dk, dv, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(do),
-            _bhs_strides(dk), _bhs_strides(dv), B, H, S, Dh, float(scale), int(split_mode), wsp, ws_bytes, st))
+    _timed("attn_bwd_dkv_kernel", 6.0 * S * S * Dh * B * H, lambda: _lib.call(
+        "vgpa_attn_bwd_dkv_w1", q, k, v, do, stats, dk, dv, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(do),
+        _bhs_strides(dk), _bhs_strides(dv), B, H, S, Dh, float(scale), int(split_mode), wsp, ws_bytes, st))
     _timed("attn_bwd_dq_kernel", 2.0 * S * S * Dh * B * H, lambda: _lib.call(
-        "vgpa_attn_bwd_dq_w1" if "dq" in ATTN_W1 else "vgpa_attn_bwd_dq_ws", q, k, v, do, lse, delta, dq, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(do),
+        "vgpa_attn_bwd_dq_w1", q, k, v, do, lse, delta, dq, _bhs_strides(q), _bhs_strides(k), _bhs_strides(v), _bhs_strides(do),
         _bhs_strides(dq), B, H, S, Dh, float(scale), int(split_mode), wsp, ws_bytes, st))
 
 
@@ -1267,7 +1235,7 @@ class _QKNormAttentionFn(torch.autograd.Function):
         # what the output's bf16 rounding drops, for the backward's delta -- only where a backward will run and on the w1 forward; lean activations keep it too
         # (1 byte per output element next to the 6 that recompute_qk gives back)
         o_res = None
-        if precise_delta and "fwd" in ATTN_W1 and ctx.needs_input_grad[0]:
+        if precise_delta and ctx.needs_input_grad[0]:
             o_res = torch.empty(B, S, H * Dh, dtype=torch.uint8 if precise_delta == "int8" else torch.bfloat16, device=qkv.device)
         o, lse = attention_fwd_raw(qn, kn, v, q_prescaled=True, o_pad=o_pad, o_res=o_res, policy=fwd_policy)
         if recompute_qk:

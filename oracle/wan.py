@@ -165,7 +165,7 @@ class _F8Attn(torch.autograd.Function):
         kmax = k8.pow(2).sum(-1).amax(dim=-1, keepdim=True).sqrt().unsqueeze(-1)
         M = qn * kmax * 1.0009765625
         Lk = s.shape[-1]
-        if Lk >= 128:                                                            # W1H_SAMPLE_KEYS = 64, W1H_SAMPLE_UP = 64 (csrc/attention_hd128.hip)
+        if Lk >= 128:                                                            # W1_SAMPLE_KEYS = 64, W1_SAMPLE_UP = 64 (csrc/attn_w1.h)
             ms = s[..., torch.arange(64, device=s.device) * (Lk // 64)].amax(dim=-1, keepdim=True)
             M = M - torch.floor(torch.clamp(M - (ms + 64.0), min=0.0))
         p = torch.exp2(s - M)

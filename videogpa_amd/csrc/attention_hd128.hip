@@ -19,12 +19,6 @@
 #define P128 136
 #define T128 (64 * P128)   // elements of one [64 x 128] LDS tile
 
-// consecutive workgroup ids go round-robin over the 8 XCDs: give every XCD a contiguous range of tasks (its L2 then sees one (b, h) at a time)
-__device__ __forceinline__ int xcd_remap128(int bid, int nblocks) {
-    const int q = nblocks >> 3, r = nblocks & 7, xcd = bid & 7, j = bid >> 3;
-    return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + j;
-}
-
 __device__ __forceinline__ rsrc_t rsrc128(const bf16_t* base /* uniform */, uint32_t row_stride, int S) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<bf16_t*>(base), 0, ((uint32_t)(S - 1) * row_stride + (uint32_t)D128) * 2u, 0x00020000);
 }
@@ -207,59 +201,19 @@ __global__ __launch_bounds__(256, 2) void attn128_fwd_kernel(const bf16_t* __res
 // The forward on the one-wave-per-SIMD structure of attention_w1.hip at head_dim 128: 4 waves x 2 q-blocks
 // = 256 query rows per workgroup, K/V tiles [64 x 128] by LDS-DMA into a 4-slot ring of 32 KiB slots, main loop from
 // tools/gen_w1_asm.py::Fwd128Loop (w1_fwd128_loop.inc: pipeline, LDS image and register map in its docstring).  Softmax shift = the
-// row bound M[q] = c |q| max|k| (attn128_kmax_kernel), strips that underflow / overflow / are not finite are flagged and redone by
+// row bound M[q] = c |q| max|k| (w1_kmax_kernel), strips that underflow / overflow / are not finite are flagged and redone by
 // attn128_fwd_kernel.
 #include "attn_w1.h"
 
 #include <cstdlib>
 
-typedef __attribute__((ext_vector_type(16))) uint32_t u32x16_t;
-typedef __attribute__((ext_vector_type(8))) uint32_t u32x8_t;
-#define W1H_TILE_BYTES 16384
-#define W1H_SLOT_BYTES 32768
-#define W1H_RING_BYTES (4 * W1H_SLOT_BYTES)
-#define W1H_L_MIN 7.888609052210118e-31f   // 2^-100
-#define W1H_L_MAX 3.3230699e35f            // 2^118: as W1_L_MAX (attention_w1.hip) -- a finite row sum next to overflowed O accumulators must flag the strip too
-#define W1H_M_MAX 1024.0f      // as W1_M_MAX (attention_w1.hip): the fp32 accumulator's ulp at |M'| = 1024 is a fiftieth of the weight's bf16 rounding
-#define W1H_SAMPLE_KEYS 64     // as W1_SAMPLE_KEYS / W1_SAMPLE_UP (attention_w1.hip): the shift follows a sampled lower bound of the row maximum
-#define W1H_SAMPLE_UP 64.0f
-
-__device__ __forceinline__ uint32_t w1h_swz(uint32_t r) { return ((r & 3u) << 2) | ((r >> 2) & 3u); }
-
-__global__ __launch_bounds__(256) void attn128_kmax_kernel(const bf16_t* __restrict__ K, TStride sk, int S, int H, unsigned* __restrict__ kmax2) {
-    const int bh = blockIdx.y, b = bh / H, h = bh % H;
-    const bf16_t* Kb = K + ((size_t)b * sk.b + (size_t)h * sk.h);
-    float mx = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)S * 16; i += (int64_t)gridDim.x * 256) {   // 16 lanes per row
-        const int row = (int)(i >> 4), c16 = (int)(i & 15);
-        float f[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(Kb + ((size_t)row * sk.s + c16 * 8)), f);
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a += f[j] * f[j];
-        a += __shfl_xor(a, 1, 64);
-        a += __shfl_xor(a, 2, 64);
-        a += __shfl_xor(a, 4, 64);
-        a += __shfl_xor(a, 8, 64);
-        mx = fmaxf(mx, a);
-    }
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) atomicMax(kmax2 + bh, __float_as_uint(mx));
-}
-
-__device__ __forceinline__ u32x16_t pack4h(const bf16x8_t& a, const bf16x8_t& b, const bf16x8_t& c, const bf16x8_t& d) {
-    const u32x4_t w[4] = {__builtin_bit_cast(u32x4_t, a), __builtin_bit_cast(u32x4_t, b), __builtin_bit_cast(u32x4_t, c), __builtin_bit_cast(u32x4_t, d)};
-    u32x16_t r;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) r[i] = w[i >> 2][i & 3];
-    return r;
-}
+typedef W1Tile<D128> W1H;   // the [64 x 128] tile geometry: 16-KiB tiles, 32-KiB slots, four pieces per wave
 
 __global__ __launch_bounds__(256, 1) void attn128_fwd_w1_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                                   bf16_t* __restrict__ O, float* __restrict__ LSE2, const unsigned* __restrict__ KMAX2,
                                                                   int* __restrict__ flags, TStride sq, TStride sk, TStride sv, TStride so, int Sq, int Skv,
                                                                   int H, int n_qt, float c, uint8_t* __restrict__ ORES, TStride sor) {
-    __shared__ __attribute__((aligned(1024))) uint8_t lds[W1H_RING_BYTES];   // slot = [K tile | V tile]
+    __shared__ __attribute__((aligned(1024))) uint8_t lds[W1H::RING_BYTES];   // slot = [K tile | V tile]
     const int vid = blockIdx.x;
     const int bh = vid / n_qt, qt = vid % n_qt;
     const int b = bh / H, h = bh % H;
@@ -286,87 +240,33 @@ __global__ __launch_bounds__(256, 1) void attn128_fwd_w1_kernel(const bf16_t* __
         a += other_half(a);
         nmc[j] = sqrtf(a) * kmax * 1.0009765625f;                          // b[q] = |q| max|k| (unscaled: the loop multiplies by c)
     }
-    if (Skv >= 2 * W1H_SAMPLE_KEYS) {   // M'[q] = min(b, m_s + 64 log2 units), m_s = the row's maximum over 64 keys spread over the sweep (attention_w1.hip W1_SAMPLE_UP)
-        const bf16_t* Ks = K + ((size_t)b * sk.b + (size_t)h * sk.h);
-        const uint32_t step = (uint32_t)Skv / W1H_SAMPLE_KEYS;
-        float ms[2] = {-INFINITY, -INFINITY};
+    if (Skv >= 2 * W1_SAMPLE_KEYS) {   // M'[q] = min(b, m_s + W1_SAMPLE_UP log2 units), m_s = the sampled row maximum
+        float ms[2];
+        w1_sampled_max<8, load_row_frags128>(K + ((size_t)b * sk.b + (size_t)h * sk.h), sk.s, Skv, lane, qf, ms);
 #pragma unroll
-        for (int kb = 0; kb < W1H_SAMPLE_KEYS / 32; ++kb) {
-            bf16x8_t kf[8];
-            load_row_frags128(Ks, sk.s * step, 32 * kb, W1H_SAMPLE_KEYS, lane, kf);
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) asm volatile("" ::"v"(kf[ks]));
-#pragma unroll
-            for (int j = 0; j < 2; ++j) {
-                f32x16_t acc = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int ks = 0; ks < 8; ++ks) acc = mfma32(kf[ks], qf[j][ks], acc);
-                float m = acc[0];
-#pragma unroll
-                for (int i = 1; i < 16; ++i) m = fmaxf(m, acc[i]);
-                ms[j] = fmaxf(ms[j], fmaxf(m, other_half(m)));
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < 2; ++j) nmc[j] = -fminf(nmc[j], ms[j] + W1H_SAMPLE_UP / c);      // unscaled units: the loop multiplies by c
+        for (int j = 0; j < 2; ++j) nmc[j] = -fminf(nmc[j], ms[j] + W1_SAMPLE_UP / c);      // unscaled units: the loop multiplies by c
     } else {
 #pragma unroll
         for (int j = 0; j < 2; ++j) nmc[j] = -nmc[j];
     }
     const int nt = (Skv + 63) / 64;
-    {   // the pipeline's first transposed reads hit the V tile of ring slot 3: make it finite
-        const u32x4_t z = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(lds + 3 * W1H_SLOT_BYTES + W1H_TILE_BYTES + i * 4096 + threadIdx.x * 16) = z;
-    }
+    w1_zero_slot(lds, 3 * W1H::SLOT_BYTES + W1H::TILE_BYTES, 4);   // the V tile of ring slot 3
     __syncthreads();
 
     const bf16_t* Kb = K + ((size_t)b * sk.b + (size_t)h * sk.h);
     const bf16_t* Vb = V + ((size_t)b * sv.b + (size_t)h * sv.h);
     const W1Rsrc krs = w1_rsrc(Kb, ((uint32_t)(Skv - 1) * sk.s + (uint32_t)D128) * 2u);
     const W1Rsrc vrs = w1_rsrc(Vb, ((uint32_t)(Skv - 1) * sv.s + (uint32_t)D128) * 2u);
-    // this wave moves pieces 4 wave .. 4 wave + 3 of a tile: piece p = rows 4p .. 4p+3; lane -> (row 4p + lane / 16, LDS chunk lane % 16)
-    u32x8_t voff;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t row = 4u * (uint32_t)(wave * 4 + i) + (uint32_t)(lane >> 4);
-        const uint32_t cl = (uint32_t)(lane & 15) ^ w1h_swz(row);
-        voff[i] = (row * sk.s + cl * 8u) * 2u;
-        voff[4 + i] = (row * sv.s + cl * 8u) * 2u;
-    }
+    uint32_t avo[4], bvo[4];
+    w1_dma_offsets<D128>(wave, lane, sk.s, avo);
+    w1_dma_offsets<D128>(wave, lane, sv.s, bvo);
+    u32x8_t voff = {avo[0], avo[1], avo[2], avo[3], bvo[0], bvo[1], bvo[2], bvo[3]};
     const uint32_t kstep = __builtin_amdgcn_readfirstlane(64u * sk.s * 2u), vstep = __builtin_amdgcn_readfirstlane(64u * sv.s * 2u);
     const uint32_t wbase = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds + (uint32_t)wave * 4096u);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {   // tiles 0, 1 -> ring slots 0, 1
-        const uint32_t dst = wbase + (uint32_t)t * W1H_SLOT_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            w1_dma(dst + 1024u * i, krs, voff[i], 0u);
-            w1_dma(dst + W1H_TILE_BYTES + 1024u * i, vrs, voff[4 + i], 0u);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { voff[i] += kstep; voff[4 + i] += vstep; }
-    }
-    // lane-constant LDS read offsets, one set per slot pair (ds offsets are 16 bit)
-    u32x16_t la[2];
-    {
-        const uint32_t m = lane & 31;
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) la[st][ks] = st * 65536u + m * 256u + ((((uint32_t)(2 * ks) + (uint32_t)hi) ^ w1h_swz(m)) << 4);
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int r3 = 0; r3 < 2; ++r3) {
-                    const uint32_t rr = 4u * hi + ((uint32_t)(lane & 15) >> 2) + 8u * r3;
-                    const uint32_t cc = 4u * db + 2u * ((uint32_t)(lane >> 4) & 1u) + (((uint32_t)lane & 3u) >> 1);
-                    la[st][8 + 2 * db + r3] = st * 65536u + rr * 256u + ((cc ^ w1h_swz(rr)) << 4) + ((uint32_t)lane & 1u) * 8u;
-                }
-        }
-    }
-    const u32x16_t q00 = pack4h(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), q01 = pack4h(qf[0][4], qf[0][5], qf[0][6], qf[0][7]);
-    const u32x16_t q10 = pack4h(qf[1][0], qf[1][1], qf[1][2], qf[1][3]), q11 = pack4h(qf[1][4], qf[1][5], qf[1][6], qf[1][7]);
+    w1_prime<D128>(wbase, krs, vrs, voff, kstep, vstep);   // tiles 0, 1 -> ring slots 0, 1
+    const u32x16_t la[2] = {w1_read_offsets<D128>(lane), w1_read_offsets<D128>(lane, 65536u)};   // one table per slot pair
+    const u32x16_t q00 = w1_pack4(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), q01 = w1_pack4(qf[0][4], qf[0][5], qf[0][6], qf[0][7]);
+    const u32x16_t q10 = w1_pack4(qf[1][0], qf[1][1], qf[1][2], qf[1][3]), q11 = w1_pack4(qf[1][4], qf[1][5], qf[1][6], qf[1][7]);
     const uint32_t niter = (uint32_t)(nt + 1);     // one extra tile step drains the pipeline
     const uint32_t krem = (uint32_t)Skv;
     const uint32_t hi4 = 4u * (uint32_t)hi;
@@ -397,12 +297,7 @@ __global__ __launch_bounds__(256, 1) void attn128_fwd_w1_kernel(const bf16_t* __
         const float M = -nmc[j] * c;
         const int q = q0 + 32 * j + (lane & 31);
         if (q < Sq) {
-            float oabs = 0.f;
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oabs += fabsf(o[j][db][i]);
-            bad = bad || !(l >= W1H_L_MIN && l < W1H_L_MAX) || !(M <= W1H_M_MAX) || !(oabs < INFINITY);
+            bad = bad || w1_strip_bad(l, M, o[j]);
             store_col128_res8(O + ((size_t)b * so.b + (size_t)h * so.h + (size_t)q * so.s), RES_ROW(ORES, sor, b, h, q), o[j], 1.f / l, hi);
             if (hi == 0) LSE2[(size_t)bh * Sq + q] = M + __builtin_amdgcn_logf(l);
         }
@@ -614,13 +509,12 @@ __global__ __launch_bounds__(256, 1) void attn128_dkv_kernel(const bf16_t* __res
 // ----------------------------------------------------------------------------------------------------- dK, dV, w1 structure
 // One 32-key block per wave (dK^T, dV^T and the K, V fragments in AGPRs), Q | dO tiles and the statistics planes by LDS-DMA, main loop from
 // tools/gen_w1_asm.py::Dkv128Loop.  LDS-bandwidth-bound by construction (one fragment read per MFMA), see the generator's docstring.
-#define W1H_STAT_BYTES 1024
 __global__ __launch_bounds__(256, 1) void attn128_dkv_w1_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                                   const bf16_t* __restrict__ dO, const float* __restrict__ STATS, bf16_t* __restrict__ dK,
                                                                   bf16_t* __restrict__ dV, TStride sq, TStride sk, TStride sv, TStride sdo, TStride sdk,
                                                                   TStride sdv, int Sq, int Skv, int H, int n_kt, float c, float scale) {
-    __shared__ __attribute__((aligned(1024))) uint8_t lds[W1H_RING_BYTES + 4 * W1H_STAT_BYTES];   // slot = [Q tile | dO tile]; statistics behind the ring
-    const int vid = xcd_remap128(blockIdx.x, gridDim.x);
+    __shared__ __attribute__((aligned(1024))) uint8_t lds[W1H::RING_BYTES + W1_SLOTS * W1_STAT_BYTES];   // slot = [Q tile | dO tile]; statistics behind the ring
+    const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = vid / n_kt, kt = vid % n_kt;
     const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, hi = lane >> 5;
@@ -633,17 +527,13 @@ __global__ __launch_bounds__(256, 1) void attn128_dkv_w1_kernel(const bf16_t* __
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) { asm volatile("" ::"v"(kf[ks])); asm volatile("" ::"v"(vf[ks])); }
     const int nt = (Sq + 63) / 64;
-    {   // the pipeline's first transposed reads hit ring slot 3 (both tiles): make it finite
-        const u32x4_t z = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int i = 0; i < 8; ++i) *reinterpret_cast<u32x4_t*>(lds + 3 * W1H_SLOT_BYTES + i * 4096 + threadIdx.x * 16) = z;
-    }
+    w1_zero_slot(lds, 3 * W1H::SLOT_BYTES, 8);   // both tiles of ring slot 3
     __syncthreads();
 
     const W1Rsrc qrs = w1_rsrc(Q + ((size_t)b * sq.b + (size_t)h * sq.h), ((uint32_t)(Sq - 1) * sq.s + (uint32_t)D128) * 2u);
     const W1Rsrc dors = w1_rsrc(dO + ((size_t)b * sdo.b + (size_t)h * sdo.h), ((uint32_t)(Sq - 1) * sdo.s + (uint32_t)D128) * 2u);
     const W1Rsrc strs = w1_rsrc(STATS + (int64_t)bh * 2 * Sq, (uint32_t)(2 * Sq) * 4u);
-    u32x8_t voff;
+    u32x8_t voff;   // w1_dma_offsets<D128> -- inline here: through the attn_w1.h helper hipcc allocates this kernel's registers differently
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const uint32_t row = 4u * (uint32_t)(wave * 4 + i) + (uint32_t)(lane >> 4);
@@ -654,43 +544,15 @@ __global__ __launch_bounds__(256, 1) void attn128_dkv_w1_kernel(const bf16_t* __
     const uint32_t qstep = __builtin_amdgcn_readfirstlane(64u * sq.s * 2u), dstep = __builtin_amdgcn_readfirstlane(64u * sdo.s * 2u);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
     const uint32_t wbase = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)wave * 4096u);
-    const uint32_t sbase = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)W1H_RING_BYTES + (uint32_t)wave * 256u);
+    const uint32_t sbase = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)W1H::RING_BYTES + (uint32_t)wave * 256u);
     // statistics piece of this wave: lanes 0..15 fetch plane 0 (-lse2 / c) of rows 16 wave + lane, lanes 16..31 plane 1 (-delta); the upper
     // half-wave repeats the lower one (its 128 bytes of the LDS piece are never read)
     uint32_t svo = ((uint32_t)((lane >> 4) & 1) * (uint32_t)Sq + (uint32_t)(16 * wave + (lane & 15))) * 4u;
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {   // tiles 0, 1 -> ring slots 0, 1
-        const uint32_t dst = wbase + (uint32_t)t * W1H_SLOT_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            w1_dma(dst + 1024u * i, qrs, voff[i], 0u);
-            w1_dma(dst + W1H_TILE_BYTES + 1024u * i, dors, voff[4 + i], 0u);
-        }
-        w1_dma4(sbase + (uint32_t)t * W1H_STAT_BYTES, strs, svo, 0u);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { voff[i] += qstep; voff[4 + i] += dstep; }
-        svo += 256u;
-    }
-    u32x16_t la[2];
-    {
-        const uint32_t m = lane & 31;
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) la[st][ks] = st * 65536u + m * 256u + ((((uint32_t)(2 * ks) + (uint32_t)hi) ^ w1h_swz(m)) << 4);
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int r3 = 0; r3 < 2; ++r3) {
-                    const uint32_t rr = 4u * hi + ((uint32_t)(lane & 15) >> 2) + 8u * r3;
-                    const uint32_t cc = 4u * db + 2u * ((uint32_t)(lane >> 4) & 1u) + (((uint32_t)lane & 3u) >> 1);
-                    la[st][8 + 2 * db + r3] = st * 65536u + rr * 256u + ((cc ^ w1h_swz(rr)) << 4) + ((uint32_t)lane & 1u) * 8u;
-                }
-        }
-    }
-    const uint32_t sread = lds0 + (uint32_t)W1H_RING_BYTES + 16u * (uint32_t)hi;
-    const u32x16_t kf0 = pack4h(kf[0], kf[1], kf[2], kf[3]), kf1 = pack4h(kf[4], kf[5], kf[6], kf[7]);
-    const u32x16_t vf0 = pack4h(vf[0], vf[1], vf[2], vf[3]), vf1 = pack4h(vf[4], vf[5], vf[6], vf[7]);
+    w1_prime<D128>(wbase, qrs, dors, voff, qstep, dstep, &strs, sbase, &svo);   // tiles 0, 1 (and their statistics) -> ring slots 0, 1
+    const u32x16_t la[2] = {w1_read_offsets<D128>(lane), w1_read_offsets<D128>(lane, 65536u)};   // one table per slot pair
+    const uint32_t sread = lds0 + (uint32_t)W1H::RING_BYTES + 16u * (uint32_t)hi;
+    const u32x16_t kf0 = w1_pack4(kf[0], kf[1], kf[2], kf[3]), kf1 = w1_pack4(kf[4], kf[5], kf[6], kf[7]);
+    const u32x16_t vf0 = w1_pack4(vf[0], vf[1], vf[2], vf[3]), vf1 = w1_pack4(vf[4], vf[5], vf[6], vf[7]);
     const uint32_t niter = (uint32_t)(nt + 1);   // one extra tile step drains the pipeline
     const uint32_t cs = __builtin_amdgcn_readfirstlane(__float_as_uint(c));
     f32x16_t dk[4], dv[4];
@@ -722,8 +584,8 @@ __global__ __launch_bounds__(256, 1) void attn128_dq_w1x2_kernel(const bf16_t* _
                                                                    const bf16_t* __restrict__ dO, const float* __restrict__ STATS, bf16_t* __restrict__ dQ,
                                                                    TStride sq, TStride sk, TStride sv, TStride sdo, TStride sdq, int Sq, int Skv, int H, int n_qt,
                                                                    float c, float scale) {
-    __shared__ __attribute__((aligned(1024))) uint8_t lds[W1H_RING_BYTES];   // slot = [K tile | V tile]
-    const int vid = xcd_remap128(blockIdx.x, gridDim.x);
+    __shared__ __attribute__((aligned(1024))) uint8_t lds[W1H::RING_BYTES];   // slot = [K tile | V tile]
+    const int vid = xcd_remap(blockIdx.x, gridDim.x);
     const int bh = vid / n_qt, qt = vid % n_qt;
     const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, hi = lane >> 5;
@@ -742,57 +604,27 @@ __global__ __launch_bounds__(256, 1) void attn128_dq_w1x2_kernel(const bf16_t* _
         st4[2 + j] = __float_as_uint(STATS[(size_t)bh * 2 * Sq + Sq + qc]);
     }
     const int nt = (Skv + 63) / 64;
-    {   // the pipeline's first transposed reads hit the K tile of ring slot 3: make it finite
+    {   // the K tile of ring slot 3 (w1_zero_slot -- inline here: through the attn_w1.h helper hipcc allocates this kernel's registers differently)
         const u32x4_t z = {0u, 0u, 0u, 0u};
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(lds + 3 * W1H_SLOT_BYTES + i * 4096 + threadIdx.x * 16) = z;
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(lds + 3 * W1H::SLOT_BYTES + i * 4096 + threadIdx.x * 16) = z;
     }
     __syncthreads();
 
     const W1Rsrc krs = w1_rsrc(K + ((size_t)b * sk.b + (size_t)h * sk.h), ((uint32_t)(Skv - 1) * sk.s + (uint32_t)D128) * 2u);
     const W1Rsrc vrs = w1_rsrc(V + ((size_t)b * sv.b + (size_t)h * sv.h), ((uint32_t)(Skv - 1) * sv.s + (uint32_t)D128) * 2u);
-    u32x8_t voff;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const uint32_t row = 4u * (uint32_t)(wave * 4 + i) + (uint32_t)(lane >> 4);
-        const uint32_t cl = (uint32_t)(lane & 15) ^ w1h_swz(row);
-        voff[i] = (row * sk.s + cl * 8u) * 2u;
-        voff[4 + i] = (row * sv.s + cl * 8u) * 2u;
-    }
+    uint32_t avo[4], bvo[4];
+    w1_dma_offsets<D128>(wave, lane, sk.s, avo);
+    w1_dma_offsets<D128>(wave, lane, sv.s, bvo);
+    u32x8_t voff = {avo[0], avo[1], avo[2], avo[3], bvo[0], bvo[1], bvo[2], bvo[3]};
     const uint32_t kstep = __builtin_amdgcn_readfirstlane(64u * sk.s * 2u), vstep = __builtin_amdgcn_readfirstlane(64u * sv.s * 2u);
     const uint32_t wbase = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds + (uint32_t)wave * 4096u);
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const uint32_t dst = wbase + (uint32_t)t * W1H_SLOT_BYTES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-            w1_dma(dst + 1024u * i, krs, voff[i], 0u);
-            w1_dma(dst + W1H_TILE_BYTES + 1024u * i, vrs, voff[4 + i], 0u);
-        }
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { voff[i] += kstep; voff[4 + i] += vstep; }
-    }
-    u32x16_t la[2];
-    {
-        const uint32_t m = lane & 31;
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-#pragma unroll
-            for (int ks = 0; ks < 8; ++ks) la[st][ks] = st * 65536u + m * 256u + ((((uint32_t)(2 * ks) + (uint32_t)hi) ^ w1h_swz(m)) << 4);
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int r3 = 0; r3 < 2; ++r3) {
-                    const uint32_t rr = 4u * hi + ((uint32_t)(lane & 15) >> 2) + 8u * r3;
-                    const uint32_t cc = 4u * db + 2u * ((uint32_t)(lane >> 4) & 1u) + (((uint32_t)lane & 3u) >> 1);
-                    la[st][8 + 2 * db + r3] = st * 65536u + rr * 256u + ((cc ^ w1h_swz(rr)) << 4) + ((uint32_t)lane & 1u) * 8u;
-                }
-        }
-    }
-    const u32x16_t q00 = pack4h(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), q01 = pack4h(qf[0][4], qf[0][5], qf[0][6], qf[0][7]);
-    const u32x16_t q10 = pack4h(qf[1][0], qf[1][1], qf[1][2], qf[1][3]), q11 = pack4h(qf[1][4], qf[1][5], qf[1][6], qf[1][7]);
-    const u32x16_t d00 = pack4h(dof[0][0], dof[0][1], dof[0][2], dof[0][3]), d01 = pack4h(dof[0][4], dof[0][5], dof[0][6], dof[0][7]);
-    const u32x16_t d10 = pack4h(dof[1][0], dof[1][1], dof[1][2], dof[1][3]), d11 = pack4h(dof[1][4], dof[1][5], dof[1][6], dof[1][7]);
+    w1_prime<D128>(wbase, krs, vrs, voff, kstep, vstep);   // tiles 0, 1 -> ring slots 0, 1
+    const u32x16_t la[2] = {w1_read_offsets<D128>(lane), w1_read_offsets<D128>(lane, 65536u)};   // one table per slot pair
+    const u32x16_t q00 = w1_pack4(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), q01 = w1_pack4(qf[0][4], qf[0][5], qf[0][6], qf[0][7]);
+    const u32x16_t q10 = w1_pack4(qf[1][0], qf[1][1], qf[1][2], qf[1][3]), q11 = w1_pack4(qf[1][4], qf[1][5], qf[1][6], qf[1][7]);
+    const u32x16_t d00 = w1_pack4(dof[0][0], dof[0][1], dof[0][2], dof[0][3]), d01 = w1_pack4(dof[0][4], dof[0][5], dof[0][6], dof[0][7]);
+    const u32x16_t d10 = w1_pack4(dof[1][0], dof[1][1], dof[1][2], dof[1][3]), d11 = w1_pack4(dof[1][4], dof[1][5], dof[1][6], dof[1][7]);
     const uint32_t niter = (uint32_t)(nt + 1);
     const uint32_t cs = __builtin_amdgcn_readfirstlane(__float_as_uint(c));
     f32x16_t dq[2][4];
@@ -855,7 +687,7 @@ extern "C" int32_t vgpa_attn128_fwd(const void* q, const void* k, const void* v,
         unsigned* kmax2 = (unsigned*)workspace;
         int* flags = (int*)workspace + B * H;
         if (hipMemsetAsync(workspace, 0, vgpa_attn128_fwd_workspace_bytes(B, H, Sq), stream) != hipSuccess) return VGPA_ERR_LAUNCH;
-        VGPA_LAUNCH(attn128_kmax_kernel, dim3(16, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)k, mk(k_strides), (int)Skv, (int)H, kmax2);
+        VGPA_LAUNCH((w1_kmax_kernel<D128 / 8>), dim3(16, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)k, mk(k_strides), (int)Skv, (int)H, kmax2);
         VGPA_LAUNCH(attn128_fwd_w1_kernel, dim3((unsigned)tasks256), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v, (bf16_t*)o, lse2,
                     (const unsigned*)kmax2, flags, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)Sq, (int)Skv, (int)H, (int)n_q256, c,
                     ores, sor);
@@ -1078,18 +910,18 @@ __global__ __launch_bounds__(256, 1) void attn128_fwd_f8_kernel(const uint8_t* _
             for (int u = 0; u < 2; ++u) qf[j][ks][u] = *reinterpret_cast<const u32x4_t*>(row + 64 * ks + 32 * u + 16 * hi);
         nm[j] = -(sqrtf(QN2[(size_t)bh * Sq + q]) * kmax * 1.0009765625f);      // -b[q]: a hair above |q8 row| max |k8 row| >= every score of the row
     }
-    if (Skv >= 2 * W1H_SAMPLE_KEYS) {
-        // Round 6: the shift follows the data here too (attention_w1.hip W1_SAMPLE_UP).  M'[q] = b[q] - n, n = floor(max(0, b - (m_s + 64))) with m_s the row's maximum over
+    if (Skv >= 2 * W1_SAMPLE_KEYS) {
+        // Round 6: the shift follows the data here too (attn_w1.h W1_SAMPLE_UP).  M'[q] = b[q] - n, n = floor(max(0, b - (m_s + 64))) with m_s the row's maximum over
         // 64 keys spread evenly over the sweep (8 scaled MFMAs per wave on the e4m3 operands themselves).  n is an INTEGER: every p = exp2(s - M') is the bound-shifted
         // p times 2^n exactly, the per-tile exponent x moves by n with it, so P8 = e4m3(p / 2^x) keeps the bits oracle/wan.py::_F8Attn models -- except that rows whose
         // scores lie > 100 log2 units under the bound (QK-norm gains >= 2.5: every strip) no longer underflow into the redo pass (measured 14.3 ms per launch there
         // against 4.1: profiles/r06_bench_cfg5_trained_like.json).  Flags as in the bf16 kernels: l outside [2^-100, 2^118), M' > 1024, a non-finite accumulator.
         typedef int v8i_t __attribute__((ext_vector_type(8)));
-        const uint32_t step = (uint32_t)Skv / W1H_SAMPLE_KEYS;
+        const uint32_t step = (uint32_t)Skv / W1_SAMPLE_KEYS;
         const int sa = 127 + ek, sb = 127 + eq;
         float ms[2] = {-INFINITY, -INFINITY};
 #pragma unroll
-        for (int kb = 0; kb < W1H_SAMPLE_KEYS / 32; ++kb) {
+        for (int kb = 0; kb < W1_SAMPLE_KEYS / 32; ++kb) {
             const uint8_t* krow = K8 + ((size_t)bh * Skv + (size_t)(32 * kb + m) * step) * 128;
             u32x4_t kf[2][2];
 #pragma unroll
@@ -1113,15 +945,11 @@ __global__ __launch_bounds__(256, 1) void attn128_fwd_f8_kernel(const uint8_t* _
             }
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) nm[j] += floorf(fmaxf(0.f, -nm[j] - (ms[j] + W1H_SAMPLE_UP)));      // -M' = -b + n
+        for (int j = 0; j < 2; ++j) nm[j] += floorf(fmaxf(0.f, -nm[j] - (ms[j] + W1_SAMPLE_UP)));      // -M' = -b + n
     }
-    {   // C of the first two iterations reads the V8^T halves of ring slots 2 and 3: make them finite (P8 = 0 there)
-        const u32x4_t z = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int sl = 2; sl < 4; ++sl)
-#pragma unroll
-            for (int i = 0; i < 2; ++i) *reinterpret_cast<u32x4_t*>(lds + sl * F8_SLOT_BYTES + 8192 + i * 4096 + threadIdx.x * 16) = z;
-    }
+    // C of the first two iterations reads the V8^T halves of ring slots 2 and 3: make them finite (P8 = 0 there)
+    w1_zero_slot(lds, 2 * F8_SLOT_BYTES + 8192, 2);
+    w1_zero_slot(lds, 3 * F8_SLOT_BYTES + 8192, 2);
     __syncthreads();
 
     const W1Rsrc krs = w1_rsrc(K8 + (size_t)bh * Skv * 128, (uint32_t)Skv * 128u);                 // rows >= Skv read as zeros
@@ -1195,12 +1023,7 @@ __global__ __launch_bounds__(256, 1) void attn128_fwd_f8_kernel(const uint8_t* _
         const float M = -nm[j];
         const int q = q0 + 32 * j + m;
         if (q < Sq) {
-            float oabs = 0.f;
-#pragma unroll
-            for (int db = 0; db < 4; ++db)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oabs += fabsf(o[j][db][i]);
-            bad = bad || !(l >= W1H_L_MIN && l < W1H_L_MAX) || !(M <= W1H_M_MAX) || !(oabs < INFINITY);
+            bad = bad || w1_strip_bad(l, M, o[j]);
             store_col128_res8(O + ((size_t)b * so.b + (size_t)h * so.h + (size_t)q * so.s), RES_ROW(ORES, sor, b, h, q), o[j], 1.f / l, hi);
             if (hi == 0) LSE2[(size_t)bh * Sq + q] = M + __builtin_amdgcn_logf(l);
         }

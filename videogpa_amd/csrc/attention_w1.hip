@@ -8,11 +8,9 @@
 //   * K/V (Q/dO) tiles never pass through VGPRs: each wave issues `buffer_load_dwordx4 ... lds` pieces two tiles ahead
 //     into a 4-slot ring (attn_w1.h), completion counted by hand (s_waitcnt vmcnt(N)), ONE s_barrier per 64-row tile.
 //   * the LDS image is unpadded and chunk-swizzled: row-fragment reads and transpose reads are both conflict-free.
-#include "attn_common.h"
-
 #include <type_traits>
 
-#include "attn_w1.h"
+#include "attn_w1.h"   // the ring, and the shell pieces the three kernels below share with attention_hd128.hip
 
 // fp32 partials one (task, chunk) of a split backward task leaves in the workspace: the kernels' SPLIT epilogues, the merge kernels, the
 // launchers' plans and vgpa_attn_bwd_split_workspace_bytes all go by these two
@@ -24,17 +22,6 @@
 // (S^T and dP^T are made per 32-key half-tile with q on the MFMA columns; -lse2 and -delta ride an extra k-step.)
 // The main loop is tools/gen_w1_asm.py::DqLoop (w1_dq_loop.inc): read its docstring for the pipeline and the register map.
 // =====================================================================================================
-typedef __attribute__((ext_vector_type(16))) uint32_t u32x16_t;
-typedef __attribute__((ext_vector_type(8))) uint32_t u32x8_t;
-
-__device__ __forceinline__ u32x16_t pack4(const bf16x8_t& a, const bf16x8_t& b, const bf16x8_t& c, const bf16x8_t& d) {
-    const u32x4_t w[4] = {__builtin_bit_cast(u32x4_t, a), __builtin_bit_cast(u32x4_t, b), __builtin_bit_cast(u32x4_t, c), __builtin_bit_cast(u32x4_t, d)};
-    u32x16_t r;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) r[i] = w[i >> 2][i & 3];
-    return r;
-}
-
 // SPLIT: workgroup (task0 + blockIdx / nsplit, chunk blockIdx % nsplit) sweeps key tiles [nt*chunk/nsplit, nt*(chunk+1)/nsplit)
 // and leaves its unscaled fp32 dQ [256][64] in `part` (w1_dq_merge_kernel adds the chunks).
 template <bool SPLIT>
@@ -46,8 +33,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
                                                                   float* __restrict__ part) {
     constexpr int QB = 2;
     __shared__ __attribute__((aligned(1024))) uint8_t lds[W1_RING_BYTES];   // slot = [K tile | V tile]
-    const int vid = task0 + (SPLIT ? (int)blockIdx.x / nsplit : xcd_remap(blockIdx.x, gridDim.x));
-    const int chunk = SPLIT ? (int)blockIdx.x % nsplit : 0;
+    int vid, chunk;
+    w1_task<SPLIT>(task0, nsplit, vid, chunk);
     const int bh = vid / n_qt, qt = vid % n_qt;
     const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, hi = lane >> 5;
@@ -71,16 +58,10 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
 #pragma unroll
     for (int j = 0; j < QB; ++j) { frags_arrived(qf[j]); frags_arrived(dof[j]); }
 
-    const int nt_all = (S + TILE - 1) / TILE;
-    const int tb = SPLIT ? nt_all * chunk / nsplit : 0;              // this workgroup's key tiles: [tb, nt)
-    const int nt = SPLIT ? nt_all * (chunk + 1) / nsplit : nt_all;
+    const W1Range tr = w1_split_range(S, chunk, nsplit, SPLIT);      // this workgroup's key tiles: [tb, nt)
+    const int tb = tr.tb, nt = tr.nt;
 
-    // the pipeline's first transposed-K reads hit the slot "before" tile tb (ring slot 3): make it finite
-    {
-        const u32x4_t z = {0u, 0u, 0u, 0u};
-        *reinterpret_cast<u32x4_t*>(lds + 3 * W1_SLOT_BYTES + threadIdx.x * 16) = z;
-        *reinterpret_cast<u32x4_t*>(lds + 3 * W1_SLOT_BYTES + 4096 + threadIdx.x * 16) = z;
-    }
+    w1_zero_slot(lds, 3 * W1_SLOT_BYTES, 2);   // the K tile of the slot "before" tile tb
     __syncthreads();
 
     const bf16_t* Kb = K + ((size_t)b * sk.b + (size_t)h * sk.h);
@@ -88,27 +69,16 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
     const W1Rsrc krs = w1_rsrc(Kb, ((uint32_t)(S - 1) * sk.s + (uint32_t)HD) * 2u);
     const W1Rsrc vrs = w1_rsrc(Vb, ((uint32_t)(S - 1) * sv.s + (uint32_t)HD) * 2u);
     uint32_t kvo[2], vvo[2];
-    w1_dma_offsets<2>(wave, lane, sk.s, kvo);
-    w1_dma_offsets<2>(wave, lane, sv.s, vvo);
+    w1_dma_offsets<HD>(wave, lane, sk.s, kvo);
+    w1_dma_offsets<HD>(wave, lane, sv.s, vvo);
     const uint32_t kstep = __builtin_amdgcn_readfirstlane(64u * sk.s * 2u), vstep = __builtin_amdgcn_readfirstlane(64u * sv.s * 2u);   // bytes per tile
     const uint32_t wbase = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds + (uint32_t)wave * 2048u);
-    // The tile offset rides in the per-lane offset (not in the scalar offset): the descriptor's range check must see it, so
-    // that rows at or past S -- and whole tiles past the end -- arrive as zeros.
     u32x4_t voff = {kvo[0] + (uint32_t)tb * kstep, kvo[1] + (uint32_t)tb * kstep, vvo[0] + (uint32_t)tb * vstep, vvo[1] + (uint32_t)tb * vstep};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {   // tiles tb, tb + 1 -> ring slots 0, 1
-        const uint32_t dst = wbase + (uint32_t)i * W1_SLOT_BYTES;
-        w1_dma(dst, krs, voff[0], 0u);
-        w1_dma(dst + 1024u, krs, voff[1], 0u);
-        w1_dma(dst + W1_TILE_BYTES, vrs, voff[2], 0u);
-        w1_dma(dst + W1_TILE_BYTES + 1024u, vrs, voff[3], 0u);
-        voff[0] += kstep; voff[1] += kstep; voff[2] += vstep; voff[3] += vstep;
-    }
+    w1_prime<HD>(wbase, krs, vrs, voff, kstep, vstep);   // tiles tb, tb + 1 -> ring slots 0, 1
 
-    const W1Lane la = w1_lane_offsets(lane);
-    const u32x8_t la8 = {la.row[0], la.row[1], la.row[2], la.row[3], la.tr[0][0], la.tr[0][1], la.tr[1][0], la.tr[1][1]};
-    const u32x16_t qf0 = pack4(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), qf1 = pack4(qf[1][0], qf[1][1], qf[1][2], qf[1][3]);
-    const u32x16_t do0 = pack4(dof[0][0], dof[0][1], dof[0][2], dof[0][3]), do1 = pack4(dof[1][0], dof[1][1], dof[1][2], dof[1][3]);
+    const u32x8_t la8 = w1_read_offsets<HD>(lane);
+    const u32x16_t qf0 = w1_pack4(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), qf1 = w1_pack4(qf[1][0], qf[1][1], qf[1][2], qf[1][3]);
+    const u32x16_t do0 = w1_pack4(dof[0][0], dof[0][1], dof[0][2], dof[0][3]), do1 = w1_pack4(dof[1][0], dof[1][1], dof[1][2], dof[1][3]);
     const uint32_t niter = (uint32_t)(nt - tb + 1);   // one extra tile step drains the pipeline
     f32x16_t dq[QB][2];
     uint32_t t0, t1, t2;
@@ -126,6 +96,7 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
 #pragma unroll
     for (int j = 0; j < QB; ++j) { asm volatile("" : "+v"(dq[j][0])); asm volatile("" : "+v"(dq[j][1])); }
 
+    // both epilogues (w1_store_part_row, w1_store_bf16_row) -- inline here: through the attn_w1.h helper hipcc allocates this kernel's registers differently
     if (SPLIT) {
         float* pb = part + ((size_t)(vid - task0) * nsplit + chunk) * W1_DQ_PART_FLOATS;
 #pragma unroll
@@ -173,31 +144,12 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dq_w1_kernel(const bf16_t* __
 // =====================================================================================================
 #include "w1_fwd_knobs.inc"                   // W1_FWD_MFSUM: what the generated loop expects around it (tools/gen_w1_asm.py W1_KNOBS mfsum; 1 in the product)
 #define W1_FWD_PART_FLOATS (256 * (HD + 2))   // per (task, chunk) of a split forward task: O[256][64] (un-normalised), M[256], l[256]
-#define W1_L_MIN 7.8886e-31f                  // 2^-100: below this the row's sum is too close to underflow -> redo
-// ... and above 2^118 too close to overflow: the O accumulators carry sum_j p_j v_j <= l max|v| (a row whose true maximum lies 112-128 above the shift has a FINITE
-// l next to O = +-inf, and 1 / l flushes to zero from 2^126 on).  Found by `bench.py --weights trained_like` (one row of block 38, true maximum 127.7 above M':
-// l = 2^127.7, O = inf, strip not flagged -> NaN loss; tools/attn_fault_repro.py).  2^118 leaves |v| < 2^10 before an accumulator overflows, and the epilogue checks
-// the accumulators themselves (oabs) for whatever |v| the caller brings; a first cut at 2^100 moved the cliff of tools/attn_robust.py in by 18 log2 units of row
-// maximum for nothing (gain 4: 11 % -> 46 % of the strips redone).
-#define W1_L_MAX 3.3230699e35f                // 2^118
 // With the shift at the row BOUND the largest weight of a row is exp2(s_max - M), not 1, so it carries a bf16 rounding error in the
 // numerator (2^-9 relative) that the fp32 denominator does not share; over a few dozen keys these errors average out, over one or
 // two they do not (S = 1: O off by up to 0.4 %).  Rows that short are not a performance case: below this length every strip goes to
 // the online-softmax kernel.
 #define W1_FWD_MIN_S 128
-// The shift M' only has to put exp2(s - M') inside fp32's range for every score that matters, it does not have to be an upper bound: the weights go to the matrix
-// pipe as bf16 (fp32's exponent range) and l, O accumulate in fp32.  M'[q] = min(b[q], m_s[q] + W1_SAMPLE_UP) with b = |q| max|k| (Cauchy-Schwarz, >= every score) and
-// m_s = the row's maximum over W1_SAMPLE_KEYS keys spread evenly over the sequence (16 MFMAs per wave in the prologue: 0.2 % of the sweep), a LOWER bound of the true
-// maximum m*.  Then  M' - m* <= M' - m_s <= 64  always (nothing that matters underflows: terms below 2^-62 of the row's largest are dropped), and  m* - M' <= 112
-// (no overflow: l <= S 2^112 < 2^127) whenever b - m_s <= 176 or, beyond that, whenever the true maximum is not more than 176 log2 units above the sampled one.  A row
-// outside (an extreme outlier key the sample missed) makes l = inf: the strip is flagged and redone by the online-softmax kernel, as before.
-// Round 5 shifted by b itself (p <= 1) and flagged every strip whose maximum lay > 100 below b or whose b exceeded 160: a QK-norm gain of 2.5 with a few outlier
-// channels (row entropy < 1 bit) sent the whole launch to the redo kernel, 2.5-3 x the time (tools/attn_robust.py, profiles/r06*_attn_trained_like.*).
-#define W1_SAMPLE_KEYS 64
-#define W1_SAMPLE_UP 64.0f
-// the scores are accumulated on top of -M' in fp32: at |M'| = 1024 the accumulator's ulp is 2^-13 log2 units = 8e-5 relative in a weight, a fiftieth of the bf16
-// rounding the weight gets anyway (round 5 flagged every strip above 160: a QK-norm gain of 3.8 already sent the whole launch to the online-softmax kernel)
-#define W1_M_MAX 1024.0f
+// (The shift M'[q] = min(b[q], m_s[q] + W1_SAMPLE_UP) and the flag thresholds W1_L_MIN, W1_L_MAX, W1_M_MAX: attn_w1.h, shared with head_dim 128.)
 
 // The rounding residual of four outputs, x - bf16(x), itself as bf16 (relative error 2^-9 of a quantity that is 2^-9 of x: the pair (o, o_res)
 // carries O to ~2^-17).  Consumer: the backward's delta = rowsum(dO o (O + O_res)) (w1_bwd_prep_kernel / attn_delta_kernel).  Why: delta stands for
@@ -211,27 +163,6 @@ __device__ __forceinline__ u32x2_t w1_residual4(const float* x, u32x2_t packed) 
     return r;
 }
 
-// max_k |k| per (batch, head): kmax2[bh] = max over keys of sum_d k^2 (fp32 bits compared as integers: non-negative floats)
-__global__ __launch_bounds__(256) void w1_kmax_kernel(const bf16_t* __restrict__ K, TStride sk, int S, int H, unsigned* __restrict__ kmax2) {
-    const int bh = blockIdx.y, b = bh / H, h = bh % H;
-    const bf16_t* Kb = K + ((size_t)b * sk.b + (size_t)h * sk.h);
-    float mx = 0.f;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < (int64_t)S * 8; i += (int64_t)gridDim.x * 256) {   // 8 lanes per row
-        const int row = (int)(i >> 3), c8 = (int)(i & 7);
-        float f[8];
-        unpack8(*reinterpret_cast<const u32x4_t*>(Kb + ((size_t)row * sk.s + c8 * 8)), f);
-        float a = 0.f;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) a += f[j] * f[j];
-        a += __shfl_xor(a, 1, 64);
-        a += __shfl_xor(a, 2, 64);
-        a += __shfl_xor(a, 4, 64);
-        mx = fmaxf(mx, a);
-    }
-    mx = wave_max(mx);
-    if ((threadIdx.x & 63) == 0) atomicMax(kmax2 + bh, __float_as_uint(mx));
-}
-
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K, const bf16_t* __restrict__ V,
                                                                bf16_t* __restrict__ O, float* __restrict__ LSE2, const unsigned* __restrict__ KMAX2,
@@ -240,8 +171,8 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const bf16_t* __res
                                                                TStride sor, int res_kind) {
     constexpr int QB = 2;
     __shared__ __attribute__((aligned(1024))) uint8_t lds[W1_RING_BYTES];   // slot = [K tile | V tile]
-    const int vid = task0 + (SPLIT ? (int)blockIdx.x / nsplit : xcd_remap(blockIdx.x, gridDim.x));
-    const int chunk = SPLIT ? (int)blockIdx.x % nsplit : 0;
+    int vid, chunk;
+    w1_task<SPLIT>(task0, nsplit, vid, chunk);
     const int bh = vid / n_qt, qt = vid % n_qt;
     const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, hi = lane >> 5;
@@ -268,6 +199,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const bf16_t* __res
         nm[j] = sqrtf(a) * kmax * 1.0009765625f;         // b[q], a hair above |q| |k|max: rounding of the bound itself can never let a score exceed it
     }
     {   // m_s[q]: the row's maximum over W1_SAMPLE_KEYS keys spread evenly over the sequence -- a LOWER bound of the true maximum (see W1_SAMPLE_UP)
+        // (w1_sampled_max<4, load_row_frags> -- inline here: through the attn_w1.h helper hipcc allocates this kernel's registers differently)
         const bf16_t* Ks = K + ((size_t)b * sk.b + (size_t)h * sk.h);
         const uint32_t step = (uint32_t)S / W1_SAMPLE_KEYS;          // S >= W1_FWD_MIN_S = 128 here: step >= 2, the last sampled row is 63 step < S
         float ms[QB];
@@ -293,15 +225,10 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const bf16_t* __res
         for (int j = 0; j < QB; ++j) nm[j] = -fminf(nm[j], ms[j] + W1_SAMPLE_UP);        // -M'[q]
     }
 
-    const int nt_all = (S + TILE - 1) / TILE;
-    const int tb = SPLIT ? nt_all * chunk / nsplit : 0;              // this workgroup's key tiles: [tb, nt)
-    const int nt = SPLIT ? nt_all * (chunk + 1) / nsplit : nt_all;
+    const W1Range tr = w1_split_range(S, chunk, nsplit, SPLIT);      // this workgroup's key tiles: [tb, nt)
+    const int tb = tr.tb, nt = tr.nt;
 
-    {   // the pipeline's first transposed reads hit the V tile of the slot "before" tile tb (ring slot 3): make it finite
-        const u32x4_t z = {0u, 0u, 0u, 0u};
-        *reinterpret_cast<u32x4_t*>(lds + 3 * W1_SLOT_BYTES + W1_TILE_BYTES + threadIdx.x * 16) = z;
-        *reinterpret_cast<u32x4_t*>(lds + 3 * W1_SLOT_BYTES + W1_TILE_BYTES + 4096 + threadIdx.x * 16) = z;
-    }
+    w1_zero_slot(lds, 3 * W1_SLOT_BYTES + W1_TILE_BYTES, 2);   // the V tile of the slot "before" tile tb
     __syncthreads();
 
     const bf16_t* Kb = K + ((size_t)b * sk.b + (size_t)h * sk.h);
@@ -309,24 +236,15 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const bf16_t* __res
     const W1Rsrc krs = w1_rsrc(Kb, ((uint32_t)(S - 1) * sk.s + (uint32_t)HD) * 2u);
     const W1Rsrc vrs = w1_rsrc(Vb, ((uint32_t)(S - 1) * sv.s + (uint32_t)HD) * 2u);
     uint32_t kvo[2], vvo[2];
-    w1_dma_offsets<2>(wave, lane, sk.s, kvo);
-    w1_dma_offsets<2>(wave, lane, sv.s, vvo);
+    w1_dma_offsets<HD>(wave, lane, sk.s, kvo);
+    w1_dma_offsets<HD>(wave, lane, sv.s, vvo);
     const uint32_t kstep = __builtin_amdgcn_readfirstlane(64u * sk.s * 2u), vstep = __builtin_amdgcn_readfirstlane(64u * sv.s * 2u);
     const uint32_t wbase = __builtin_amdgcn_readfirstlane((uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds + (uint32_t)wave * 2048u);
     u32x4_t voff = {kvo[0] + (uint32_t)tb * kstep, kvo[1] + (uint32_t)tb * kstep, vvo[0] + (uint32_t)tb * vstep, vvo[1] + (uint32_t)tb * vstep};
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {   // tiles tb, tb + 1 -> ring slots 0, 1
-        const uint32_t dst = wbase + (uint32_t)i * W1_SLOT_BYTES;
-        w1_dma(dst, krs, voff[0], 0u);
-        w1_dma(dst + 1024u, krs, voff[1], 0u);
-        w1_dma(dst + W1_TILE_BYTES, vrs, voff[2], 0u);
-        w1_dma(dst + W1_TILE_BYTES + 1024u, vrs, voff[3], 0u);
-        voff[0] += kstep; voff[1] += kstep; voff[2] += vstep; voff[3] += vstep;
-    }
+    w1_prime<HD>(wbase, krs, vrs, voff, kstep, vstep);   // tiles tb, tb + 1 -> ring slots 0, 1
 
-    const W1Lane la = w1_lane_offsets(lane);
-    const u32x8_t la8 = {la.row[0], la.row[1], la.row[2], la.row[3], la.tr[0][0], la.tr[0][1], la.tr[1][0], la.tr[1][1]};
-    const u32x16_t qf0 = pack4(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), qf1 = pack4(qf[1][0], qf[1][1], qf[1][2], qf[1][3]);
+    const u32x8_t la8 = w1_read_offsets<HD>(lane);
+    const u32x16_t qf0 = w1_pack4(qf[0][0], qf[0][1], qf[0][2], qf[0][3]), qf1 = w1_pack4(qf[1][0], qf[1][1], qf[1][2], qf[1][3]);
     const uint32_t niter = (uint32_t)(nt - tb + 1);                       // one extra tile step drains the pipeline
     const int kend = nt * TILE < S ? nt * TILE : S;
     const uint32_t krem = (uint32_t)(kend - tb * TILE);                   // valid keys from tile tb on (of this chunk)
@@ -368,7 +286,7 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const bf16_t* __res
         float* pb = part + ((size_t)(vid - task0) * nsplit + chunk) * W1_FWD_PART_FLOATS;
 #pragma unroll
         for (int j = 0; j < QB; ++j) {
-            const int r = wave * (32 * QB) + 32 * j + (lane & 31);
+            const int r = wave * (32 * QB) + 32 * j + (lane & 31);   // w1_store_part_row -- inline here: through the attn_w1.h helper hipcc allocates this kernel's registers differently
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
@@ -385,29 +303,20 @@ __global__ __launch_bounds__(256, 1) void attn_fwd_w1_kernel(const bf16_t* __res
     for (int j = 0; j < QB; ++j) {
         const int q = q0 + 32 * j + (lane & 31);
         if (q < S) {
-            float oabs = 0.f;                                 // inf / NaN in any accumulator of the row survives the sum (fmaxf would drop a NaN)
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) oabs += fabsf(o[j][db][i]);
-            bad = bad || !(l[j] >= W1_L_MIN && l[j] < W1_L_MAX) || !(-nm[j] <= W1_M_MAX) || !(oabs < INFINITY);
+            bad = bad || w1_strip_bad(l[j], -nm[j], o[j]);
             const float inv = 1.f / l[j];
             bf16_t* op = O + ((size_t)b * so.b + (size_t)h * so.h + (size_t)q * so.s);
             const size_t ro = (size_t)b * sor.b + (size_t)h * sor.h + (size_t)q * sor.s;      // residual row (elements of either kind)
 #pragma unroll
             for (int db = 0; db < 2; ++db)
 #pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {          // 16-byte stores of the output (8-byte ones of its res8 bytes): common.h pair_rows8
+                for (int gp = 0; gp < 2; ++gp) {          // w1_store_bf16_row with the residual (8-byte stores of the res8 bytes)
                     u32x2_t w[2], rw[2];
                     uint32_t rb[2];
 #pragma unroll
                     for (int e = 0; e < 2; ++e) {
-                        const int g = 2 * gp + e;
                         float x[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) x[i] = o[j][db][4 * g + i] * inv;
-                        w[e][0] = pack_bf16x2(x[0], x[1]);
-                        w[e][1] = pack_bf16x2(x[2], x[3]);
+                        w[e] = w1_pack_bf16x4(o[j][db], 2 * gp + e, inv, x);
                         if (res_kind == VGPA_RES_8) rb[e] = res8_pack4(x, w[e]);
                         else if (res_kind == VGPA_RES_BF16) rw[e] = w1_residual4(x, w[e]);
                     }
@@ -452,7 +361,7 @@ __global__ __launch_bounds__(256) void w1_fwd_merge_kernel(const float* __restri
     const bool obad = __any(!(fabsf(acc) < INFINITY));      // the row's 64 un-normalised outputs live one per lane
     if (lane == 0) {
         LSE2[(int64_t)bh * S + q] = pb[256 * HD + r] + __builtin_amdgcn_logf(L);
-        if (!(L >= W1_L_MIN && L < W1_L_MAX) || !(pb[256 * HD + r] <= W1_M_MAX) || obad) flags[vid] = 1;
+        if (w1_stats_bad(L, pb[256 * HD + r]) || obad) flags[vid] = 1;
     }
 }
 
@@ -461,7 +370,6 @@ __global__ __launch_bounds__(256) void w1_fwd_merge_kernel(const float* __restri
 // The main loop is tools/gen_w1_asm.py::DkvLoop (w1_dkv_loop.inc).  `stats` = fp32 [B, H, 2, S]: plane 0 = -lse2, plane 1 = -delta
 // (w1_bwd_prep_kernel); the 64 rows' statistics of a tile travel next to it by LDS-DMA and enter the score chains as srcC.
 // =====================================================================================================
-#define W1_STAT_BYTES 1024   // per ring slot: 4 waves x (16 x -lse2 | 16 x -delta | 128 B unused)
 template <bool SPLIT>
 __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* __restrict__ Q, const bf16_t* __restrict__ K,
                                                                    const bf16_t* __restrict__ V, const bf16_t* __restrict__ dO,
@@ -470,8 +378,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* _
                                                                    int H, int n_kt, float kscale, int task0, int nsplit, float* __restrict__ part) {
     constexpr int KB = 2;
     __shared__ __attribute__((aligned(1024))) uint8_t lds[W1_RING_BYTES + W1_SLOTS * W1_STAT_BYTES];   // slot = [Q tile | dO tile]; statistics behind the ring
-    const int vid = task0 + (SPLIT ? (int)blockIdx.x / nsplit : xcd_remap(blockIdx.x, gridDim.x));
-    const int chunk = SPLIT ? (int)blockIdx.x % nsplit : 0;
+    int vid, chunk;
+    w1_task<SPLIT>(task0, nsplit, vid, chunk);
     const int bh = vid / n_kt, kt = vid % n_kt;
     const int b = bh / H, h = bh % H;
     const int lane = threadIdx.x & 63, hi = lane >> 5;
@@ -487,11 +395,11 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* _
 #pragma unroll
     for (int j = 0; j < KB; ++j) { frags_arrived(kf[j]); frags_arrived(vf[j]); }
 
-    const int nt_all = (S + TILE - 1) / TILE;
-    const int tb = SPLIT ? nt_all * chunk / nsplit : 0;              // this workgroup's query tiles: [tb, nt)
-    const int nt = SPLIT ? nt_all * (chunk + 1) / nsplit : nt_all;
+    const W1Range tr = w1_split_range(S, chunk, nsplit, SPLIT);      // this workgroup's query tiles: [tb, nt)
+    const int tb = tr.tb, nt = tr.nt;
 
     // the pipeline's first transposed reads hit the slot "before" tile tb (ring slot 3, both tiles): make it finite
+    // (w1_zero_slot, and w1_prime below -- inline here: through the attn_w1.h helper hipcc allocates this kernel's registers differently)
     {
         const u32x4_t z = {0u, 0u, 0u, 0u};
 #pragma unroll
@@ -505,8 +413,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* _
     const W1Rsrc dors = w1_rsrc(dOb, ((uint32_t)(S - 1) * sdo.s + (uint32_t)HD) * 2u);
     const W1Rsrc strs = w1_rsrc(STATS + (int64_t)bh * 2 * S, (uint32_t)(2 * S) * 4u);
     uint32_t qvo[2], dvo[2];
-    w1_dma_offsets<2>(wave, lane, sq.s, qvo);
-    w1_dma_offsets<2>(wave, lane, sdo.s, dvo);
+    w1_dma_offsets<HD>(wave, lane, sq.s, qvo);
+    w1_dma_offsets<HD>(wave, lane, sdo.s, dvo);
     const uint32_t qstep = __builtin_amdgcn_readfirstlane(64u * sq.s * 2u), dstep = __builtin_amdgcn_readfirstlane(64u * sdo.s * 2u);
     const uint32_t lds0 = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) uint8_t*)lds;
     const uint32_t wbase = __builtin_amdgcn_readfirstlane(lds0 + (uint32_t)wave * 2048u);
@@ -528,11 +436,10 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* _
         svo += 256u;
     }
 
-    const W1Lane la = w1_lane_offsets(lane);
-    const u32x8_t la8 = {la.row[0], la.row[1], la.row[2], la.row[3], la.tr[0][0], la.tr[0][1], la.tr[1][0], la.tr[1][1]};
+    const u32x8_t la8 = w1_read_offsets<HD>(lane);
     const uint32_t sread = lds0 + (uint32_t)W1_RING_BYTES + 16u * (uint32_t)hi;
-    const u32x16_t kf0 = pack4(kf[0][0], kf[0][1], kf[0][2], kf[0][3]), kf1 = pack4(kf[1][0], kf[1][1], kf[1][2], kf[1][3]);
-    const u32x16_t vf0 = pack4(vf[0][0], vf[0][1], vf[0][2], vf[0][3]), vf1 = pack4(vf[1][0], vf[1][1], vf[1][2], vf[1][3]);
+    const u32x16_t kf0 = w1_pack4(kf[0][0], kf[0][1], kf[0][2], kf[0][3]), kf1 = w1_pack4(kf[1][0], kf[1][1], kf[1][2], kf[1][3]);
+    const u32x16_t vf0 = w1_pack4(vf[0][0], vf[0][1], vf[0][2], vf[0][3]), vf1 = w1_pack4(vf[1][0], vf[1][1], vf[1][2], vf[1][3]);
     const uint32_t niter = (uint32_t)(nt - tb + 1);   // one extra tile step drains the pipeline
     f32x16_t dk[KB][2], dv[KB][2];
     uint32_t t0, t1;
@@ -555,15 +462,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* _
 #pragma unroll
         for (int j = 0; j < KB; ++j) {
             const int r = wave * (32 * KB) + 32 * j + (lane & 31);
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int g = 0; g < 4; ++g) {
-                    const f32x4_t wk = {dk[j][db][4 * g], dk[j][db][4 * g + 1], dk[j][db][4 * g + 2], dk[j][db][4 * g + 3]};
-                    const f32x4_t wv = {dv[j][db][4 * g], dv[j][db][4 * g + 1], dv[j][db][4 * g + 2], dv[j][db][4 * g + 3]};
-                    *reinterpret_cast<f32x4_t*>(pb + r * HD + db * 32 + 8 * g + 4 * hi) = wk;
-                    *reinterpret_cast<f32x4_t*>(pb + 256 * HD + r * HD + db * 32 + 8 * g + 4 * hi) = wv;
-                }
+            w1_store_part_row(pb, r, dk[j], hi);
+            w1_store_part_row(pb + 256 * HD, r, dv[j], hi);
         }
         return;
     }
@@ -571,24 +471,8 @@ __global__ __launch_bounds__(256, 1) void attn_bwd_dkv_w1_kernel(const bf16_t* _
     for (int j = 0; j < KB; ++j) {
         const int k = k0 + 32 * j + (lane & 31);
         if (k < S) {
-            bf16_t* kp = dK + ((size_t)b * sdk.b + (size_t)h * sdk.h + (size_t)k * sdk.s);
-            bf16_t* vp = dV + ((size_t)b * sdv.b + (size_t)h * sdv.h + (size_t)k * sdv.s);
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int gp = 0; gp < 2; ++gp) {          // 16-byte stores: common.h pair_rows8
-                    u32x2_t wk[2], wv[2];
-#pragma unroll
-                    for (int e = 0; e < 2; ++e) {
-                        const int g = 2 * gp + e;
-                        wk[e][0] = pack_bf16x2(dk[j][db][4 * g] * kscale, dk[j][db][4 * g + 1] * kscale);
-                        wk[e][1] = pack_bf16x2(dk[j][db][4 * g + 2] * kscale, dk[j][db][4 * g + 3] * kscale);
-                        wv[e][0] = pack_bf16x2(dv[j][db][4 * g], dv[j][db][4 * g + 1]);
-                        wv[e][1] = pack_bf16x2(dv[j][db][4 * g + 2], dv[j][db][4 * g + 3]);
-                    }
-                    *reinterpret_cast<u32x4_t*>(kp + db * 32 + 8 * (2 * gp + hi)) = pair_rows8(wk[0], wk[1]);
-                    *reinterpret_cast<u32x4_t*>(vp + db * 32 + 8 * (2 * gp + hi)) = pair_rows8(wv[0], wv[1]);
-                }
+            w1_store_bf16_row(dK + ((size_t)b * sdk.b + (size_t)h * sdk.h + (size_t)k * sdk.s), dk[j], kscale, hi);
+            w1_store_bf16_row(dV + ((size_t)b * sdv.b + (size_t)h * sdv.h + (size_t)k * sdv.s), dv[j], 1.f, hi);
         }
     }
 }
@@ -703,13 +587,11 @@ int32_t vgpa_attn_bwd_dq_w1(const void* q, const void* k, const void* v, const v
         !view_ok(dq_strides, B, H, S, HD) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dq) || (workspace && !al16(workspace)))
         return VGPA_ERR_INVALID;
     const int rows = 256;
-    const int n_t = (int)((S + rows - 1) / rows);
-    const int64_t tasks = (int64_t)n_t * B * H;
-    if (tasks > 0x7fffffff) return VGPA_ERR_INVALID;
-    TailSplit p;
-    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), W1_DQ_PART_FLOATS * sizeof(float), workspace,
-                                       ws_bytes, 0, &p);
+    W1Plan pl;
+    const int32_t rc = plan_w1(B, H, S, split_mode, W1_MAX_SPLIT, w1_slots(), W1_DQ_PART_FLOATS * sizeof(float), workspace, ws_bytes, 0, &pl);
     if (rc) return rc;
+    const int n_t = pl.n_t;
+    const TailSplit& p = pl.p;
     if (p.n_main > 0) {
         VGPA_LAUNCH((attn_bwd_dq_w1_kernel<false>), dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k,
                     (const bf16_t*)v, (const bf16_t*)d_o, lse2, delta, (bf16_t*)dq, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides),
@@ -757,14 +639,12 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
         !view_ok(dk_strides, B, H, S, HD) || !view_ok(dv_strides, B, H, S, HD) || !al16(q) || !al16(k) || !al16(v) || !al16(d_o) || !al16(dk) ||
         !al16(dv) || (workspace && !al16(workspace)))
         return VGPA_ERR_INVALID;
-    const int n_t = (int)((S + 255) / 256);
-    const int64_t tasks = (int64_t)n_t * B * H;
-    if (tasks > 0x7fffffff) return VGPA_ERR_INVALID;
     const float kscale = 0.6931471805599453f;   // q arrives pre-scaled by scale * log2(e): dK = ln 2 * (dS^T Q)
-    TailSplit p;
-    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), W1_DKV_PART_FLOATS * sizeof(float), workspace,
-                                       ws_bytes, 0, &p);
+    W1Plan pl;
+    const int32_t rc = plan_w1(B, H, S, split_mode, W1_MAX_SPLIT, w1_slots(), W1_DKV_PART_FLOATS * sizeof(float), workspace, ws_bytes, 0, &pl);
     if (rc) return rc;
+    const int n_t = pl.n_t;
+    const TailSplit& p = pl.p;
     if (p.n_main > 0) {
         VGPA_LAUNCH((attn_bwd_dkv_w1_kernel<false>), dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
                     (const bf16_t*)d_o, stats, (bf16_t*)dk, (bf16_t*)dv, mk(q_strides), mk(k_strides), mk(v_strides), mk(do_strides), mk(dk_strides),
@@ -787,10 +667,11 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
 // The forward: o = softmax(q k^T) v (bf16), lse2 = log2 sum_k exp2(q.k) per row (fp32 [B,H,S]).  split_mode as in vgpa_attn_bwd_dq_w1, along the
 // keys.  The workspace (>= vgpa_attn_fwd_w1_workspace_bytes) is REQUIRED: it holds max_k |k|^2 per (batch, head), one redo flag per 256-row
 // strip and the tail-split partials.
+// its head: one kmax word per (batch, head) and one flag word per task, rounded up to 256 bytes
+static inline size_t fwd_w1_ws_head(int64_t B, int64_t H, int64_t tasks) { return (((size_t)(B * H) + (size_t)tasks) * 4 + 255) / 256 * 256; }
 size_t vgpa_attn_fwd_w1_workspace_bytes(int64_t B, int64_t H, int64_t S) {
-    const int64_t n_qt = (S + 255) / 256, tasks = n_qt * B * H;
-    const size_t head = (((size_t)(B * H) + (size_t)tasks) * 4 + 255) / 256 * 256;
-    return head + (size_t)max_split_parts(tasks, W1_MAX_SPLIT, w1_slots()) * W1_FWD_PART_FLOATS * sizeof(float);
+    const int64_t tasks = (S + 255) / 256 * B * H;
+    return fwd_w1_ws_head(B, H, tasks) + (size_t)max_split_parts(tasks, W1_MAX_SPLIT, w1_slots()) * W1_FWD_PART_FLOATS * sizeof(float);
 }
 // The forward can also leave what the bf16 rounding of the output dropped, for the backward's delta (vgpa_attn_bwd_prep_w1_res /
 // vgpa_attn_bwd_delta_res): o_res = a [B,H,S,64] view with its own element strides (NULL: not written) of
@@ -808,11 +689,17 @@ static int32_t fwd_w1_impl(const void* q, const void* k, const void* v, void* o,
     void* ores = o_res;
     const int rk = o_res ? (int)res_kind : VGPA_RES_NONE;
     const TStride sor = o_res ? mk(ores_strides) : mk(o_strides);
-    const int n_qt = (int)((S + 255) / 256);
-    const int64_t tasks = (int64_t)n_qt * B * H;
-    if (tasks > 0x7fffffff || B * H > 65535) return VGPA_ERR_INVALID;
-    const size_t head = (((size_t)(B * H) + (size_t)tasks) * 4 + 255) / 256 * 256;
+    if (B * H > 65535) return VGPA_ERR_INVALID;
+    // The workspace is mandatory here: always planned.  The all-online call never splits (split_mode 0), so a workspace too short for a forced split
+    // is no error there; a workspace shorter than its head is VGPA_ERR_WORKSPACE from the plan (forced split) or from the check below -- the same code.
+    const size_t head = fwd_w1_ws_head(B, H, (S + 255) / 256 * B * H);
+    W1Plan pl;
+    const int32_t rc = plan_w1(B, H, S, force_online ? 0 : split_mode, W1_MAX_SPLIT, w1_slots(), W1_FWD_PART_FLOATS * sizeof(float), workspace, ws_bytes, head, &pl);
+    if (rc) return rc;
     if (ws_bytes < head) return VGPA_ERR_WORKSPACE;
+    const int n_qt = pl.n_t;
+    const int64_t tasks = pl.tasks;
+    const TailSplit& p = pl.p;
     unsigned* kmax2 = (unsigned*)workspace;
     int* flags = (int*)workspace + B * H;
     float* part = (float*)((char*)workspace + head);
@@ -822,12 +709,8 @@ static int32_t fwd_w1_impl(const void* q, const void* k, const void* v, void* o,
                                            flags, stream, ores, sor, rk);
     }
     if (hipMemsetAsync(workspace, 0, head, stream) != hipSuccess) return VGPA_ERR_LAUNCH;
-    VGPA_LAUNCH(w1_kmax_kernel, dim3(16, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)k, mk(k_strides), (int)S, (int)H, kmax2);
+    VGPA_LAUNCH((w1_kmax_kernel<HD / 8>), dim3(16, (unsigned)(B * H)), dim3(256), 0, stream, (const bf16_t*)k, mk(k_strides), (int)S, (int)H, kmax2);
     VGPA_CHECK_LAUNCH();
-    TailSplit p;   // the workspace is mandatory here: always planned
-    const int32_t rc = plan_tail_split(tasks, (int)((S + TILE - 1) / TILE), split_mode, W1_MAX_SPLIT, w1_slots(), W1_FWD_PART_FLOATS * sizeof(float),
-                                       workspace, ws_bytes, head, &p);
-    if (rc) return rc;
     if (p.n_main > 0) {
         VGPA_LAUNCH((attn_fwd_w1_kernel<false>), dim3((unsigned)p.n_main), dim3(256), 0, stream, (const bf16_t*)q, (const bf16_t*)k, (const bf16_t*)v,
                     (bf16_t*)o, lse2, (const unsigned*)kmax2, flags, mk(q_strides), mk(k_strides), mk(v_strides), mk(o_strides), (int)S, (int)H, n_qt, 0, 1,

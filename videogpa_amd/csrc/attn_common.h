@@ -112,6 +112,17 @@ static inline int32_t plan_tail_split(int64_t tasks, int key_tiles, int split_mo
     return VGPA_OK;
 }
 
+// The plan of a head_dim-64 w1 operation over [B, H, S]: one task per 256 rows of a (batch, head), each sweeping the S / TILE streamed tiles, the
+// tasks of a mostly empty last round tail-split (plan_tail_split).  More than 2^31 - 1 tasks: VGPA_ERR_INVALID, before any workspace check.
+struct W1Plan { int n_t; int64_t tasks; TailSplit p; };
+static inline int32_t plan_w1(int64_t B, int64_t H, int64_t S, int split_mode, int max_split, int64_t slots, size_t part_bytes, const void* workspace,
+                              size_t ws_bytes, size_t ws_head, W1Plan* out) {
+    out->n_t = (int)((S + 255) / 256);
+    out->tasks = (int64_t)out->n_t * B * H;
+    if (out->tasks > 0x7fffffff) return VGPA_ERR_INVALID;
+    return plan_tail_split(out->tasks, (int)((S + TILE - 1) / TILE), split_mode, max_split, slots, part_bytes, workspace, ws_bytes, ws_head, &out->p);
+}
+
 // attention.hip: the online-softmax forward over the flagged 256-row strips only (redo pass of the w1 forward)
 int32_t vgpa_internal_attn_fwd_redo(const void* q, const void* k, const void* v, void* o, float* lse2, TStride sq, TStride sk, TStride sv, TStride so,
                                     int S, int H, int n_qt, int64_t tasks, const int* flags, hipStream_t stream, void* o_res = nullptr, TStride sor = TStride{0, 0, 0},

@@ -411,6 +411,25 @@ int32_t vgpa_dino_embed(const void* images, int32_t in_dtype, const float* w_pac
 int32_t vgpa_stream_ln_f32(const float* x, const void* y, const float* gamma, const float* ln_w, const float* ln_b, float* x_new, void* n,
                            int32_t n_dtype, int64_t M, int64_t D, float eps, vgpa_stream_t stream);
 
+/* ---- LPIPS-VGG around the convolutions (lpips 0.1, lpips/lpips.py; csrc/lpips.hip): fp32, NHWC, forward only, 16-byte aligned bases ----
+ * ScalingLayer + layout change in front of conv1_1: x [N,3,H,W] NCHW in [-1,1] -> out [N,H,W,16], channels 0..2 = (x - shift_c) / scale_c
+ * (a true division), channels 3..15 = 0, so that conv1_1 runs on vgpa_conv3x3_f32 with a [3][3][16][64] weight whose rows 3..15 are zero.
+ * flags bit0: x is in [0,1] and is mapped to 2 x - 1 first (upstream's normalize=True).  x is read one float at a time, so any float-aligned base
+ * (a frame slice of a batch of odd-sized frames) is valid; out is 16-byte aligned. */
+int32_t vgpa_lpips_input_f32(const float* x, float* out, int64_t N, int64_t H, int64_t W, float shift0, float shift1, float shift2,
+                             float scale0, float scale1, float scale2, int32_t flags, vgpa_stream_t stream);
+/* 2 x 2 max pool, stride 2, floor: x [N,H,W,C] -> out [N,H/2,W/2,C]; C a multiple of 4, H and W >= 2.  flags bit0: relu(x) is pooled. */
+int32_t vgpa_maxpool2x2_f32(const float* x, float* out, int64_t N, int64_t H, int64_t W, int64_t C, int32_t flags, vgpa_stream_t stream);
+/* One LPIPS layer: f0, f1 [N,H,W,C] (C a multiple of 4, <= 512), w [C] (the `lin` 1x1 convolution, no bias);
+ *   value[n] = mean over the H W pixels of  sum_c w_c (f0_c / (||f0||_2 + 1e-10) - f1_c / (||f1||_2 + 1e-10))^2
+ * (normalize_tensor, lin, spatial_average).  out fp32 [N] and / or total fp64 [N] (either may be NULL) receive it.
+ * flags bit0: ReLU on both maps as they are loaded; bit1: total[n] += value instead of total[n] = value.
+ * Fixed-order fp64 reduction, no float atomics: bit-identical from run to run, and a frame's value does not depend on N.
+ * An all-zero pixel contributes exactly 0. */
+size_t vgpa_lpips_layer_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t C);
+int32_t vgpa_lpips_layer_f32(const float* f0, const float* f1, const float* w, float* out, double* total, int64_t N, int64_t H, int64_t W,
+                             int64_t C, int32_t flags, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

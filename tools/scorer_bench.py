@@ -1,6 +1,6 @@
 """The geometry scorer at the reference's scale (10 views x 518 x 518, a cloud of 10 * 518 * 518 points: train/01_preference_pair.py:33-34, utils/projection_utils.py):
 the SAME measurement bench.py attaches as its `scorer` block (bench.scorer_report: ms per video, point-views / s, algorithmic GB/s against the 8 TB/s peak, atomics / s,
-the reference's argsort + scatter formulation on this GPU, the CPU oracle), plus the kernels that block does not touch (confidence cut, MVCS, 8-point + Sampson, SSIM, the VGGT heads, the DINOv2 patch embedding) so that
+the reference's argsort + scatter formulation on this GPU, the CPU oracle), plus the kernels that block does not touch (confidence cut, MVCS, 8-point + Sampson, SSIM, the VGGT heads, the DINOv2 patch embedding, LPIPS-VGG) so that
 a rocprofv3 pass over this script (tools/profile_round.sh) sees every scorer kernel.
     python tools/scorer_bench.py [--quick] [--json gpurun_out/scorer_bench.json]      # --quick: two launches of everything, no timing loops (PMC passes)"""
 import argparse
@@ -162,6 +162,10 @@ out["vggt_heads"] = heads
 # The DINOv2 patch embedding (csrc/dino_embed.hip, vggt.DinoVisionTransformer) and VGGT end to end at the same scale: tools/dinov2_bench.py
 import dinov2_bench  # noqa: E402
 out["vggt_dinov2"] = dinov2_bench.run(dev, a.quick)
+
+# LPIPS-VGG (csrc/lpips.hip, videogpa_amd.lpips.LPIPS) at 10 + 10 frames of 518 x 518, per convolution shape and per layer kernel: tools/lpips_bench.py
+import lpips_bench  # noqa: E402
+out["lpips"] = lpips_bench.run(dev, a.quick)
 if not a.quick:
     os.makedirs(os.path.dirname(a.json), exist_ok=True)
     with open(a.json, "w") as f:

@@ -95,6 +95,10 @@ SIGNATURES = {
     "vgpa_attn_small_f32": (I32, [P, P, P, I64, I64, I64, P, I64, I64, I64, I64, F32, P]),
     "vgpa_dino_embed": (I32, [P, I32, P, I64, P, P, P, P, P, I32, I64, I64, I64, I64, I64, I64, P]),
     "vgpa_stream_ln_f32": (I32, [P, P, P, P, P, P, P, I32, I64, I64, F32, P]),
+    "vgpa_lpips_input_f32": (I32, [P, P, I64, I64, I64, F32, F32, F32, F32, F32, F32, I32, P]),
+    "vgpa_maxpool2x2_f32": (I32, [P, P, I64, I64, I64, I64, I32, P]),
+    "vgpa_lpips_layer_workspace_bytes": (SZ, [I64, I64, I64, I64]),
+    "vgpa_lpips_layer_f32": (I32, [P, P, P, P, P, I64, I64, I64, I64, I32, P, SZ, P]),
 }
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library

@@ -1477,3 +1477,60 @@ def stream_ln(x, y=None, gamma=None, ln_w=None, ln_b=None, eps=1e-6, n_dtype=tor
     _timed("stream_ln_f32", nbytes * M * D,
            lambda: _lib.call("vgpa_stream_ln_f32", x, y, gamma, ln_w, ln_b, x_new, n, _DT[n_dtype], M, D, float(eps), _stream()), "byte")
     return x_new, n
+
+
+# ---- LPIPS-VGG around the convolutions (csrc/lpips.hip): fp32, channels-last, forward only ------------------------------------------------
+LPIPS_SHIFT = (-.030, -.088, -.188)     # lpips.ScalingLayer's buffers
+LPIPS_SCALE = (.458, .448, .450)
+
+
+def lpips_input_f32(x, shift=LPIPS_SHIFT, scale=LPIPS_SCALE, normalize=False, out=None):
+    """ScalingLayer + layout change: x [N,3,H,W] in [-1,1] ([0,1] with `normalize`) -> [N,H,W,16], channels 0..2 = (x - shift) / scale, the rest 0.
+    `out`: a contiguous [N,H,W,16] view to write into (the two halves of one batch)."""
+    _heads_in(x, out)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError(f"lpips_input_f32: expected [N,3,H,W], got {tuple(x.shape)}")
+    N, _, H, W = x.shape
+    if out is None:
+        out = torch.empty(N, H, W, 16, device=x.device, dtype=torch.float32)
+    elif tuple(out.shape) != (N, H, W, 16):
+        raise RuntimeError("lpips_input_f32: `out` must be [N,H,W,16]")
+    _timed("lpips_input_f32", 4.0 * (x.numel() + out.numel()),
+           lambda: _lib.call("vgpa_lpips_input_f32", x, out, N, H, W, *[float(v) for v in shift], *[float(v) for v in scale], 1 if normalize else 0,
+                             _stream()), "byte")
+    return out
+
+
+def maxpool2x2_f32(x, relu=False):
+    """F.max_pool2d(relu?(x), 2, 2) of x [N,H,W,C] -> [N,H//2,W//2,C]"""
+    _heads_in(x)
+    N, H, W, C = x.shape
+    if H < 2 or W < 2 or C % 4:
+        raise RuntimeError(f"maxpool2x2_f32: needs H, W >= 2 and channels in multiples of 4, got {tuple(x.shape)}")
+    out = torch.empty(N, H // 2, W // 2, C, device=x.device, dtype=torch.float32)
+    _timed("maxpool2x2_f32", 4.0 * (4 * out.numel() + out.numel()),
+           lambda: _lib.call("vgpa_maxpool2x2_f32", x, out, N, H, W, C, 1 if relu else 0, _stream()), "byte")
+    return out
+
+
+def lpips_layer_f32(f0, f1, w, relu=False, total=None, accumulate=False, out=None):
+    """One LPIPS layer of f0, f1 [N,H,W,C] with the lin weight w [C]: the spatial mean of sum_c w_c (f0_c / (|f0| + 1e-10) - f1_c / (|f1| + 1e-10))^2
+    -> fp32 [N] (written into `out` when given).  `total` (fp64 [N]) receives the unrounded value too, added to what it holds with `accumulate`."""
+    _heads_in(f0, f1, w, out)
+    N, H, W, C = f0.shape
+    if f1.shape != f0.shape or w.numel() != C or C % 4 or C > 512:
+        raise RuntimeError(f"lpips_layer_f32: maps {tuple(f0.shape)} / {tuple(f1.shape)} and weight {tuple(w.shape)} do not fit (C % 4 == 0, C <= 512)")
+    if total is not None:
+        _req(total, torch.float64)
+        if total.numel() != N:
+            raise RuntimeError("lpips_layer_f32: `total` must hold N values")
+    if out is None:
+        out = torch.empty(N, device=f0.device, dtype=torch.float32)
+    elif out.numel() != N:
+        raise RuntimeError("lpips_layer_f32: `out` must hold N values")
+    ws_bytes = _lib.query("vgpa_lpips_layer_workspace_bytes", N, H, W, C)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=f0.device)
+    _timed("lpips_layer_f32", 2.0 * f0.numel() * 4,
+           lambda: _lib.call("vgpa_lpips_layer_f32", f0, f1, w, out, total, N, H, W, C, (1 if relu else 0) | (2 if accumulate else 0), ws, ws_bytes,
+                             _stream()), "byte")
+    return out

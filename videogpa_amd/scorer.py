@@ -278,9 +278,11 @@ def frames_to_pm1(x, size=None):
 
 
 class LPIPSMetric(Metric):
-    """Video-level LPIPS (metrics/lpips.py:7-36).  The perceptual network (`lpips.LPIPS(net='vgg')` upstream) is third-party: it is
-    passed in, exactly as the reference's own drivers pass it (`LPIPSMetric(device=..., lpips_net=net)`, replicate_scorer.py:63-74);
-    the input normalisation / layout / resize in front of it runs on the device."""
+    """Video-level LPIPS (metrics/lpips.py:7-36).  The perceptual network is passed in, exactly as the reference's own drivers pass it
+    (`LPIPSMetric(device=..., lpips_net=net)`, replicate_scorer.py:63-74): `videogpa_amd.lpips.LPIPS(net='vgg', ...)` runs it on the
+    device (csrc/lpips.hip + the fp32 MFMA convolution); upstream's `lpips.LPIPS(net='vgg')` is accepted as well.  Only the trained
+    weights stay third-party: they are not bundled and never fetched, so without a net `compute` can only raise.  The input
+    normalisation / layout / resize in front of the network runs on the device."""
 
     def __init__(self, device=None, lpips_net=None):
         super().__init__(name="lpips")
@@ -289,7 +291,8 @@ class LPIPSMetric(Metric):
 
     def compute(self, *, gt, rep, **kwargs) -> float:
         if self.lpips is None:
-            raise RuntimeError("LPIPSMetric: the LPIPS-VGG weights are third-party and not bundled; pass lpips_net=lpips.LPIPS(net='vgg')")
+            raise RuntimeError("LPIPSMetric: the LPIPS-VGG weights are third-party and not bundled; pass lpips_net=videogpa_amd.lpips.LPIPS(net='vgg', "
+                               "model_path=..., vgg_path=...) (the network on the device, from local weight files) or upstream's lpips.LPIPS(net='vgg')")
         gt_t = frames_to_pm1(gt)
         rep_t = frames_to_pm1(rep, size=tuple(gt_t.shape[-2:]))
         with torch.no_grad():
@@ -298,8 +301,8 @@ class LPIPSMetric(Metric):
 
 
 class Consistency_Score(Metric):
-    """MSE + ratio * LPIPS, motion score returned separately (metrics/consistency_score.py:43-72).  `lpips_net` is the caller's
-    perceptual network, wrapped in LPIPSMetric like the reference does (:54-58)."""
+    """MSE + ratio * LPIPS, motion score returned separately (metrics/consistency_score.py:43-72).  `lpips_net` is the
+    perceptual network (`videogpa_amd.lpips.LPIPS` on the device, or upstream's), wrapped in LPIPSMetric like the reference does (:54-58)."""
 
     def __init__(self, lpips_net=None, device="cuda"):
         super().__init__("Consistency_Score")

@@ -430,6 +430,35 @@ size_t vgpa_lpips_layer_workspace_bytes(int64_t N, int64_t H, int64_t W, int64_t
 int32_t vgpa_lpips_layer_f32(const float* f0, const float* f1, const float* w, float* out, double* total, int64_t N, int64_t H, int64_t W,
                              int64_t C, int32_t flags, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
 
+/* ---- Depth Anything 3's DINOv2 backbone between its blocks, and its camera decoding (csrc/da3.hip): fp32, forward only, 16-byte aligned bases ----
+ * Tokens are x fp32 [B,S,N,C] (S views of N tokens, token 0 the class / camera token).  The reference view of a batch element lives in a DEVICE
+ * int32 [B] buffer that the selection writes and the other entry points read; no entry point needs it on the host.
+ *
+ * select_reference_view, depth_anything_3/model/reference_view_selector.py:29-112, on token 0 of every view.  strategy 0 "first", 1 "middle" (S / 2),
+ * 2 "saddle_balanced", 3 "saddle_sim_range"; S <= 64.  metrics fp64 [B,S,4] (may be NULL) receives per view: the mean off-diagonal cosine similarity,
+ * the token's norm, the unbiased variance of the normalised token, and the score the strategy ranks by (the balance score sum |minmax(m) - 0.5|; for
+ * strategy 3 the range of the view's similarity row).  Reductions run in fp64 in a fixed order; a tie resolves to the lowest index; S == 1 gives 0. */
+int32_t vgpa_da3_ref_view(const float* x, int64_t B, int64_t S, int64_t N, int64_t C, int32_t strategy, double* metrics, int32_t* ref_idx,
+                          vgpa_stream_t stream);
+/* reorder_by_reference / restore_original_order, reference_view_selector.py:115-222, over whole [N][C] slabs: inverse == 0 writes
+ * out[b, j] = in[b, order_j], order = [ref, 0, .., ref-1, ref+1, ..]; inverse != 0 undoes it.  A second tensor (b_in, b_out; both NULL for none) rides
+ * in the same launch.  Never in place: an output that aliases an input is an invalid argument.  N * C a multiple of 4. */
+int32_t vgpa_da3_view_gather(const float* a_in, float* a_out, const float* b_in, float* b_out, const int32_t* ref_idx, int32_t inverse, int64_t B,
+                             int64_t S, int64_t N, int64_t C, vgpa_stream_t stream);
+/* x[b, s, 0, :] = cam (vision_transformer.py:323-331), in place: per_view != 0 reads cam [B,S,C] (the caller's tokens), per_view == 0 reads the
+ * camera_token parameter [2,C]: row 0 for view 0, row 1 for every other view.  No other row of x is touched. */
+int32_t vgpa_da3_cam_token(float* x, const float* cam, int32_t per_view, int64_t B, int64_t S, int64_t N, int64_t C, vgpa_stream_t stream);
+/* One out layer (vision_transformer.py:341-346,382-398 with cat_token) in one launch: feats [B,S,N-1,2C] = [local_x | LayerNorm(x) * ln_w + ln_b] of
+ * tokens 1.., cam [B,S,2C] = [local_x | x] of token 0, un-normalised.  The local half and the camera row are bit-exact copies.  ref_idx != NULL
+ * restores the original view order (output view t reads reordered position inverse_t); NULL reads views as they are.  C a multiple of 4;
+ * feats may be NULL when N == 1. */
+int32_t vgpa_da3_tap(const float* local_x, const float* x, const float* ln_w, const float* ln_b, float eps, const int32_t* ref_idx, float* feats,
+                     float* cam, int64_t B, int64_t S, int64_t N, int64_t C, vgpa_stream_t stream);
+/* DepthAnything3Net._process_camera_estimation, depth_anything_3/model/da3.py:209-221: pose_enc fp32 [n,9] (translation, scalar-last quaternion,
+ * fov_h, fov_w; camera-to-world) -> ext fp32 [n,3,4] = its inverse [R^T | -R^T T] (world-to-camera), intr fp32 [n,3,3] with focal =
+ * (size / 2) / max(tan(fov / 2), 1e-6) and the principal point at the image centre. */
+int32_t vgpa_da3_pose_decode(const float* pose_enc, int64_t n, float image_h, float image_w, float* ext, float* intr, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,228 @@
+"""Depth Anything 3's backbone and camera decoder on the HIP kernels: what `DepthAnything3Net` (depth_anything_3/model/da3.py) runs up to `extrinsics` /
+`intrinsics`.  Mirrors the reference-held modules so that a DA3 checkpoint loads by name:
+
+    DinoVisionTransformer   depth_anything_3/model/dinov2/vision_transformer.py:83-398  (DINOv2 with alternating local / global attention from `alt_start`,
+                                                                QK-norm from `qknorm_start`, 2-D RoPE from `rope_start`, reference-view selection, camera
+                                                                tokens, concatenated taps)
+    DinoV2                  depth_anything_3/model/dinov2/dinov2.py:22-64               (the network under `.pretrained`; "vits" | "vitb" | "vitl")
+    CameraDec               depth_anything_3/model/cam_dec.py:19-45
+    decode_cameras          da3.py:209-221, model/utils/transform.py:41-65, utils/geometry.py:55-59
+    DA3Cameras              backbone + camera decoder of a DepthAnything3Net state dict; the DualDPT depth head (`depth` / `conf`) is not built here
+
+Precision is that of vggt.DinoVisionTransformer, which this backbone extends: an fp32 residual stream (csrc/dino_stream.hip), bf16 GEMM and attention
+operands, fp32 outputs -- the bf16-autocast evaluation upstream uses; bf16 parameters, or fp32 parameters under torch.autocast(dtype=torch.bfloat16).
+Blocks without QK-norm are vggt.DinoBlock itself; blocks with it put ops.qknorm_attention (QK-norm + RoPE + flash attention) on the same stream.  What
+sits between the blocks is csrc/da3.hip: the selected view stays in a device buffer from the selection to the last tap.  Forward only."""
+import functools
+import itertools
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import ops
+from . import vggt
+from .transformer import _f32
+
+THRESH_FOR_REF_SELECTION = 3          # depth_anything_3/utils/constants.py:19
+
+
+class DA3Attention(vggt.DinoAttention):
+    """depth_anything_3/model/dinov2/layers/attention.py:18-81: DinoAttention's parameters plus LayerNorm(head_dim) on q and k where `qk_norm`"""
+
+    def __init__(self, dim, num_heads=8, qkv_bias=True, proj_bias=True, qk_norm=False, rope=None):
+        super().__init__(dim, num_heads=num_heads, qkv_bias=qkv_bias, proj_bias=proj_bias)
+        if rope is not None and not qk_norm:
+            raise NotImplementedError("RoPE without QK-norm (rope_start < qknorm_start): no DA3 configuration builds it")
+        self.q_norm = nn.LayerNorm(self.head_dim) if qk_norm else nn.Identity()
+        self.k_norm = nn.LayerNorm(self.head_dim) if qk_norm else nn.Identity()
+        self.qk_norm, self.rope = qk_norm, rope
+
+
+class DA3Block(vggt.DinoBlock):
+    """depth_anything_3/model/dinov2/layers/block.py:26-103 on vggt.DinoBlock's fp32 stream.  Without QK-norm it IS that block; with it the attention is
+    ops.qknorm_attention on the qkv GEMM's output: stream_ln (norm1) -> qkv -> QK-norm + RoPE + attention -> proj -> stream_ln (ls1.gamma, norm2) ->
+    fc1, GELU, fc2 -> stream_ln (ls2.gamma)."""
+
+    def __init__(self, dim, num_heads, qk_norm=False, rope=None, **kwargs):
+        super().__init__(dim, num_heads, attn_class=functools.partial(DA3Attention, qk_norm=qk_norm, rope=rope), **kwargs)
+
+    def forward(self, x, rope=None):
+        """x fp32 [B,N,C]; rope = (cos, sin) fp32 [N,64] for the blocks that rotate -> fp32 [B,N,C]"""
+        at = self.attn
+        if not at.qk_norm:
+            return super().forward(x)
+        _, n1 = ops.stream_ln(x, None, None, _f32(self.norm1.weight), _f32(self.norm1.bias), self.norm1.eps)
+        o = ops.qknorm_attention(at.qkv(n1).contiguous(), _f32(at.q_norm.weight), _f32(at.q_norm.bias), _f32(at.k_norm.weight), _f32(at.k_norm.bias),
+                                 at.num_heads, text_len=0, rope=rope if at.rope is not None else None, eps=at.q_norm.eps, rope_mode=1, precise_delta=None)
+        x, n2 = ops.stream_ln(x, at.proj(o).contiguous(), _f32(self.ls1.gamma), _f32(self.norm2.weight), _f32(self.norm2.bias), self.norm2.eps)
+        return ops.stream_ln(x, self.mlp(n2).contiguous(), _f32(self.ls2.gamma))[0]
+
+
+class DinoVisionTransformer(vggt.DinoVisionTransformer):
+    """depth_anything_3/model/dinov2/vision_transformer.py:83-398 with ffn_layer="mlp": token embedding, position table and the blocks' stream are the
+    parent's (one fused embed launch, interpolate_offset 0.1, no antialias, no register tokens); this class adds the block schedule and the taps.
+
+    get_intermediate_layers(x [B,S,3,H,W], n, cam_token=None, ref_view_strategy="saddle_balanced") ->
+        (tuple of (features fp32 [B,S,P,2C], camera token fp32 [B,S,2C]) per layer in `n`, [])"""
+
+    def __init__(self, img_size=518, patch_size=14, embed_dim=1024, depth=24, num_heads=16, mlp_ratio=4.0, init_values=1.0, alt_start=-1, qknorm_start=-1,
+                 rope_start=-1, rope_freq=100, cat_token=True):
+        if not cat_token:
+            raise NotImplementedError("cat_token=False: every DA3 configuration concatenates the local and the global tokens")
+        rope = vggt.RotaryPositionEmbedding2D(frequency=rope_freq) if rope_start != -1 and rope_freq > 0 else None
+        index = itertools.count()
+
+        def block_fn(**kw):
+            i = next(index)
+            return DA3Block(qk_norm=qknorm_start != -1 and i >= qknorm_start, rope=rope if rope_start != -1 and i >= rope_start else None, **kw)
+        super().__init__(img_size=img_size, patch_size=patch_size, embed_dim=embed_dim, depth=depth, num_heads=num_heads, mlp_ratio=mlp_ratio,
+                         init_values=init_values, block_fn=block_fn, block_chunks=0, num_register_tokens=0, interpolate_antialias=False,
+                         interpolate_offset=0.1)
+        del self.mask_token                                    # DA3's DINOv2 carries none
+        self.norm = nn.LayerNorm(embed_dim)                    # eps 1e-5 here; the blocks' norms keep 1e-6
+        self.alt_start, self.qknorm_start, self.rope_start, self.cat_token, self.patch_start_idx = alt_start, qknorm_start, rope_start, cat_token, 1
+        if alt_start != -1:
+            self.camera_token = nn.Parameter(torch.randn(1, 2, embed_dim))
+        self.rope, self.ref_idx = rope, None
+        self._rope_tables = {}
+
+    def _prepare_rope(self, S, H, W, device):
+        """(local, global) cos / sin tables: local rows are one view's tokens (token 0 at (0, 0), the patch grid from (1, 1)); global rows are the S views
+        in a row, every patch at (1, 1) (`pos_nodiff`: token 0 still rotates differently from the patches)"""
+        if self.rope is None:
+            return None, None
+        key = (S, H // self.patch_size, W // self.patch_size, str(device))
+        if key not in self._rope_tables:
+            if len(self._rope_tables) > 16:
+                self._rope_tables.clear()
+            yy, xx = torch.meshgrid(torch.arange(key[1], device=device), torch.arange(key[2], device=device), indexing="ij")
+            pos = torch.cat([torch.zeros(1, 2, dtype=torch.long, device=device), torch.stack([yy.reshape(-1), xx.reshape(-1)], dim=-1) + 1])
+            nodiff = pos.clamp(max=1).repeat(S, 1)
+            self._rope_tables[key] = (self.rope.tables(pos, 64), self.rope.tables(nodiff, 64))
+        return self._rope_tables[key]
+
+    def get_intermediate_layers(self, x, n=1, export_feat_layers=(), cam_token=None, ref_view_strategy="saddle_balanced", attn_mask=None):
+        if export_feat_layers is not None and len(export_feat_layers):
+            raise NotImplementedError("export_feat_layers: auxiliary feature maps are not built (no VideoGPA path asks for them)")
+        if attn_mask is not None:
+            raise NotImplementedError("attn_mask is not supported by the HIP attention path")
+        if ref_view_strategy not in ops.DA3_REF_VIEW_STRATEGIES:
+            raise ValueError(f"Unknown reference view selection strategy: {ref_view_strategy}. Must be one of: "
+                             f"{', '.join(map(repr, ops.DA3_REF_VIEW_STRATEGIES))}")
+        B, S, _, H, W = x.shape
+        take = range(len(self.blocks) - n, len(self.blocks)) if isinstance(n, int) else n
+        t = self._tokens(x.reshape(B * S, *x.shape[2:]))
+        N, C = t.shape[1:]
+        t = t.view(B, S, N, C)
+        local_rope, global_rope = self._prepare_rope(S, H, W, x.device)
+        alt = self.alt_start
+        local, ref_idx, output = None, None, []
+        self.ref_idx = None                                    # the last forward's selection: a device int32 [B], or None when none was made
+        for i, blk in enumerate(self.blocks):
+            if alt != -1 and i == alt - 1 and S >= THRESH_FOR_REF_SELECTION and cam_token is None:
+                ref_idx = ops.da3_ref_view(t, ref_view_strategy)                     # stays on the device
+                self.ref_idx = ref_idx
+                t = ops.da3_view_gather(t, ref_idx)       # upstream reorders local_x too; block i is local and replaces it before any tap reads it
+            if alt != -1 and i == alt:                                               # in place, as upstream: `local` is this tensor when block i - 1 was local
+                if cam_token is not None:
+                    if tuple(cam_token.shape) != (B, S, C):
+                        raise ValueError(f"cam_token must be [B,S,C] = {(B, S, C)}, got {tuple(cam_token.shape)}")
+                    ops.da3_cam_token(t, cam_token.detach().float().contiguous(), per_view=True)
+                else:
+                    ops.da3_cam_token(t, _f32(self.camera_token), per_view=False)
+            if alt != -1 and i >= alt and i % 2 == 1:
+                t = blk(t.view(B, S * N, C), rope=global_rope).view(B, S, N, C)
+            else:
+                t = local = blk(t.view(B * S, N, C), rope=local_rope).view(B, S, N, C)
+            if i in take:
+                output.append(ops.da3_tap(local, t, _f32(self.norm.weight), _f32(self.norm.bias), self.norm.eps, ref_idx))
+        assert len(output) == len(take), f"only {len(output)} / {len(take)} blocks found"
+        return tuple(output), []
+
+
+_ENCODERS = {"vits": dict(embed_dim=384, depth=12, num_heads=6), "vitb": dict(embed_dim=768, depth=12, num_heads=12),
+             "vitl": dict(embed_dim=1024, depth=24, num_heads=16)}
+
+
+class DinoV2(nn.Module):
+    """depth_anything_3/model/dinov2/dinov2.py:22-64: `forward(x [B,S,3,H,W], cam_token=None, export_feat_layers=[], ref_view_strategy=...)` ->
+    (tuple of (features, camera token) per out layer, aux list).  `encoder_kwargs` override the named encoder's sizes (reduced configurations; a DA3
+    checkpoint needs none)."""
+
+    def __init__(self, name, out_layers, alt_start=-1, qknorm_start=-1, rope_start=-1, cat_token=True, encoder_kwargs=None):
+        super().__init__()
+        assert name in {"vits", "vitb", "vitl", "vitg"}
+        if name == "vitg":
+            raise NotImplementedError("vitg (DA3-Giant) uses the SwiGLU feed-forward, which is not built; vits / vitb / vitl are")
+        self.name, self.out_layers = name, list(out_layers)
+        self.alt_start, self.qknorm_start, self.rope_start, self.cat_token = alt_start, qknorm_start, rope_start, cat_token
+        self.pretrained = DinoVisionTransformer(**{**dict(img_size=518, patch_size=14, **_ENCODERS[name]), **(encoder_kwargs or {})}, alt_start=alt_start,
+                                                qknorm_start=qknorm_start, rope_start=rope_start, cat_token=cat_token)
+
+    def forward(self, x, cam_token=None, export_feat_layers=(), ref_view_strategy="saddle_balanced", attn_mask=None):
+        return self.pretrained.get_intermediate_layers(x, self.out_layers, export_feat_layers=export_feat_layers, cam_token=cam_token,
+                                                       ref_view_strategy=ref_view_strategy, attn_mask=attn_mask)
+
+
+class CameraDec(nn.Module):
+    """depth_anything_3/model/cam_dec.py:19-45: camera token [B,S,dim_in] -> pose encoding [B,S,9] = (translation, scalar-last quaternion, fov_h, fov_w).
+    A handful of rows: the Linear layers are torch, in fp32 whatever autocast or the parameters' dtype say (upstream runs this part with autocast off)."""
+
+    def __init__(self, dim_in=1536):
+        super().__init__()
+        self.backbone = nn.Sequential(nn.Linear(dim_in, dim_in), nn.ReLU(), nn.Linear(dim_in, dim_in), nn.ReLU())
+        self.fc_t = nn.Linear(dim_in, 3)
+        self.fc_qvec = nn.Linear(dim_in, 4)
+        self.fc_fov = nn.Sequential(nn.Linear(dim_in, 2), nn.ReLU())
+
+    def forward(self, feat, camera_encoding=None):
+        if camera_encoding is not None:
+            raise NotImplementedError("camera_encoding (rotation and field of view from the caller) is not used by the scorer")
+        B, S = feat.shape[:2]
+        lin = lambda layer, t: F.linear(t, layer.weight.float(), layer.bias.float())          # fp32 arithmetic for bf16 parameters too
+        with torch.autocast(feat.device.type, enabled=False):
+            f = feat.reshape(B * S, -1).float()
+            f = F.relu(lin(self.backbone[2], F.relu(lin(self.backbone[0], f))))
+            return torch.cat([lin(self.fc_t, f), lin(self.fc_qvec, f), F.relu(lin(self.fc_fov[0], f))], dim=-1).reshape(B, S, 9)
+
+
+def decode_cameras(pose_enc, image_size_hw):
+    """da3.py:209-221: pose_enc fp32 [..., 9] -> (extrinsics [..., 3, 4] world-to-camera = affine_inverse of the decoded camera-to-world, intrinsics
+    [..., 3, 3]) in one launch (ops.da3_pose_decode)"""
+    return ops.da3_pose_decode(pose_enc.float().contiguous(), image_size_hw)
+
+
+class DA3Cameras(nn.Module):
+    """The part of DepthAnything3Net that is built here: `forward(images [B,S,3,H,W], already normalised and sized to multiples of 14) ->
+    {"feats": the backbone's per-layer (features, camera token) pairs, "pose_enc" [B,S,9], "extrinsics" [B,S,3,4] (world-to-camera), "intrinsics"
+    [B,S,3,3]}`.  The DualDPT head that turns `feats` into depth / conf, and the input resizing of depth_anything_3/api.py, stay the caller's."""
+
+    IGNORED_PREFIXES = ("head.", "cam_enc.", "gs_head.", "gs_adapter.")
+
+    def __init__(self, backbone, cam_dec):
+        super().__init__()
+        self.backbone, self.cam_dec = backbone, cam_dec
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        """A DepthAnything3Net state dict (an optional leading `model.` on every key is stripped): `backbone.*` and `cam_dec.*` must match by name;
+        `head.*`, `cam_enc.*`, `gs_head.*`, `gs_adapter.*` are not built here and are skipped -> the sorted list of the skipped prefixes that occurred"""
+        if not strict:
+            raise ValueError("DA3Cameras loads strictly: everything but the listed prefixes must match")
+        own, met = {}, set()
+        for k, v in state_dict.items():
+            k = k[len("model."):] if k.startswith("model.") else k
+            hit = next((p for p in self.IGNORED_PREFIXES if k.startswith(p)), None)
+            if hit is None:
+                own[k] = v
+            else:
+                met.add(hit)
+        super().load_state_dict(own, strict=True, **kw)
+        return sorted(met)
+
+    def forward(self, images, cam_token=None, ref_view_strategy="saddle_balanced"):
+        vggt._forward_only(self, images)
+        feats, _ = self.backbone(images, cam_token=cam_token, ref_view_strategy=ref_view_strategy)
+        pose_enc = self.cam_dec(feats[-1][1])
+        extrinsics, intrinsics = decode_cameras(pose_enc, images.shape[-2:])
+        return {"feats": feats, "pose_enc": pose_enc, "extrinsics": extrinsics, "intrinsics": intrinsics}

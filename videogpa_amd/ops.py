@@ -1534,3 +1534,96 @@ def lpips_layer_f32(f0, f1, w, relu=False, total=None, accumulate=False, out=Non
            lambda: _lib.call("vgpa_lpips_layer_f32", f0, f1, w, out, total, N, H, W, C, (1 if relu else 0) | (2 if accumulate else 0), ws, ws_bytes,
                              _stream()), "byte")
     return out
+
+
+# ---- Depth Anything 3's backbone between its blocks, and its camera decoding (csrc/da3.hip): fp32, forward only ---------------------------
+DA3_REF_VIEW_STRATEGIES = {"first": 0, "middle": 1, "saddle_balanced": 2, "saddle_sim_range": 3}
+
+
+def _da3_tokens(name, x, *more):
+    _req(x, torch.float32)
+    if x.dim() != 4:
+        raise RuntimeError(f"{name}: tokens are fp32 [B,S,N,C], got {tuple(x.shape)}")
+    for t in more:
+        if t is not None:
+            _req(t, torch.float32)
+            if t.shape != x.shape:
+                raise RuntimeError(f"{name}: the two token tensors do not fit ({tuple(x.shape)}, {tuple(t.shape)})")
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, *more)):
+        raise RuntimeError(f"{name} is forward only: call it under torch.no_grad()")
+    return x.shape
+
+
+def _da3_ref(name, ref_idx, B):
+    _req(ref_idx, torch.int32)
+    if ref_idx.numel() != B:
+        raise RuntimeError(f"{name}: ref_idx is a device int32 [B]")
+    return ref_idx
+
+
+def da3_ref_view(x, strategy="saddle_balanced", return_metrics=False):
+    """select_reference_view on token 0 of x fp32 [B,S,N,C] -> ref_idx, a DEVICE int32 [B] (it is never read on the host; the kernels below take it as it
+    is).  return_metrics: also fp64 [B,S,4] = (mean off-diagonal cosine similarity, norm, variance of the normalised token, ranking score) per view."""
+    B, S, N, C = _da3_tokens("da3_ref_view", x)
+    if strategy not in DA3_REF_VIEW_STRATEGIES:
+        raise ValueError(f"Unknown reference view selection strategy: {strategy}. Must be one of: {', '.join(map(repr, DA3_REF_VIEW_STRATEGIES))}")
+    ref_idx = torch.empty(B, device=x.device, dtype=torch.int32)
+    metrics = torch.empty(B, S, 4, device=x.device, dtype=torch.float64) if return_metrics else None
+    _timed("da3_ref_view", 4.0 * B * S * C, lambda: _lib.call("vgpa_da3_ref_view", x, B, S, N, C, DA3_REF_VIEW_STRATEGIES[strategy], metrics, ref_idx,
+                                                               _stream()), "byte")
+    return (ref_idx, metrics) if return_metrics else ref_idx
+
+
+def da3_view_gather(x, ref_idx, other=None, inverse=False):
+    """reorder_by_reference (inverse: restore_original_order) of x fp32 [B,S,N,C] -- and of `other`, same shape, in the same launch -- into new tensors:
+    -> reordered x, or (x, other)"""
+    B, S, N, C = _da3_tokens("da3_view_gather", x, other)
+    _da3_ref("da3_view_gather", ref_idx, B)
+    out = torch.empty_like(x)
+    out2 = None if other is None else torch.empty_like(other)
+    _timed("da3_view_gather", 8.0 * x.numel() * (1 if other is None else 2),
+           lambda: _lib.call("vgpa_da3_view_gather", x, out, other, out2, ref_idx, 1 if inverse else 0, B, S, N, C, _stream()), "byte")
+    return out if other is None else (out, out2)
+
+
+def da3_cam_token(x, cam, per_view):
+    """x[:, :, 0] = cam IN PLACE.  per_view: cam fp32 [B,S,C], one token per view (the caller's); else cam is the camera_token parameter [1,2,C]: row 0
+    for view 0 and row 1 for every other view.  -> x"""
+    B, S, N, C = _da3_tokens("da3_cam_token", x)
+    _req(cam, torch.float32)
+    if tuple(cam.shape) != ((B, S, C) if per_view else (1, 2, C)):
+        raise RuntimeError(f"da3_cam_token: cam {tuple(cam.shape)} is not {'[B,S,C]' if per_view else 'the camera_token parameter [1,2,C]'}")
+    _timed("da3_cam_token", 8.0 * B * S * C, lambda: _lib.call("vgpa_da3_cam_token", x, cam, 1 if per_view else 0, B, S, N, C, _stream()), "byte")
+    return x
+
+
+def da3_tap(local_x, x, ln_w, ln_b, eps=1e-5, ref_idx=None):
+    """One out layer of the backbone: -> (features fp32 [B,S,N-1,2C] = [local_x | LayerNorm(x)] of tokens 1.., camera token fp32 [B,S,2C] = [local_x | x]
+    of token 0), views restored to their original order when ref_idx (device int32 [B]) is given"""
+    B, S, N, C = _da3_tokens("da3_tap", x, local_x)
+    for t in (ln_w, ln_b):
+        _req(t, torch.float32)
+    if ln_w.numel() != C or ln_b.numel() != C:
+        raise RuntimeError("da3_tap: the LayerNorm parameters do not fit the tokens")
+    if ref_idx is not None:
+        _da3_ref("da3_tap", ref_idx, B)
+    feats = torch.empty(B, S, N - 1, 2 * C, device=x.device, dtype=torch.float32)
+    cam = torch.empty(B, S, 2 * C, device=x.device, dtype=torch.float32)
+    _timed("da3_tap", 16.0 * x.numel(), lambda: _lib.call("vgpa_da3_tap", local_x, x, ln_w, ln_b, float(eps), ref_idx, feats if N > 1 else None, cam,
+                                                          B, S, N, C, _stream()), "byte")
+    return feats, cam
+
+
+def da3_pose_decode(pose_enc, image_size_hw):
+    """pose_enc fp32 [..., 9] (camera-to-world) -> (extrinsics fp32 [..., 3, 4] world-to-camera, intrinsics fp32 [..., 3, 3])"""
+    _req(pose_enc, torch.float32)
+    if pose_enc.shape[-1] != 9 or pose_enc.numel() == 0:
+        raise RuntimeError(f"da3_pose_decode: pose encodings are [..., 9], got {tuple(pose_enc.shape)}")
+    if torch.is_grad_enabled() and pose_enc.requires_grad:
+        raise RuntimeError("da3_pose_decode is forward only: call it under torch.no_grad()")
+    lead, n = pose_enc.shape[:-1], pose_enc.numel() // 9
+    ext = torch.empty(*lead, 3, 4, device=pose_enc.device, dtype=torch.float32)
+    intr = torch.empty(*lead, 3, 3, device=pose_enc.device, dtype=torch.float32)
+    H, W = image_size_hw
+    _timed("da3_pose_decode", 4.0 * n * 30, lambda: _lib.call("vgpa_da3_pose_decode", pose_enc, n, float(H), float(W), ext, intr, _stream()), "byte")
+    return ext, intr

@@ -3,10 +3,11 @@
 contract and the same `compute_metrics` dispatch by metric name ("Consistency_Score" -> (score, motion_norm) tuple,
 "MVCS" -> needs depths / intrinsics / extrinsics, anything else -> compute(gt=, rep=)).
 
-What is NOT here, because it is a third-party network or host I/O outside the hot path: the DA3
-backbone, VGGT's DINOv2 patch embedding and video decoding.  VGGT itself -- aggregator, camera head, depth and point heads --
-is `videogpa_amd.vggt.VGGT` (pass it as `vggt_model=VGGT(...)`; any other `model(images) -> predictions` works the same way).
-They are passed in:
+What is NOT here: Depth Anything 3's DualDPT depth head (`depth` / `conf`) with its input resizing, and video
+decoding.  VGGT itself -- DINOv2 patch embedding, aggregator, camera head, depth and point heads -- is `videogpa_amd.vggt.VGGT` (pass it
+as `vggt_model=VGGT(...)`; any other `model(images) -> predictions` works the same way).  Of DA3, `videogpa_amd.da3.DA3Cameras` runs
+the backbone's tokens and the cameras (`extrinsics` / `intrinsics`) on the device; until the depth head is here a "da3" `backbone_fn`
+still brings the whole network.  They are passed in:
   * `frame_sampler(video_path, n_frames) -> uint8 [T,H,W,3]`      (utils/video_utils.py:19-44, decord + cv2 upstream)
   * backbone "vggt":  `backbone_fn(frames) -> dict` with the keys utils/model_utils.py:89-122 returns
       images [T,3,H,W] in [0,1], world_points_from_depth [T,H,W,3], depth_conf [T,H,W], depth, and either

@@ -221,12 +221,12 @@ class DinoBlock(nn.Module):
     norm2) -> fc1, GELU, fc2 -> stream_ln (ls2.gamma).  head_dim**-0.5 * log2(e), which the attention kernel wants on q, is folded into the q rows of a cached bf16
     copy of qkv.weight / qkv.bias (one bf16 rounding, as ops.prescale_q costs): no permute, no prescale pass."""
 
-    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, proj_bias=True, ffn_bias=True, init_values=None, eps=1e-6):
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, proj_bias=True, ffn_bias=True, init_values=None, eps=1e-6, attn_class=DinoAttention):
         super().__init__()
         if not init_values:
             raise NotImplementedError("DINOv2 blocks without LayerScale are not used by VGGT's aggregator (init_values=1.0)")
         self.norm1 = nn.LayerNorm(dim, eps=eps)
-        self.attn = DinoAttention(dim, num_heads=num_heads, qkv_bias=qkv_bias, proj_bias=proj_bias)
+        self.attn = attn_class(dim, num_heads=num_heads, qkv_bias=qkv_bias, proj_bias=proj_bias)     # a subclass with further parameters: videogpa_amd.da3
         self.ls1 = LayerScale(dim, init_values)
         self.norm2 = nn.LayerNorm(dim, eps=eps)
         self.mlp = Mlp(dim, int(dim * mlp_ratio), bias=ffn_bias)

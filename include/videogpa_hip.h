@@ -240,37 +240,30 @@ int32_t vgpa_attn128_bwd_prescaled(const void* q, const void* k, const void* v, 
 /* ---- row kernels of the Wan2.2 denoiser block (WanAttentionBlock / WanRMSNorm / rope_apply of the Wan2.2 checkout imported at
  * train/Wan2.2-TI2V-5B/03_train.py:43-48).  fp32 residual stream, bf16 matmul operands.  Per-token modulation as a table: row
  * gid[row] of a [groups, mod_stride] fp32 table (shift / scale / gate point at their chunk's column offset); gid NULL = row 0.
- *   ln_mod_fwd : out(bf16, row stride out_ld >= D: the LoRA tail of the consuming projection may follow each row) = ([round_bf16] LN_eps(x)) * ln_w
- *                + ln_b, then * (1 + scale[g]) + shift[g]   (affine / modulation optional; x_dtype VGPA_DTYPE_F32 | VGPA_DTYPE_BF16); with q8 / q8_scale the
- *                same rows are ALSO (or, out NULL, only) written as the e4m3 operand of the fp8 feed-forward GEMM: q8 [rows, D] bytes, q8_scale [rows]
- *                fp32, bit-identical to vgpa_quant_fp8_rows of the bf16 output
- *   ln_mod_bwd : dx(fp32) = [dres +] LN-backward(dy (1 + scale) ln_w)
+ *   ln_mod_fwd : out(row stride out_ld >= D: the LoRA tail of the consuming projection may follow each row) = ([round_bf16] LN_eps(x)) * ln_w + ln_b,
+ *                then * (1 + scale[g]) + shift[g]   (affine / modulation optional); with q8 / q8_scale the same rows are ALSO (or, out NULL, only) written
+ *                as the e4m3 operand of the fp8 feed-forward GEMM: q8 [rows, D] bytes, q8_scale [rows] fp32, bit-identical to vgpa_quant_fp8_rows of the bf16
+ *                output.  With y the row is first x_out(fp32) = x + y(bf16) * gate[g] (gate NULL = 1), the gated residual add in front of this LayerNorm
+ *                (upstream WanAttentionBlock.forward: `x = x + y * e[2]` followed by norm3 / norm2 of that x), in the same pass.
+ *   ln_mod_bwd : dx(fp32) = [dres +] LN-backward(dy (1 + scale) ln_w); with dy_prev also dy_prev(bf16, row stride ld_dy_prev) = dx * gate_prev[g] (NULL = 1),
+ *                the gradient of the y of that residual add.  gate / gate_prev index the same table rows as shift / scale (mod_stride).
+ *   dtypes (VGPA_DTYPE_*), each combination one kernel instantiation, anything else VGPA_ERR_INVALID:
+ *                forward   x fp32 | bf16 -> bf16 out and / or q8;   x fp32 + y -> the same, round_xhat 0;   x fp32 -> fp32 out, no y / affine / q8 / round_xhat
+ *                backward  dy bf16, x fp32 | bf16;   dy bf16, x fp32 + dy_prev;   dy fp32, x fp32, no dy_prev / ln_w / dres
+ *                (the fp32 form is WanModel's output head: upstream Head.forward runs LN, modulation and the projection in fp32; reference call site
+ *                train/Wan2.2-TI2V-5B/03_train.py:227-233 through WanModel.forward)
  *   gate_residual: out(fp32) = [x +] y(bf16) * gate[g]  (gate NULL = 1; out may alias x)
  *   gate_bwd   : dy(bf16, row stride ld_dy) = dout(fp32) * gate[g];   gate_bwd_q8: the same rows as e4m3 + per-row scale (fp8 dX GEMM operand)
  *   rms_rope   : n = bf16(u rsqrt(mean(u^2) + eps)) over the whole row [heads * head_dim]; y = bf16(n w); interleaved pairs of every head
  *                rotated by the angle at rope_{cos,sin}[(row % L) * head_dim/2 + pair]  (NULL: no rotation); u / out / dout / du are row-strided
  *                (ld_* in elements) so that q and k are read from and their gradients written into the fused [rows, 3 D (+ LoRA tail)] buffers */
-int32_t vgpa_wan_ln_mod_fwd(const void* x, int32_t x_dtype, const int32_t* gid, const float* ln_w, const float* ln_b, const float* shift,
-                            const float* scale, int64_t mod_stride, int64_t rows, int64_t D, float eps, int32_t round_xhat, void* out, int64_t out_ld,
-                            void* q8, float* q8_scale, float* mean, float* rstd, vgpa_stream_t stream);
-int32_t vgpa_wan_ln_mod_bwd(const void* dy, const void* x, int32_t x_dtype, const float* mean, const float* rstd, const int32_t* gid, const float* ln_w,
-                            const float* scale, int64_t mod_stride, int64_t rows, int64_t D, const float* dres, float* dx, vgpa_stream_t stream);
-/* the same two row kernels with an fp32 result / fp32 incoming gradient: WanModel's output head (upstream Head.forward runs LN, modulation and
- * the projection in fp32; reference call site train/Wan2.2-TI2V-5B/03_train.py:227-233 through WanModel.forward) */
-int32_t vgpa_wan_ln_mod_fwd_f32(const float* x, const int32_t* gid, const float* shift, const float* scale, int64_t mod_stride, int64_t rows, int64_t D, float eps,
-                                float* out, float* mean, float* rstd, vgpa_stream_t stream);
-int32_t vgpa_wan_ln_mod_bwd_f32(const float* dy, const float* x, const float* mean, const float* rstd, const int32_t* gid, const float* scale, int64_t mod_stride,
-                                int64_t rows, int64_t D, float* dx, vgpa_stream_t stream);
-/* a block's [gated residual add -> LayerNorm] pair in one pass (upstream WanAttentionBlock.forward: `x = x + y * e[2]` followed by norm3 / norm2 of that x):
- *   gate_ln_mod_fwd : xo(fp32) = x + y(bf16) * gate[g] (gate NULL = 1); then exactly ln_mod_fwd of xo (bf16 and / or e4m3 result)
- *   ln_mod_bwd_gate : dx = [dres +] LN-backward(...) as ln_mod_bwd, and dy_prev(bf16, row stride ld_dy_prev) = dx * gate_prev[g] (NULL = 1): the gradient of
- *                     the y of that residual add.  gate / gate_prev index the same table rows as shift / scale (mod_stride). */
-int32_t vgpa_wan_gate_ln_mod_fwd(const float* x, const void* y, const int32_t* gid, const float* gate, const float* ln_w, const float* ln_b, const float* shift,
-                                 const float* scale, int64_t mod_stride, int64_t rows, int64_t D, float eps, float* xo, void* out, int64_t out_ld, void* q8,
-                                 float* q8_scale, float* mean, float* rstd, vgpa_stream_t stream);
-int32_t vgpa_wan_ln_mod_bwd_gate(const void* dy, const float* x, const float* mean, const float* rstd, const int32_t* gid, const float* ln_w, const float* scale,
-                                 int64_t mod_stride, int64_t rows, int64_t D, const float* dres, float* dx, const float* gate_prev, void* dy_prev,
-                                 int64_t ld_dy_prev, vgpa_stream_t stream);
+int32_t vgpa_wan_ln_mod_fwd(const void* x, int32_t x_dtype, const void* y, const float* gate, float* x_out, const int32_t* gid, const float* ln_w,
+                            const float* ln_b, const float* shift, const float* scale, int64_t mod_stride, int64_t rows, int64_t D, float eps,
+                            int32_t round_xhat, void* out, int32_t out_dtype, int64_t out_ld, void* q8, float* q8_scale, float* mean, float* rstd,
+                            vgpa_stream_t stream);
+int32_t vgpa_wan_ln_mod_bwd(const void* dy, int32_t dy_dtype, const void* x, int32_t x_dtype, const float* mean, const float* rstd, const int32_t* gid,
+                            const float* ln_w, const float* scale, int64_t mod_stride, int64_t rows, int64_t D, const float* dres, float* dx,
+                            const float* gate_prev, void* dy_prev, int64_t ld_dy_prev, vgpa_stream_t stream);
 int32_t vgpa_wan_gate_residual(const float* x, const void* y, const int32_t* gid, const float* gate, int64_t mod_stride, int64_t rows, int64_t D, float* out,
                                vgpa_stream_t stream);
 int32_t vgpa_wan_gate_bwd(const float* dout, const int32_t* gid, const float* gate, int64_t mod_stride, int64_t rows, int64_t D, void* dy, int64_t ld_dy,

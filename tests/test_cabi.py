@@ -14,6 +14,30 @@ def _header_symbols():
     return set(re.findall(r"\b(vgpa_[a-z0-9_]+)\s*\(", src))
 
 
+_CTYPE = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "vgpa_stream_t": ctypes.c_void_p}
+
+
+def _header_signatures(variants):
+    """name -> (restype, [argtypes]) of every prototype of the header (variants: of its VGPA_VARIANTS block instead), pointers as c_void_p"""
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "videogpa_hip.h")).read(), flags=re.S)
+    blocks = re.findall(r"#ifdef VGPA_VARIANTS(.*?)#endif", src, flags=re.S)
+    src = "".join(blocks) if variants else re.sub(r"#ifdef VGPA_VARIANTS.*?#endif", "", src, flags=re.S)
+    ctype = lambda decl: ctypes.c_void_p if "*" in decl else _CTYPE[decl.replace("const", "").split()[0]]
+    return {name: (ctype(ret), [ctype(a) for a in args.split(",") if a.strip() != "void"])
+            for ret, name, args in re.findall(r"\b(\w+)\s+(vgpa_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", src)}
+
+
+def test_ctypes_table_matches_every_prototype_of_the_header():
+    """_lib.SIGNATURES is written by hand: a wrong width there corrupts arguments on the device and nothing on the CPU would notice"""
+    from videogpa_amd import _lib
+    declared = _header_signatures(variants=False)
+    assert set(declared) == _header_symbols() and len(declared) >= 20
+    wrong = {n: (sig, _lib.SIGNATURES.get(n)) for n, sig in declared.items() if _lib.SIGNATURES.get(n) != sig}
+    assert not wrong and set(_lib.SIGNATURES) == set(declared), wrong
+    optional = _header_signatures(variants=True)
+    assert optional == _lib.OPTIONAL_SIGNATURES, (optional, _lib.OPTIONAL_SIGNATURES)
+
+
 def test_library_exports_every_declared_symbol():
     from videogpa_amd import _lib, build
     build.build(verbose=False)

@@ -524,6 +524,81 @@ def test_wan_ln_mod_forward_backward(xdt, affine, mod, rnd):
     assert (xg.grad.double() - xr.grad).abs().max().item() <= tol * xr.grad.abs().max().item()
 
 
+@pytest.mark.parametrize("rows,C", [(5, 264), (9, 3072), (6, 4096)])
+def test_wan_ln_mod_fp32_result_forward_backward(rows, C):
+    """the output head's form -- fp32 x, fp32 result, fp32 incoming gradient, modulation only -- through ln_mod(out_dtype=torch.float32): rows that do not
+    fill the four waves of a workgroup with a partly filled first chunk, six full chunks, all eight chunks; against the fp64 expression, fp32 bound"""
+    from videogpa_amd.wan_model import ln_mod
+    g = torch.Generator(device="cuda").manual_seed(5)
+    G = 2
+    x = torch.randn(rows, C, device="cuda", generator=g) * 2 + 0.3
+    gid = (torch.arange(rows, device="cuda") % G).int()
+    tab = _tab(G, 2, C, g)
+    dy = torch.randn(rows, C, device="cuda", generator=g)
+    xg = x.clone().requires_grad_(True)
+    out = ln_mod(xg, gid, None, None, tab[:, 0], tab[:, 1], 1e-6, out_dtype=torch.float32)
+    out.backward(dy)
+    xr = x.double().requires_grad_(True)
+    h = torch.nn.functional.layer_norm(xr, (C,), None, None, 1e-6) * (1 + tab[:, 1].double()[gid.long()]) + tab[:, 0].double()[gid.long()]
+    h.backward(dy.double())
+    assert out.dtype == torch.float32 and xg.grad.dtype == torch.float32
+    eo = (out.double() - h.detach()).abs().max().item() / h.detach().abs().max().item()
+    eg = (xg.grad.double() - xr.grad).abs().max().item() / xr.grad.abs().max().item()
+    print(f"ln_mod fp32 result {rows}x{C}: out {eo:.3g} grad {eg:.3g}")
+    assert eo <= 1e-5 and eg <= 1e-5, (eo, eg)
+
+
+def test_wan_ln_mod_entries_reject_combinations_no_kernel_is_built_for():
+    """vgpa_wan_ln_mod_fwd / _bwd take the arguments of six former entries; a combination none of those accepted is VGPA_ERR_INVALID before any launch.
+    Every buffer holds fp32 [rows, D + 64], so a call accepted by mistake would still be a valid launch."""
+    from videogpa_amd import _lib
+    lib = _lib.load()
+    rows, D, F32, BF16 = 8, 256, 0, 1
+    st = torch.cuda.current_stream().cuda_stream
+    buf = lambda: torch.zeros(rows, D + 64, device="cuda")
+    x, y, gate, xo, gid, w, b, sh, sc, out, q8, q8s, mean, rstd, dy, dres, dx, dyp = (buf() for _ in range(18))
+
+    def fwd(x_dtype=F32, y=None, gate=None, x_out=None, ln_w=None, ln_b=None, round_xhat=0, out=out, out_dtype=BF16, q8=None, q8_scale=None):
+        p = lambda t: None if t is None else t.data_ptr()
+        return lib.vgpa_wan_ln_mod_fwd(p(x), x_dtype, p(y), p(gate), p(x_out), p(gid), p(ln_w), p(ln_b), p(sh), p(sc), D + 64, rows, D, 1e-6, round_xhat,
+                                       p(out), out_dtype, D + 64, p(q8), p(q8_scale), p(mean), p(rstd), st)
+
+    def bwd(dy_dtype=BF16, x_dtype=F32, ln_w=None, dres=None, gate_prev=None, dy_prev=None):
+        p = lambda t: None if t is None else t.data_ptr()
+        return lib.vgpa_wan_ln_mod_bwd(p(dy), dy_dtype, p(x), x_dtype, p(mean), p(rstd), p(gid), p(ln_w), p(sc), D + 64, rows, D, p(dres), p(dx), p(gate_prev),
+                                       p(dy_prev), D + 64, st)
+
+    assert fwd() == 0 and fwd(y=y, gate=gate, x_out=xo) == 0 and fwd(out_dtype=F32) == 0            # the three forms themselves are accepted
+    assert bwd() == 0 and bwd(gate_prev=gate, dy_prev=dyp) == 0 and bwd(dy_dtype=F32) == 0
+    rejected = {
+        "y with bf16 x": fwd(x_dtype=BF16, y=y, x_out=xo),
+        "y with round_xhat": fwd(y=y, x_out=xo, round_xhat=1),
+        "gate without y": fwd(gate=gate),
+        "x_out without y": fwd(x_out=xo),
+        "y without x_out": fwd(y=y, gate=gate),
+        "y with fp32 result": fwd(y=y, x_out=xo, out_dtype=F32),
+        "fp32 result with bf16 x": fwd(x_dtype=BF16, out_dtype=F32),
+        "fp32 result with q8": fwd(out_dtype=F32, q8=q8, q8_scale=q8s),
+        "fp32 result with affine": fwd(out_dtype=F32, ln_w=w, ln_b=b),
+        "fp32 result with round_xhat": fwd(out_dtype=F32, round_xhat=1),
+        "fp32 result without out": fwd(out=None, out_dtype=F32, q8=q8, q8_scale=q8s),
+        "unknown x dtype": fwd(x_dtype=2),
+        "unknown out dtype": fwd(out_dtype=2),
+        "dy_prev with bf16 x": bwd(x_dtype=BF16, dy_prev=dyp),
+        "dy_prev with fp32 dy": bwd(dy_dtype=F32, dy_prev=dyp),
+        "gate_prev without dy_prev": bwd(gate_prev=gate),
+        "fp32 dy with bf16 x": bwd(dy_dtype=F32, x_dtype=BF16),
+        "fp32 dy with ln_w": bwd(dy_dtype=F32, ln_w=w),
+        "fp32 dy with dres": bwd(dy_dtype=F32, dres=dres),
+        "unknown dy dtype": bwd(dy_dtype=2),
+    }
+    assert all(rc == -1 for rc in rejected.values()), rejected
+    torch.cuda.synchronize()
+    from videogpa_amd.wan_model import ln_mod
+    with pytest.raises(ValueError, match="fp32 result"):          # the Python entry says so before any node is built
+        ln_mod(x[:, :D].contiguous(), None, None, None, sh[0, :D], sc[0, :D], 1e-6, passthrough=True, out_dtype=torch.float32)
+
+
 def test_wan_gate_residual_forward_backward():
     from videogpa_amd.wan_model import gate_residual
     g = torch.Generator(device="cuda").manual_seed(2)
@@ -630,7 +705,8 @@ def test_fp8_operands_written_by_their_producers_match_the_unfused_chain():
     q = torch.empty(rows, C, dtype=torch.float8_e4m3fn, device="cuda"); sc = torch.empty(rows, 1, device="cuda")
     mean = torch.empty(rows, device="cuda"); rstd = torch.empty(rows, device="cuda")
     h2 = torch.empty(rows, C + 64, dtype=torch.bfloat16, device="cuda")
-    _lib.call("vgpa_wan_ln_mod_fwd", x, 0, gid, None, None, tab[:, 3], tab[:, 4], tab.stride(0), rows, C, 1e-6, 0, h2, C + 64, q, sc, mean, rstd, st)
+    _lib.call("vgpa_wan_ln_mod_fwd", x, 0, None, None, None, gid, None, None, tab[:, 3], tab[:, 4], tab.stride(0), rows, C, 1e-6, 0, h2, 1, C + 64, q, sc,
+              mean, rstd, st)
     assert torch.equal(h2[:, :C], h)                                     # strided bf16 output next to the e4m3 one
     _same_q8(q, sc, rq, rs, "ln_mod")
     # GELU forward / backward

@@ -17,7 +17,7 @@ LIB_PATH = os.environ.get("VGPA_LIB") or os.path.join(_HERE, "csrc", "libvgpa_hi
 
 P, I64, I32, F32, SZ = c_void_p, c_int64, c_int32, c_float, c_size_t
 
-# name -> (restype, [argtypes]) ; must mirror include/videogpa_hip.h (tests/test_cabi.py checks the symbol set)
+# name -> (restype, [argtypes]) ; must mirror include/videogpa_hip.h (tests/test_cabi.py checks every prototype against it)
 SIGNATURES = {
     "vgpa_dpo_loss_workspace_bytes": (SZ, [I64]),
     "vgpa_dpo_loss_fwd": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I32, F32, F32, I32, I32, P, P, P, P, SZ, P]),
@@ -56,12 +56,8 @@ SIGNATURES = {
     "vgpa_attn128_bwd_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_attn128_bwd": (I32, [P] * 19 + [I64, I64, I64, I64, F32, I32, P, SZ, P]),
     "vgpa_attn128_bwd_prescaled": (I32, [P] * 19 + [I64, I64, I64, I64, F32, I32, P, SZ, P]),
-    "vgpa_wan_ln_mod_fwd": (I32, [P, I32, P, P, P, P, P, I64, I64, I64, F32, I32, P, I64, P, P, P, P, P]),
-    "vgpa_wan_ln_mod_bwd": (I32, [P, P, I32, P, P, P, P, P, I64, I64, I64, P, P, P]),
-    "vgpa_wan_ln_mod_fwd_f32": (I32, [P, P, P, P, I64, I64, I64, F32, P, P, P, P]),
-    "vgpa_wan_ln_mod_bwd_f32": (I32, [P, P, P, P, P, P, I64, I64, I64, P, P]),
-    "vgpa_wan_gate_ln_mod_fwd": (I32, [P, P, P, P, P, P, P, P, I64, I64, I64, F32, P, P, I64, P, P, P, P, P]),
-    "vgpa_wan_ln_mod_bwd_gate": (I32, [P, P, P, P, P, P, P, I64, I64, I64, P, P, P, P, I64, P]),
+    "vgpa_wan_ln_mod_fwd": (I32, [P, I32, P, P, P, P, P, P, P, P, I64, I64, I64, F32, I32, P, I32, I64, P, P, P, P, P]),
+    "vgpa_wan_ln_mod_bwd": (I32, [P, I32, P, I32, P, P, P, P, P, I64, I64, I64, P, P, P, P, I64, P]),
     "vgpa_wan_gate_residual": (I32, [P, P, P, P, I64, I64, I64, P, P]),
     "vgpa_wan_gate_bwd": (I32, [P, P, P, I64, I64, I64, P, I64, P]),
     "vgpa_wan_gate_bwd_q8": (I32, [P, P, P, I64, I64, I64, P, P, P]),

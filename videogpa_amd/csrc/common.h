@@ -188,6 +188,43 @@ struct Raw8<VGPA_DTYPE_F32> {
     }
 };
 
+// ---- OCP e4m3 rows: scale = amax(row) / 448 (1 for an all-zero row), q = e4m3(v / scale), round-to-nearest-even, saturating.  Every producer of an fp8
+// GEMM operand (csrc/fp8.hip, csrc/wan.hip) writes through these two, which is what makes them bit-identical to vgpa_quant_fp8_rows of the bf16 rows.
+#define FP8_E4M3_MAX 448.0f
+__device__ __forceinline__ float e4m3_row_scale(float amax) { return amax > 0.f ? amax / FP8_E4M3_MAX : 1.f; }
+__device__ __forceinline__ void store8_e4m3(uint8_t* row, int i0, const float* v, float sc) {          // eight values -> one 8-byte store
+    float t[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) t[j] = fminf(fmaxf(v[j] / sc, -FP8_E4M3_MAX), FP8_E4M3_MAX);
+    u32x2_t w;
+    int p = 0;
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], p, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], p, true);
+    w[0] = (uint32_t)p;
+    p = 0;
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], p, false);
+    p = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], p, true);
+    w[1] = (uint32_t)p;
+    *reinterpret_cast<u32x2_t*>(row + i0) = w;
+}
+
+// ---- gelu_tanh(x) = 0.5 x (1 + tanh z), z = c (x + 0.044715 x^3)  ==  x * sigmoid(2z) = x / (1 + 2^(x (k1 + k2 x^2))),
+//   k1 = -2 c log2(e), k2 = 0.044715 k1.  One exp2 + one rcp + 5 full-rate VALU operations per element (the tanh form needs 10):
+// at 4.8 TB/s the GELU kernels spent two thirds of their time in VALU issue.  Saturates cleanly (2^+inf -> x * 0, 2^-inf -> x).
+#define GELU_K1 (-2.302208198f)      // -2 * 0.7978845608028654 * log2(e)
+#define GELU_K2 (-0.1029432396f)     // 0.044715 * K1
+__device__ __forceinline__ float gelu_sig(float x, float x2) {   // sigmoid(2z)
+    return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * (GELU_K1 + GELU_K2 * x2)));
+}
+__device__ __forceinline__ float gelu_tanh_value(float x) { return x * gelu_sig(x, x * x); }
+// d/dx [x s(x)] with s = sigmoid(2z):  s + x s (1 - s) 2 z'(x),  2 z' = 2c (1 + 3 * 0.044715 x^2)
+// (gelu_tanh_bwd_kernel of csrc/norm.hip writes this expression out, with these two literals: change both together)
+__device__ __forceinline__ float gelu_tanh_deriv(float x) {
+    const float x2 = x * x, sg = gelu_sig(x, x2);
+    const float dz2 = 1.5957691216057308f + 0.2140644488f * x2;          // 2c, 2c * 3 * 0.044715
+    return sg + x * (sg - sg * sg) * dz2;
+}
+
 template <int DT>
 __device__ __forceinline__ float load1(const void* base, size_t idx) {
     if (DT == VGPA_DTYPE_BF16) return bf16_to_f32(reinterpret_cast<const bf16_t*>(base)[idx]);

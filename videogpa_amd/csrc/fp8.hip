@@ -7,8 +7,6 @@
 // HBM-bound: 2 bytes read + 1 written per element.
 #include "common.h"
 
-#define FP8_E4M3_MAX 448.0f
-
 __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __restrict__ x, int64_t ldx, uint8_t* __restrict__ q, float* __restrict__ scale,
                                                                int64_t M, int K) {
     const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
@@ -23,24 +21,13 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
         for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[j]));
     }
     amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax / FP8_E4M3_MAX : 1.f;
+    const float sc = e4m3_row_scale(amax);
     if (lane == 0) scale[row] = sc;
     uint8_t* qr = q + (size_t)row * K;
     for (int i0 = lane * 8; i0 < K; i0 += 512) {
         float v[8];
         load8<VGPA_DTYPE_BF16>(xr, (size_t)i0, v);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = fminf(fmaxf(v[j] / sc, -FP8_E4M3_MAX), FP8_E4M3_MAX);
-        u32x2_t w;
-        int t = 0;
-        t = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], t, false);
-        t = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], t, true);
-        w[0] = (uint32_t)t;
-        t = 0;
-        t = __builtin_amdgcn_cvt_pk_fp8_f32(v[4], v[5], t, false);
-        t = __builtin_amdgcn_cvt_pk_fp8_f32(v[6], v[7], t, true);
-        w[1] = (uint32_t)t;
-        *reinterpret_cast<u32x2_t*>(qr + i0) = w;
+        store8_e4m3(qr, i0, v, sc);
     }
 }
 
@@ -48,9 +35,6 @@ __global__ __launch_bounds__(256) void quant_fp8_rows_kernel(const bf16_t* __res
 // One 256-thread workgroup per row, the row (<= 16384 wide) in registers as bf16-rounded values; results are bit-identical to the unfused
 // chain  gelu_tanh_{fwd,bwd} -> quant_fp8_rows  (tests/test_gpu_wan_kernels.py).
 #define Q8_NV 8
-#define GELU_K1 (-2.302208198f)      // as csrc/norm.hip
-#define GELU_K2 (-0.1029432396f)
-__device__ __forceinline__ float q8_gelu_sig(float x, float x2) { return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * (GELU_K1 + GELU_K2 * x2))); }
 
 __device__ __forceinline__ float q8_block_max(float v, float* smem) {
     v = wave_max(v);
@@ -63,21 +47,7 @@ __device__ __forceinline__ void q8_store_row(const float (*v)[8], int K, float s
 #pragma unroll
     for (int c = 0; c < Q8_NV; ++c) {
         const int i0 = (c * 256 + (int)threadIdx.x) * 8;
-        if (i0 < K) {
-            float t[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t[j] = fminf(fmaxf(v[c][j] / sc, -FP8_E4M3_MAX), FP8_E4M3_MAX);
-            u32x2_t w;
-            int p = 0;
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], p, false);
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], p, true);
-            w[0] = (uint32_t)p;
-            p = 0;
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], p, false);
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], p, true);
-            w[1] = (uint32_t)p;
-            *reinterpret_cast<u32x2_t*>(qr + i0) = w;
-        }
+        if (i0 < K) store8_e4m3(qr, i0, v[c], sc);
     }
 }
 
@@ -108,21 +78,13 @@ __global__ __launch_bounds__(256) void gelu_q8_kernel(const bf16_t* __restrict__
             if (BWD) unpack8(ga[c], g);
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
-                const float x = a[j], x2 = x * x, sg = q8_gelu_sig(x, x2);
-                float r;
-                if (BWD) {
-                    const float dz2 = 1.5957691216057308f + 0.2140644488f * x2;
-                    r = g[j] * (sg + x * (sg - sg * sg) * dz2);
-                } else {
-                    r = x * sg;
-                }
-                v[c][j] = round_bf16(r);
+                v[c][j] = round_bf16(BWD ? gelu_tanh_deriv(a[j]) * g[j] : gelu_tanh_value(a[j]));
                 amax = fmaxf(amax, fabsf(v[c][j]));
             }
         }
     }
     amax = q8_block_max(amax, smem);
-    const float sc = amax > 0.f ? amax / FP8_E4M3_MAX : 1.f;
+    const float sc = e4m3_row_scale(amax);
     if (threadIdx.x == 0) scale[row] = sc;
     q8_store_row(v, K, sc, q + (size_t)row * K);
 }

@@ -8,7 +8,7 @@
 //
 // HBM-bound: one wave per token row, the whole row lives in registers (D <= 4096), 16-byte loads, exact
 // two-pass mean/variance, wave-level reductions only (no LDS, no barriers).
-#include "common.h"
+#include "row_ln.h"
 
 #define WAVES_PER_BLOCK 4
 #define ROWS_PER_WAVE 4
@@ -83,7 +83,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void ln_modulate_fwd_kernel(
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             const int i0 = (c * 64 + lane) * 8;
-            if (i0 < D) {
+            if (i0 < D) {          // ln_sqdev_acc8 (row_ln.h) written out: through the helper hipcc schedules the NV = 1 instantiation differently
 #pragma unroll
                 for (int j = 0; j < 8; ++j) { const float d = v[c][j] - mean; sq += d * d; }
             }
@@ -155,7 +155,7 @@ __global__ __launch_bounds__(64 * WAVES_PER_BLOCK) void ln_modulate_bwd_kernel(
                 if (dres) unpack8(*reinterpret_cast<const u32x4_t*>(dres + (size_t)row * D + i0), o);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
-                    const float d = rstd * (g[c][j] - c1 - xh[c][j] * c2);
+                    const float d = ln_bwd_dx(rstd, g[c][j], xh[c][j], c1, c2);
                     o[j] = dres ? o[j] + d : d;
                 }
                 *reinterpret_cast<u32x4_t*>(dx + (size_t)row * D + i0) = pack8(o);
@@ -199,16 +199,8 @@ __device__ __forceinline__ float tanh_fast(float z) {
     return 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + e);
 }
 
-// gelu_tanh(x) = 0.5 x (1 + tanh z), z = c (x + 0.044715 x^3)  ==  x * sigmoid(2z) = x / (1 + 2^(x (k1 + k2 x^2))),
-//   k1 = -2 c log2(e), k2 = 0.044715 k1.  One exp2 + one rcp + 5 full-rate VALU operations per element (the tanh form needs 10):
-// at 4.8 TB/s these kernels spent two thirds of their time in VALU issue.  Saturates cleanly (2^+inf -> x * 0, 2^-inf -> x).
-// Two independent 16-byte chunks per thread and iteration keep twice the bytes in flight.
-#define GELU_K1 (-2.302208198f)      // -2 * 0.7978845608028654 * log2(e)
-#define GELU_K2 (-0.1029432396f)     // 0.044715 * K1
-__device__ __forceinline__ float gelu_sig(float x, float x2) {   // sigmoid(2z)
-    return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(x * (GELU_K1 + GELU_K2 * x2)));
-}
-
+// gelu_tanh in its sigmoid form (common.h gelu_tanh_value / gelu_tanh_deriv).  Two independent 16-byte chunks per thread and iteration keep twice
+// the bytes in flight.
 __global__ __launch_bounds__(256) void gelu_tanh_fwd_kernel(const bf16_t* __restrict__ u, int64_t total8, bf16_t* __restrict__ out) {
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x; c < total8; c += 2 * stride) {
@@ -222,15 +214,14 @@ __global__ __launch_bounds__(256) void gelu_tanh_fwd_kernel(const bf16_t* __rest
         unpack8(r1, b);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            a[j] = a[j] * gelu_sig(a[j], a[j] * a[j]);
-            b[j] = b[j] * gelu_sig(b[j], b[j] * b[j]);
+            a[j] = gelu_tanh_value(a[j]);
+            b[j] = gelu_tanh_value(b[j]);
         }
         *reinterpret_cast<u32x4_t*>(out + (size_t)c * 8) = pack8(a);
         if (two) *reinterpret_cast<u32x4_t*>(out + (size_t)c1 * 8) = pack8(b);
     }
 }
 
-// d/dx [x s(x)] with s = sigmoid(2z):  s + x s (1 - s) 2 z'(x),  2 z' = 2c (1 + 3*0.044715 x^2)
 __global__ __launch_bounds__(256) void gelu_tanh_bwd_kernel(const bf16_t* __restrict__ u, const bf16_t* __restrict__ dy, int64_t total8,
                                                               bf16_t* __restrict__ du) {
     const int64_t stride = (int64_t)gridDim.x * 256;
@@ -248,9 +239,9 @@ __global__ __launch_bounds__(256) void gelu_tanh_bwd_kernel(const bf16_t* __rest
         unpack8(ru0, a); unpack8(rg0, g); unpack8(ru1, b); unpack8(rg1, h);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-            {
+            {          // gelu_tanh_deriv written out: through the helper hipcc schedules this loop differently
                 const float x = a[j], x2 = x * x, sg = gelu_sig(x, x2);
-                const float dz2 = 1.5957691216057308f + 0.2140644488f * x2;          // 2c, 2c * 3 * 0.044715
+                const float dz2 = 1.5957691216057308f + 0.2140644488f * x2;
                 a[j] = g[j] * (sg + x * (sg - sg * sg) * dz2);
             }
             {
@@ -271,19 +262,6 @@ static inline unsigned ew_grid(int64_t total8) {
     return (unsigned)nb;
 }
 
-#define DISPATCH_NV(D, CALL)                       \
-    switch (((D) + 511) / 512) {                   \
-        case 1: { constexpr int NV = 1; CALL; } break; \
-        case 2: { constexpr int NV = 2; CALL; } break; \
-        case 3: { constexpr int NV = 3; CALL; } break; \
-        case 4: { constexpr int NV = 4; CALL; } break; \
-        case 5: { constexpr int NV = 5; CALL; } break; \
-        case 6: { constexpr int NV = 6; CALL; } break; \
-        case 7: { constexpr int NV = 7; CALL; } break; \
-        case 8: { constexpr int NV = 8; CALL; } break; \
-        default: return VGPA_ERR_INVALID;          \
-    }
-
 extern "C" {
 
 // y = LayerNorm(x; w, b, eps) [* scale1p + shift per token range].  Modulation pointers may all be NULL (plain LN).
@@ -297,7 +275,7 @@ int32_t vgpa_ln_modulate_fwd(const void* x, const float* ln_w, const float* ln_b
     if ((mean == nullptr) != (rstd == nullptr)) return VGPA_ERR_INVALID;
     const int64_t rows = B * S;
     dim3 grid((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK));
-    DISPATCH_NV(D, VGPA_LAUNCH((ln_modulate_fwd_kernel<NV>), grid, dim3(64 * WAVES_PER_BLOCK), 0, stream, (const bf16_t*)x, ln_w, ln_b,
+    ROW_DISPATCH_NV(D, VGPA_LAUNCH((ln_modulate_fwd_kernel<NV>), grid, dim3(64 * WAVES_PER_BLOCK), 0, stream, (const bf16_t*)x, ln_w, ln_b,
                                       shift_v, scale1p_v, shift_t, scale1p_t, mod_stride, (int)text_len, (int)S, (int)D, rows, eps,
                                       (bf16_t*)out, mean, rstd));
     VGPA_CHECK_LAUNCH();
@@ -313,7 +291,7 @@ int32_t vgpa_ln_modulate_bwd(const void* dy, const void* x, const float* mean, c
     if (scale1p_v && text_len > 0 && !scale1p_t) return VGPA_ERR_INVALID;
     const int64_t rows = B * S;
     dim3 grid((unsigned)((rows + ROWS_PER_BLOCK - 1) / ROWS_PER_BLOCK));
-    DISPATCH_NV(D, VGPA_LAUNCH((ln_modulate_bwd_kernel<NV>), grid, dim3(64 * WAVES_PER_BLOCK), 0, stream, (const bf16_t*)dy,
+    ROW_DISPATCH_NV(D, VGPA_LAUNCH((ln_modulate_bwd_kernel<NV>), grid, dim3(64 * WAVES_PER_BLOCK), 0, stream, (const bf16_t*)dy,
                                       (const bf16_t*)x, mean, rstd, ln_w, scale1p_v, scale1p_t, mod_stride, (int)text_len, (int)S, (int)D, rows,
                                       (const bf16_t*)dres, (bf16_t*)dx));
     VGPA_CHECK_LAUNCH();

@@ -15,7 +15,7 @@
 // (batch, range, 32-row block inside the range) -- so every row of a workgroup uses the LDS copy: the earlier layout (blocks of
 // 32 consecutive rows, a global-memory slow path for rows of another range) cost the forward 58 VGPRs for a path that 2 of 1111
 // workgroups ever took (166 -> 110 VGPRs, 3 -> 4 waves per SIMD).
-#include "common.h"
+#include "row_ln.h"
 
 #define RL_WAVES 4
 #define RL_ROWS_PER_WAVE 8
@@ -27,27 +27,22 @@ struct RLParams {
     const float* gate_v; const float* gate_t; int64_t gate_stride;
 };
 
-__device__ __forceinline__ void ld8(const float* p, float* o) {
-    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
-    o[0] = a.x; o[1] = a.y; o[2] = a.z; o[3] = a.w; o[4] = b.x; o[5] = b.y; o[6] = b.z; o[7] = b.w;
-}
-
 // alpha / beta / gate for 8 columns starting at i0, straight from global memory (slow path and LDS fill)
 __device__ __forceinline__ void params_global(const RLParams& P, int b, bool is_text, int i0, float* alpha, float* beta, float* gate) {
     float w[8], bb[8], sc[8], sh[8];
-    ld8(P.ln_w + i0, w);
-    if (P.ln_b) ld8(P.ln_b + i0, bb);
+    load8<VGPA_DTYPE_F32>(P.ln_w + i0, 0, w);
+    if (P.ln_b) load8<VGPA_DTYPE_F32>(P.ln_b + i0, 0, bb);
     const float* scp = is_text ? P.scale1p_t : P.scale1p_v;
     const float* shp = is_text ? P.shift_t : P.shift_v;
-    if (P.scale1p_v) ld8(scp + (size_t)b * P.mod_stride + i0, sc);
-    if (P.shift_v) ld8(shp + (size_t)b * P.mod_stride + i0, sh);
+    if (P.scale1p_v) load8<VGPA_DTYPE_F32>(scp + (size_t)b * P.mod_stride + i0, 0, sc);
+    if (P.shift_v) load8<VGPA_DTYPE_F32>(shp + (size_t)b * P.mod_stride + i0, 0, sh);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const float s = P.scale1p_v ? sc[j] : 1.f;
         alpha[j] = w[j] * s;
         if (beta) beta[j] = (P.ln_b ? bb[j] * s : 0.f) + (P.shift_v ? sh[j] : 0.f);
     }
-    if (gate && P.gate_v) ld8((is_text ? P.gate_t : P.gate_v) + (size_t)b * P.gate_stride + i0, gate);
+    if (gate && P.gate_v) load8<VGPA_DTYPE_F32>((is_text ? P.gate_t : P.gate_v) + (size_t)b * P.gate_stride + i0, 0, gate);
 }
 
 // All global loads of a row are issued back to back into packed registers BEFORE anything depends on them (branches
@@ -93,7 +88,7 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_fwd_kernel(const bf
             if (HAS_Y) {
                 float yy[8], g[8];
                 unpack8(yp[c], yy);
-                if (i0 < D) ld8(s_gate + i0, g);
+                if (i0 < D) load8<VGPA_DTYPE_F32>(s_gate + i0, 0, g);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[c][j] = round_bf16(v[c][j] + round_bf16(g[j] * yy[j]));
                 if (i0 < D) *reinterpret_cast<u32x4_t*>(x_new + (size_t)row * D + i0) = pack8(v[c]);
@@ -111,10 +106,7 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_fwd_kernel(const bf
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             const int i0 = (c * 64 + lane) * 8;
-            if (i0 < D) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) { const float d = v[c][j] - mean; sq += d * d; }
-            }
+            if (i0 < D) ln_sqdev_acc8(v[c], mean, sq);
         }
         const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
         if (lane == 0 && mean_out) { mean_out[row] = mean; rstd_out[row] = rstd; }
@@ -123,8 +115,8 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_fwd_kernel(const bf
             const int i0 = (c * 64 + lane) * 8;
             if (i0 < D) {
                 float a[8], be[8], o[8];
-                ld8(s_alpha + i0, a);
-                ld8(s_beta + i0, be);
+                load8<VGPA_DTYPE_F32>(s_alpha + i0, 0, a);
+                load8<VGPA_DTYPE_F32>(s_beta + i0, 0, be);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = (v[c][j] - mean) * rstd * a[j] + be[j];
                 *reinterpret_cast<u32x4_t*>(n_out + (size_t)row * n_stride + i0) = pack8(o);
@@ -175,7 +167,7 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_bwd_kernel(const bf
                 float g[8], xh[8], a[8];
                 unpack8(dnp[c], g);
                 unpack8(xp[c], xh);
-                ld8(s_alpha + i0, a);
+                load8<VGPA_DTYPE_F32>(s_alpha + i0, 0, a);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const float gg = g[j] * a[j];
@@ -192,11 +184,13 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_bwd_kernel(const bf
                 float g[8], xh[8], a[8], gt[8], o[8], r[8];
                 unpack8(dnp[c], g);
                 unpack8(xp[c], xh);
-                ld8(s_alpha + i0, a);
-                if (HAS_DY) ld8(s_gate + i0, gt);
+                load8<VGPA_DTYPE_F32>(s_alpha + i0, 0, a);
+                if (HAS_DY) load8<VGPA_DTYPE_F32>(s_gate + i0, 0, gt);
                 if (HAS_DRES) unpack8(rp[c], r);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
+                    // ln_bwd_dx (row_ln.h) written out: g and xhat are made again inside the expression here, and as arguments of the helper they are
+                    // evaluated in another order, which changes the instruction sequence of all 32 instantiations
                     const float d = rstd * (g[j] * a[j] - c1 - ((xh[j] - mean) * rstd) * c2);
                     o[j] = round_bf16(HAS_DRES ? r[j] + d : d);
                 }
@@ -210,19 +204,6 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_bwd_kernel(const bf
         }
     }
 }
-
-#define RL_DISPATCH(D, CALL)                           \
-    switch (((D) + 511) / 512) {                       \
-        case 1: { constexpr int NV = 1; CALL; } break; \
-        case 2: { constexpr int NV = 2; CALL; } break; \
-        case 3: { constexpr int NV = 3; CALL; } break; \
-        case 4: { constexpr int NV = 4; CALL; } break; \
-        case 5: { constexpr int NV = 5; CALL; } break; \
-        case 6: { constexpr int NV = 6; CALL; } break; \
-        case 7: { constexpr int NV = 7; CALL; } break; \
-        case 8: { constexpr int NV = 8; CALL; } break; \
-        default: return VGPA_ERR_INVALID;              \
-    }
 
 extern "C" {
 
@@ -245,8 +226,8 @@ int32_t vgpa_residual_ln_fwd(const void* x, const void* y, const float* gate_v, 
     const size_t shmem = (size_t)3 * D * sizeof(float);
 #define FWD_ARGS grid, dim3(64 * RL_WAVES), shmem, stream, (const bf16_t*)x, (const bf16_t*)y, P, (int)text_len, (int)S, (int)D, rows, eps, \
                  (bf16_t*)x_new, (bf16_t*)n_out, n_stride, mean, rstd
-    if (y) { RL_DISPATCH(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, true>), FWD_ARGS)); }
-    else { RL_DISPATCH(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, false>), FWD_ARGS)); }
+    if (y) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, true>), FWD_ARGS)); }
+    else { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, false>), FWD_ARGS)); }
 #undef FWD_ARGS
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
@@ -268,10 +249,10 @@ int32_t vgpa_residual_ln_bwd(const void* dn, const void* x_new, const float* mea
     const size_t shmem = (size_t)2 * D * sizeof(float);
 #define BWD_ARGS grid, dim3(64 * RL_WAVES), shmem, stream, (const bf16_t*)dn, (const bf16_t*)x_new, mean, rstd, P, (int)text_len, (int)S, (int)D, \
                  rows, (const bf16_t*)dres, (bf16_t*)dx, (bf16_t*)dy, dy_stride
-    if (dres && dy) { RL_DISPATCH(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, true, true>), BWD_ARGS)); }
-    else if (dres) { RL_DISPATCH(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, true, false>), BWD_ARGS)); }
-    else if (dy) { RL_DISPATCH(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, false, true>), BWD_ARGS)); }
-    else { RL_DISPATCH(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, false, false>), BWD_ARGS)); }
+    if (dres && dy) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, true, true>), BWD_ARGS)); }
+    else if (dres) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, true, false>), BWD_ARGS)); }
+    else if (dy) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, false, true>), BWD_ARGS)); }
+    else { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, false, false>), BWD_ARGS)); }
 #undef BWD_ARGS
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;

@@ -7,7 +7,7 @@
 //   * q / k go through WanRMSNorm over the FULL projection width (all heads), times a bf16 weight, then the 3-axis RoPE on
 //     interleaved pairs of each 128-wide head.
 // One wave per row, rows of C <= 4096 elements held in registers; all HBM-bound (algorithmic bytes in DESIGN.md section 4).
-#include "common.h"
+#include "row_ln.h"
 
 #define WAN_NV 8                 // 64 lanes x 8 elements x WAN_NV >= C
 #define WAN_WAVES 4
@@ -24,26 +24,12 @@ __device__ __forceinline__ void wan_quant_row(const float (*v)[8], int D, int la
             for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[c][j]));
         }
     amax = wave_max(amax);
-    const float sc = amax > 0.f ? amax / 448.0f : 1.f;
+    const float sc = e4m3_row_scale(amax);
     if (lane == 0) *scale = sc;
 #pragma unroll
     for (int c = 0; c < WAN_NV; ++c) {
         const int i0 = (c * 64 + lane) * 8;
-        if (i0 < D) {
-            float t[8];
-#pragma unroll
-            for (int j = 0; j < 8; ++j) t[j] = fminf(fmaxf(v[c][j] / sc, -448.0f), 448.0f);
-            u32x2_t w;
-            int p = 0;
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[0], t[1], p, false);
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[2], t[3], p, true);
-            w[0] = (uint32_t)p;
-            p = 0;
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[4], t[5], p, false);
-            p = __builtin_amdgcn_cvt_pk_fp8_f32(t[6], t[7], p, true);
-            w[1] = (uint32_t)p;
-            *reinterpret_cast<u32x2_t*>(qr + i0) = w;
-        }
+        if (i0 < D) store8_e4m3(qr, i0, v[c], sc);
     }
 }
 
@@ -99,10 +85,7 @@ __global__ __launch_bounds__(64 * WAN_WAVES) void wan_ln_mod_fwd_kernel(const vo
     float sq = 0.f;
 #pragma unroll
     for (int c = 0; c < WAN_NV; ++c)
-        if ((c * 64 + lane) * 8 < D) {
-#pragma unroll
-            for (int j = 0; j < 8; ++j) { const float d = v[c][j] - mean; sq += d * d; }
-        }
+        if ((c * 64 + lane) * 8 < D) ln_sqdev_acc8(v[c], mean, sq);
     const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
     if (lane == 0 && mean_out) { mean_out[row] = mean; rstd_out[row] = rstd; }
     const size_t g = gid ? (size_t)gid[row] * mod_stride : 0;
@@ -188,7 +171,7 @@ __global__ __launch_bounds__(64 * WAN_WAVES) void wan_ln_mod_bwd_kernel(const vo
             float o[8];
             if (dres) load8<VGPA_DTYPE_F32>(dres, (size_t)row * D + i0, o);
 #pragma unroll
-            for (int j = 0; j < 8; ++j) o[j] = (dres ? o[j] : 0.f) + rs * (gy[c][j] - c1 - xh[c][j] * c2);
+            for (int j = 0; j < 8; ++j) o[j] = (dres ? o[j] : 0.f) + ln_bwd_dx(rs, gy[c][j], xh[c][j], c1, c2);
             store8<VGPA_DTYPE_F32>(dx, (size_t)row * D + i0, o);
             if (GB) {
                 float gt[8];
@@ -389,78 +372,46 @@ static inline bool wan_dims_ok(int64_t rows, int64_t D) { return rows > 0 && D >
 static inline dim3 wan_grid(int64_t rows) { return dim3((unsigned)((rows + WAN_WAVES - 1) / WAN_WAVES)); }
 static inline dim3 wan_ew_grid(int64_t n8) { const int64_t b = (n8 + 255) / 256; return dim3((unsigned)(b < 65536 ? b : 65536)); }
 
-extern "C" int32_t vgpa_wan_ln_mod_fwd(const void* x, int32_t x_dtype, const int32_t* gid, const float* ln_w, const float* ln_b, const float* shift,
-                                       const float* scale, int64_t mod_stride, int64_t rows, int64_t D, float eps, int32_t round_xhat, void* out, int64_t out_ld,
-                                       void* q8, float* q8_scale, float* mean, float* rstd, hipStream_t stream) {
+// One entry per direction; the arguments pick the instantiation (table at the prototypes in include/videogpa_hip.h), and any combination outside that table is
+// VGPA_ERR_INVALID.  The fp32-result / fp32-gradient form is the output head of WanModel, which upstream runs in fp32 (LN, modulation and the projection under
+// autocast(float32)); y / dy_prev select the fused forms of a block's [gated residual add -> LayerNorm] pairs (GR / GB notes at the kernels).
+extern "C" int32_t vgpa_wan_ln_mod_fwd(const void* x, int32_t x_dtype, const void* y, const float* gate, float* x_out, const int32_t* gid, const float* ln_w,
+                                       const float* ln_b, const float* shift, const float* scale, int64_t mod_stride, int64_t rows, int64_t D, float eps,
+                                       int32_t round_xhat, void* out, int32_t out_dtype, int64_t out_ld, void* q8, float* q8_scale, float* mean, float* rstd,
+                                       hipStream_t stream) {
     if (!x || (!out && !q8) || !wan_dims_ok(rows, D) || (ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale == nullptr) ||
         (mean == nullptr) != (rstd == nullptr) || (q8 == nullptr) != (q8_scale == nullptr) || (out && (out_ld < D || out_ld % 8)))
         return VGPA_ERR_INVALID;
-    if (x_dtype == VGPA_DTYPE_F32)
-        VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_F32>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, x, gid, ln_w, ln_b, shift, scale, mod_stride, (int)D, rows,
-                    eps, round_xhat, out, out_ld, (uint8_t*)q8, q8_scale, mean, rstd);
-    else if (x_dtype == VGPA_DTYPE_BF16)
-        VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_BF16>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, x, gid, ln_w, ln_b, shift, scale, mod_stride, (int)D, rows,
-                    eps, round_xhat, out, out_ld, (uint8_t*)q8, q8_scale, mean, rstd);
-    else
-        return VGPA_ERR_INVALID;
+    const bool x32 = x_dtype == VGPA_DTYPE_F32, out32 = out_dtype == VGPA_DTYPE_F32;
+    if ((!x32 && x_dtype != VGPA_DTYPE_BF16) || (!out32 && out_dtype != VGPA_DTYPE_BF16)) return VGPA_ERR_INVALID;
+    if (y ? (!x32 || !x_out || round_xhat || out32) : (gate || x_out)) return VGPA_ERR_INVALID;
+    if (out32 && (!out || !x32 || ln_w || q8 || round_xhat)) return VGPA_ERR_INVALID;
+#define FWD_ARGS wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, x, gid, ln_w, ln_b, shift, scale, mod_stride, (int)D, rows, eps, round_xhat, out, out_ld, (uint8_t*)q8, \
+                 q8_scale, mean, rstd, (const bf16_t*)y, gate, x_out
+    if (y) VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_BF16, true>), FWD_ARGS);
+    else if (out32) VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_F32>), FWD_ARGS);
+    else if (x32) VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_F32>), FWD_ARGS);
+    else VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_BF16>), FWD_ARGS);
+#undef FWD_ARGS
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }
 
-extern "C" int32_t vgpa_wan_ln_mod_bwd(const void* dy, const void* x, int32_t x_dtype, const float* mean, const float* rstd, const int32_t* gid, const float* ln_w,
-                                       const float* scale, int64_t mod_stride, int64_t rows, int64_t D, const float* dres, float* dx, hipStream_t stream) {
+extern "C" int32_t vgpa_wan_ln_mod_bwd(const void* dy, int32_t dy_dtype, const void* x, int32_t x_dtype, const float* mean, const float* rstd, const int32_t* gid,
+                                       const float* ln_w, const float* scale, int64_t mod_stride, int64_t rows, int64_t D, const float* dres, float* dx,
+                                       const float* gate_prev, void* dy_prev, int64_t ld_dy_prev, hipStream_t stream) {
     if (!dy || !x || !mean || !rstd || !dx || !wan_dims_ok(rows, D)) return VGPA_ERR_INVALID;
-    if (x_dtype == VGPA_DTYPE_F32)
-        VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_F32>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, dy, x, mean, rstd, gid, ln_w, scale, mod_stride,
-                    (int)D, rows, dres, dx);
-    else if (x_dtype == VGPA_DTYPE_BF16)
-        VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_BF16>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, dy, x, mean, rstd, gid, ln_w, scale, mod_stride,
-                    (int)D, rows, dres, dx);
-    else
-        return VGPA_ERR_INVALID;
-    VGPA_CHECK_LAUNCH();
-    return VGPA_OK;
-}
-
-// The output head of WanModel runs in fp32 upstream (LN, modulation and the projection under autocast(float32)): the same row kernels with an fp32
-// result / an fp32 incoming gradient, x fp32, no affine.
-extern "C" int32_t vgpa_wan_ln_mod_fwd_f32(const float* x, const int32_t* gid, const float* shift, const float* scale, int64_t mod_stride, int64_t rows, int64_t D,
-                                           float eps, float* out, float* mean, float* rstd, hipStream_t stream) {
-    if (!x || !out || !wan_dims_ok(rows, D) || (shift == nullptr) != (scale == nullptr) || (mean == nullptr) != (rstd == nullptr)) return VGPA_ERR_INVALID;
-    VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_F32>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, (const void*)x, gid, (const float*)nullptr,
-                (const float*)nullptr, shift, scale, mod_stride, (int)D, rows, eps, 0, (void*)out, D, (uint8_t*)nullptr, (float*)nullptr, mean, rstd);
-    VGPA_CHECK_LAUNCH();
-    return VGPA_OK;
-}
-
-extern "C" int32_t vgpa_wan_ln_mod_bwd_f32(const float* dy, const float* x, const float* mean, const float* rstd, const int32_t* gid, const float* scale,
-                                           int64_t mod_stride, int64_t rows, int64_t D, float* dx, hipStream_t stream) {
-    if (!dy || !x || !mean || !rstd || !dx || !wan_dims_ok(rows, D)) return VGPA_ERR_INVALID;
-    VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_F32>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, (const void*)dy, (const void*)x, mean, rstd, gid,
-                (const float*)nullptr, scale, mod_stride, (int)D, rows, (const float*)nullptr, dx);
-    VGPA_CHECK_LAUNCH();
-    return VGPA_OK;
-}
-
-// Fused forms of a block's [gated residual add -> LayerNorm] pairs (x' = x + y * gate[g]; h = LN(x') ...): see the GR / GB notes at the kernels.
-extern "C" int32_t vgpa_wan_gate_ln_mod_fwd(const float* x, const void* y, const int32_t* gid, const float* gate, const float* ln_w, const float* ln_b, const float* shift,
-                                            const float* scale, int64_t mod_stride, int64_t rows, int64_t D, float eps, float* xo, void* out, int64_t out_ld, void* q8,
-                                            float* q8_scale, float* mean, float* rstd, hipStream_t stream) {
-    if (!x || !y || !xo || (!out && !q8) || !wan_dims_ok(rows, D) || (ln_w == nullptr) != (ln_b == nullptr) || (shift == nullptr) != (scale == nullptr) ||
-        (mean == nullptr) != (rstd == nullptr) || (q8 == nullptr) != (q8_scale == nullptr) || (out && (out_ld < D || out_ld % 8)))
-        return VGPA_ERR_INVALID;
-    VGPA_LAUNCH((wan_ln_mod_fwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_BF16, true>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, (const void*)x, gid, ln_w, ln_b, shift, scale,
-                mod_stride, (int)D, rows, eps, 0, out, out_ld, (uint8_t*)q8, q8_scale, mean, rstd, (const bf16_t*)y, gate, xo);
-    VGPA_CHECK_LAUNCH();
-    return VGPA_OK;
-}
-
-extern "C" int32_t vgpa_wan_ln_mod_bwd_gate(const void* dy, const float* x, const float* mean, const float* rstd, const int32_t* gid, const float* ln_w, const float* scale,
-                                            int64_t mod_stride, int64_t rows, int64_t D, const float* dres, float* dx, const float* gate_prev, void* dy_prev,
-                                            int64_t ld_dy_prev, hipStream_t stream) {
-    if (!dy || !x || !mean || !rstd || !dx || !dy_prev || !wan_dims_ok(rows, D) || ld_dy_prev < D || ld_dy_prev % 8) return VGPA_ERR_INVALID;
-    VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_BF16, true>), wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, dy, (const void*)x, mean, rstd, gid, ln_w,
-                scale, mod_stride, (int)D, rows, dres, dx, gate_prev, (bf16_t*)dy_prev, ld_dy_prev);
+    const bool x32 = x_dtype == VGPA_DTYPE_F32, dy32 = dy_dtype == VGPA_DTYPE_F32;
+    if ((!x32 && x_dtype != VGPA_DTYPE_BF16) || (!dy32 && dy_dtype != VGPA_DTYPE_BF16)) return VGPA_ERR_INVALID;
+    if (dy_prev ? (!x32 || dy32 || ld_dy_prev < D || ld_dy_prev % 8) : gate_prev != nullptr) return VGPA_ERR_INVALID;
+    if (dy32 && (!x32 || ln_w || dres)) return VGPA_ERR_INVALID;
+#define BWD_ARGS wan_grid(rows), dim3(64 * WAN_WAVES), 0, stream, dy, x, mean, rstd, gid, ln_w, scale, mod_stride, (int)D, rows, dres, dx, gate_prev, (bf16_t*)dy_prev, \
+                 ld_dy_prev
+    if (dy_prev) VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_BF16, true>), BWD_ARGS);
+    else if (dy32) VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_F32, VGPA_DTYPE_F32>), BWD_ARGS);
+    else if (x32) VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_F32>), BWD_ARGS);
+    else VGPA_LAUNCH((wan_ln_mod_bwd_kernel<VGPA_DTYPE_BF16>), BWD_ARGS);
+#undef BWD_ARGS
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }

@@ -60,7 +60,8 @@ def _modulation_is_frozen(tab, who):
 
 
 class _LnModFn(torch.autograd.Function):
-    """bf16( LN_eps(x) [rounded to bf16] * ln_w + ln_b, then * (1 + scale[gid]) + shift[gid] );   x [rows, D] fp32 or bf16.
+    """out_dtype( LN_eps(x) [rounded to bf16] * ln_w + ln_b, then * (1 + scale[gid]) + shift[gid] );   x [rows, D] fp32 or bf16, out_dtype bf16, or fp32
+    for an fp32 x without affine (the output head's normalisation).
     pad > 0: the result is the head of a [rows, D + pad] buffer (ops._padded_empty) whose tail the consuming projection fills with its LoRA
     down-projection, so the K-extended GEMM (ops.LoraExt) reads its operand in place.
     passthrough: x is returned as a second output for the residual path of the same branch (x' = x + gate * f(LN(x))); the backward then gets
@@ -68,16 +69,14 @@ class _LnModFn(torch.autograd.Function):
     tensors in a pass of its own."""
 
     @staticmethod
-    def forward(ctx, x, gid, ln_w, ln_b, shift, scale, eps, round_xhat, pad, passthrough):
+    def forward(ctx, x, gid, ln_w, ln_b, shift, scale, eps, round_xhat, pad, passthrough, out_dtype):
         rows, D = x.shape
         x = x.contiguous()
-        out = ops._padded_empty((rows,), D, pad, torch.bfloat16, x.device) if pad else torch.empty(rows, D, dtype=torch.bfloat16, device=x.device)
+        out = ops._padded_empty((rows,), D, pad, out_dtype, x.device) if pad else torch.empty(rows, D, dtype=out_dtype, device=x.device)
         mean = torch.empty(rows, dtype=torch.float32, device=x.device)
         rstd = torch.empty_like(mean)
         ms = 0 if shift is None else shift.stride(0)
-        ops._timed("wan_ln_mod_fwd", (x.element_size() + 2.0) * rows * D, lambda: _lib.call(
-            "vgpa_wan_ln_mod_fwd", x, _ptr_dtype(x), gid, ln_w, ln_b, shift, scale, ms, rows, D, float(eps), int(round_xhat), out, D + pad, None, None,
-            mean, rstd, _stream()), "byte")
+        _ln_mod_fwd_raw(x, gid, ln_w, ln_b, shift, scale, ms, eps, round_xhat, out, D + pad, mean=mean, rstd=rstd)
         ctx.save_for_backward(x, mean, rstd, gid, ln_w, scale)
         ctx.ms = ms
         ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None, not as a zero tensor to be added
@@ -90,41 +89,12 @@ class _LnModFn(torch.autograd.Function):
         x, mean, rstd, gid, ln_w, scale = ctx.saved_tensors
         rows, D = x.shape
         if dy is None:
-            return (None if dres is None else dres.to(x.dtype)), None, None, None, None, None, None, None, None, None
+            return (None if dres is None else dres.to(x.dtype)), None, None, None, None, None, None, None, None, None, None
         if dres is not None and (dres.dtype != torch.float32 or not dres.is_contiguous()):
             dres = dres.float().contiguous()
         dx = torch.empty(rows, D, dtype=torch.float32, device=x.device)
-        ops._timed("wan_ln_mod_bwd", (x.element_size() + (6.0 if dres is None else 10.0)) * rows * D, lambda: _lib.call(
-            "vgpa_wan_ln_mod_bwd", dy.contiguous(), x, _ptr_dtype(x), mean, rstd, gid, ln_w, scale, ctx.ms, rows, D, dres, dx, _stream()), "byte")
-        return dx.to(x.dtype), None, None, None, None, None, None, None, None, None
-
-
-class _HeadLnModFn(torch.autograd.Function):
-    """fp32( LN_eps(x) * (1 + scale[gid]) + shift[gid] ),  x [rows, D] fp32: the output head's normalisation (csrc/wan.hip, the fp32-result form of the
-    block kernels).  The modulation table takes no gradient (see _modulation_is_frozen: checked by the caller, as in the blocks)."""
-
-    @staticmethod
-    def forward(ctx, x, gid, shift, scale, eps):
-        rows, D = x.shape
-        x = x.contiguous()
-        out = torch.empty(rows, D, dtype=torch.float32, device=x.device)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty_like(mean)
-        ms = shift.stride(0)
-        ops._timed("wan_ln_mod_fwd", 8.0 * rows * D, lambda: _lib.call(
-            "vgpa_wan_ln_mod_fwd_f32", x, gid, shift, scale, ms, rows, D, float(eps), out, mean, rstd, _stream()), "byte")
-        ctx.save_for_backward(x, mean, rstd, gid, scale)
-        ctx.ms = ms
-        return out
-
-    @staticmethod
-    def backward(ctx, dy):
-        x, mean, rstd, gid, scale = ctx.saved_tensors
-        rows, D = x.shape
-        dx = torch.empty(rows, D, dtype=torch.float32, device=x.device)
-        ops._timed("wan_ln_mod_bwd", 12.0 * rows * D, lambda: _lib.call(
-            "vgpa_wan_ln_mod_bwd_f32", dy.float().contiguous(), x, mean, rstd, gid, scale, ctx.ms, rows, D, dx, _stream()), "byte")
-        return dx, None, None, None, None
+        _ln_mod_bwd_raw(dy.contiguous(), x, mean, rstd, gid, ln_w, scale, ctx.ms, dres, dx)
+        return dx.to(x.dtype), None, None, None, None, None, None, None, None, None, None
 
 
 class _GateLnFn(torch.autograd.Function):
@@ -147,8 +117,7 @@ class _GateLnFn(torch.autograd.Function):
         ms = gate.stride(0) if gate is not None else (shift.stride(0) if shift is not None else 0)
         if gate is not None and shift is not None and gate.stride(0) != shift.stride(0):
             raise ValueError("gate and shift / scale must be columns of one modulation table")
-        ops._timed("wan_gate_ln_fwd", 12.0 * rows * D, lambda: _lib.call(
-            "vgpa_wan_gate_ln_mod_fwd", x, y, gid, gate, ln_w, ln_b, shift, scale, ms, rows, D, float(eps), xo, out, D + pad, None, None, mean, rstd, _stream()), "byte")
+        _ln_mod_fwd_raw(x, gid, ln_w, ln_b, shift, scale, ms, eps, False, out, D + pad, mean=mean, rstd=rstd, y=y, gate=gate, x_out=xo)
         ctx.save_for_backward(xo, mean, rstd, gid, ln_w, scale, gate)
         ctx.ms, ctx.dy_pad = ms, dy_pad
         ctx.set_materialize_grads(False)
@@ -170,8 +139,7 @@ class _GateLnFn(torch.autograd.Function):
             dres = dres.float().contiguous()
         dx = torch.empty(rows, D, dtype=torch.float32, device=xo.device)
         dy = ops._padded_empty((rows,), D, pad, torch.bfloat16, xo.device) if pad else torch.empty(rows, D, dtype=torch.bfloat16, device=xo.device)
-        ops._timed("wan_ln_gate_bwd", (12.0 if dres is None else 16.0) * rows * D, lambda: _lib.call(
-            "vgpa_wan_ln_mod_bwd_gate", dh.contiguous(), xo, mean, rstd, gid, ln_w, scale, ctx.ms, rows, D, dres, dx, gate, dy, D + pad, _stream()), "byte")
+        _ln_mod_bwd_raw(dh.contiguous(), xo, mean, rstd, gid, ln_w, scale, ctx.ms, dres, dx, gate, dy, D + pad)
         return dx, dy, None, None, None, None, None, None, None, None, None
 
 
@@ -210,6 +178,25 @@ def _rows2(t, D):
     except RuntimeError:
         t2 = t.contiguous().view(-1, D)
     return t2, t2.stride(0)
+
+
+def _ln_mod_fwd_raw(x, gid, ln_w, ln_b, shift, scale, ms, eps, round_xhat, out, out_ld, q8=None, q8_scale=None, mean=None, rstd=None, y=None, gate=None, x_out=None):
+    """vgpa_wan_ln_mod_fwd.  y (bf16; + gate, x_out): the gated residual add in front of the LayerNorm rides along (csrc/wan.hip, GR form).  The timer gets
+    the bytes the launch moves per element: x, the result(s), and y + x_out of the residual add."""
+    rows, D = x.shape
+    per = x.element_size() + (6 if y is not None else 0) + (out.element_size() if out is not None else 0) + (1 if q8 is not None else 0)
+    ops._timed("wan_ln_mod_fwd" if y is None else "wan_gate_ln_fwd", float(per) * rows * D, lambda: _lib.call(
+        "vgpa_wan_ln_mod_fwd", x, _ptr_dtype(x), y, gate, x_out, gid, ln_w, ln_b, shift, scale, ms, rows, D, float(eps), int(round_xhat), out,
+        _BF16 if out is None else _ptr_dtype(out), out_ld, q8, q8_scale, mean, rstd, _stream()), "byte")
+
+
+def _ln_mod_bwd_raw(dy, x, mean, rstd, gid, ln_w, scale, ms, dres, dx, gate_prev=None, dy_prev=None, ld_dy_prev=0):
+    """vgpa_wan_ln_mod_bwd.  dy_prev (bf16, row stride ld_dy_prev; + gate_prev): also the gradient of the y of the residual add in front (GB form)."""
+    rows, D = x.shape
+    per = dy.element_size() + x.element_size() + 4 + (4 if dres is not None else 0) + (2 if dy_prev is not None else 0)
+    ops._timed("wan_ln_mod_bwd" if dy_prev is None else "wan_ln_gate_bwd", float(per) * rows * D, lambda: _lib.call(
+        "vgpa_wan_ln_mod_bwd", dy, _ptr_dtype(dy), x, _ptr_dtype(x), mean, rstd, gid, ln_w, scale, ms, rows, D, dres, dx, gate_prev, dy_prev, ld_dy_prev,
+        _stream()), "byte")
 
 
 def _rms_rope_fwd_raw(u2, ld_u, w, cos, sin, L, head_dim, eps, out2, ld_out, rstd):
@@ -316,7 +303,7 @@ class _FfnFp8Fn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gid, shift, scale, gate, eps, W1, b1, W2, b2, pre=None, pre_dy_pad=0):
         """pre (bf16 [rows, D]): the branch input is x + pre -- the ungated residual add of the cross-attention in front of this branch, taken into the
-        LN pass (gate_ln_mod_fwd); the backward then also returns pre's gradient (its head in a buffer pre_dy_pad wider)."""
+        LN pass (ln_mod_fwd with y); the backward then also returns pre's gradient (its head in a buffer pre_dy_pad wider)."""
         rows, D = x.shape
         x = x.contiguous()
         dev = x.device
@@ -331,12 +318,9 @@ class _FfnFp8Fn(torch.autograd.Function):
             raise TypeError(f"ffn_fp8: `pre` is the bf16 output of the branch in front, shape {tuple(x.shape)}; got {pre.dtype} {tuple(pre.shape)}")
         if pre is not None:
             xin, x = x, torch.empty(rows, D, dtype=torch.float32, device=dev)
-            ops._timed("wan_gate_ln_fwd", 11.0 * rows * D, lambda: _lib.call(
-                "vgpa_wan_gate_ln_mod_fwd", xin, pre.contiguous(), gid, None, None, None, shift, scale, ms, rows, D, float(eps), x, None, D, hq, hs, mean, rstd,
-                _stream()), "byte")
+            _ln_mod_fwd_raw(xin, gid, None, None, shift, scale, ms, eps, False, None, D, hq, hs, mean, rstd, y=pre.contiguous(), x_out=x)
         else:
-            ops._timed("wan_ln_mod_fwd", (x.element_size() + 1.0) * rows * D, lambda: _lib.call(
-                "vgpa_wan_ln_mod_fwd", x, _ptr_dtype(x), gid, None, None, shift, scale, ms, rows, D, float(eps), 0, None, D, hq, hs, mean, rstd, _stream()), "byte")
+            _ln_mod_fwd_raw(x, gid, None, None, shift, scale, ms, eps, False, None, D, hq, hs, mean, rstd)
         u = ops._fp8_gemm(hq, hs, w1.q, w1.s, b1)
         gq, gs = ops.gelu_tanh_fwd_q8(u)
         y = ops._fp8_gemm(gq, gs, w2.q, w2.s, b2)
@@ -363,17 +347,18 @@ class _FfnFp8Fn(torch.autograd.Function):
         if ctx.pre_dy_pad is not None:
             pad = ctx.pre_dy_pad
             dpre = ops._padded_empty((rows,), D, pad, torch.bfloat16, dev) if pad else torch.empty(rows, D, dtype=torch.bfloat16, device=dev)
-            ops._timed("wan_ln_gate_bwd", 16.0 * rows * D, lambda: _lib.call(
-                "vgpa_wan_ln_mod_bwd_gate", dh, x, mean, rstd, gid, None, scale, ctx.ms, rows, D, dout, dx, None, dpre, D + pad, _stream()), "byte")
+            _ln_mod_bwd_raw(dh, x, mean, rstd, gid, None, scale, ctx.ms, dout, dx, None, dpre, D + pad)
             return dx, None, None, None, None, None, None, None, None, None, dpre, None
-        ops._timed("wan_ln_mod_bwd", (x.element_size() + 10.0) * rows * D, lambda: _lib.call(
-            "vgpa_wan_ln_mod_bwd", dh, x, _ptr_dtype(x), mean, rstd, gid, None, scale, ctx.ms, rows, D, dout, dx, _stream()), "byte")
+        _ln_mod_bwd_raw(dh, x, mean, rstd, gid, None, scale, ctx.ms, dout, dx)
         return dx, None, None, None, None, None, None, None, None, None, None, None
 
 
-def ln_mod(x, gid=None, ln_w=None, ln_b=None, shift=None, scale=None, eps=1e-6, round_xhat=False, pad=0, passthrough=False):
-    """passthrough=True returns (LN output, x): feed THAT x into the branch's residual add (see _LnModFn)"""
-    return _LnModFn.apply(x, gid, ln_w, ln_b, shift, scale, eps, round_xhat, int(pad), bool(passthrough))
+def ln_mod(x, gid=None, ln_w=None, ln_b=None, shift=None, scale=None, eps=1e-6, round_xhat=False, pad=0, passthrough=False, out_dtype=torch.bfloat16):
+    """passthrough=True returns (LN output, x): feed THAT x into the branch's residual add (see _LnModFn).  out_dtype=torch.float32 is the output
+    head's form: fp32 x, modulation only"""
+    if out_dtype == torch.float32 and (x.dtype != torch.float32 or ln_w is not None or ln_b is not None or round_xhat or passthrough):
+        raise ValueError("ln_mod: an fp32 result takes an fp32 x and neither affine, round_xhat nor passthrough")
+    return _LnModFn.apply(x, gid, ln_w, ln_b, shift, scale, eps, round_xhat, int(pad), bool(passthrough), out_dtype)
 
 
 def gate_residual(x, y, gid=None, gate=None, dy_pad=0):
@@ -576,7 +561,7 @@ class Head(nn.Module):
         fp32 library GEMM."""
         tab = (self.modulation.float() + e[:, None]).contiguous()   # [G, 2, dim]
         _modulation_is_frozen(tab, "Head")
-        h = _HeadLnModFn.apply(x, gid, tab[:, 0], tab[:, 1], self.eps)
+        h = ln_mod(x, gid, None, None, tab[:, 0], tab[:, 1], self.eps, out_dtype=torch.float32)
         w, b = self.head.weight, self.head.bias
         return F.linear(h, w.float() if w.requires_grad else _f32(w), b.float() if b.requires_grad else _f32(b))
 

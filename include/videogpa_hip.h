@@ -451,6 +451,14 @@ int32_t vgpa_da3_tap(const float* local_x, const float* x, const float* ln_w, co
  * fov_h, fov_w; camera-to-world) -> ext fp32 [n,3,4] = its inverse [R^T | -R^T T] (world-to-camera), intr fp32 [n,3,3] with focal =
  * (size / 2) / max(tan(fov / 2), 1e-6) and the principal point at the image centre. */
 int32_t vgpa_da3_pose_decode(const float* pose_enc, int64_t n, float image_h, float image_w, float* ext, float* intr, vgpa_stream_t stream);
+/* The end of DualDPT's auxiliary branch (depth_anything_3/model/dualdpt.py:250-258) in one launch on the convolution core of vgpa_conv3x3_f32:
+ * x [N,h,w,C] plus xtab [w,C/2] / ytab [h,C/2] (the 0.1-scaled halves of position_grid_to_embed at the map's own grid; both NULL = no embedding),
+ * zero padding, 3x3 conv C -> 32 (w1_packed [3][3][C][32]) + b1, LayerNorm over the 32 channels of each pixel (ln_w, ln_b [32]; biased variance of
+ * the centred values, rsqrt(var + eps)), ReLU, 1x1 conv 32 -> output_dim (w2 [output_dim][32]) + b2: preds [N,h,w,output_dim-1] as they are
+ * (linear), conf [N,h,w] = 1 + exp.  The embedded tensor is never built.  C a multiple of 16, 2 <= output_dim <= 8. */
+int32_t vgpa_dualdpt_aux_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1,
+                                  const float* ln_w, const float* ln_b, float eps, const float* w2, const float* b2, float* preds, float* conf,
+                                  int64_t N, int64_t h, int64_t w, int64_t C, int32_t output_dim, vgpa_stream_t stream);
 
 #ifdef __cplusplus
 }

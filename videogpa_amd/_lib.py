@@ -100,6 +100,7 @@ SIGNATURES = {
     "vgpa_da3_cam_token": (I32, [P, P, I32, I64, I64, I64, I64, P]),
     "vgpa_da3_tap": (I32, [P, P, P, P, F32, P, P, P, I64, I64, I64, I64, P]),
     "vgpa_da3_pose_decode": (I32, [P, I64, F32, F32, P, P, P]),
+    "vgpa_dualdpt_aux_tail_f32": (I32, [P, P, P, P, P, P, P, F32, P, P, P, P, I64, I64, I64, I64, I32, P]),
 }
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library

@@ -1343,10 +1343,11 @@ def conv1x1_f32(x, w_packed, bias=None):
     return out
 
 
-def uv_embed_tables(width, height, channels, aspect_ratio, device, ratio=0.1):
+def uv_embed_tables(width, height, channels, aspect_ratio, device, ratio=0.1, f32_angles=False):
     """The two halves of `position_grid_to_embed(create_uv_grid(width, height, aspect_ratio), channels) * ratio` (vggt/heads/utils.py:11-109,
     dpt_head.py:249-259): the embedding concatenates an x half and a y half, so it is two tables, xtab [width, channels/2] and
-    ytab [height, channels/2] (fp32: sin | cos of coordinate * 100^(-i / (channels/4)), angles in float64 as upstream)."""
+    ytab [height, channels/2] (fp32: sin | cos of coordinate * 100^(-i / (channels/4)), angles in float64 as upstream).  f32_angles: Depth
+    Anything 3's recipe (model/utils/head_utils.py:123-146), where omega and the angles are float32."""
     if channels % 8:
         raise RuntimeError("uv_embed_tables: channels must be a multiple of 8")
     diag = (aspect_ratio ** 2 + 1.0) ** 0.5
@@ -1354,12 +1355,13 @@ def uv_embed_tables(width, height, channels, aspect_ratio, device, ratio=0.1):
     xs = torch.linspace(-span_x * (width - 1) / width, span_x * (width - 1) / width, steps=width, dtype=torch.float32)
     ys = torch.linspace(-span_y * (height - 1) / height, span_y * (height - 1) / height, steps=height, dtype=torch.float32)
     half = channels // 2
-    omega = torch.arange(half // 2, dtype=torch.float64)
+    adt = torch.float32 if f32_angles else torch.float64
+    omega = torch.arange(half // 2, dtype=adt)
     omega /= half / 2.0
     omega = 1.0 / 100 ** omega
 
     def table(pos):
-        ang = torch.einsum("m,d->md", pos.double(), omega)
+        ang = torch.einsum("m,d->md", pos.to(adt), omega)
         return (torch.cat([ang.sin(), ang.cos()], dim=1).float() * ratio).contiguous().to(device)
     return table(xs), table(ys)
 
@@ -1397,6 +1399,27 @@ def dpt_tail_f32(x, H, W, w1_packed, b1, w2, b2, activation="exp", tabs=None):
     conf = torch.empty(N, H, W, device=x.device, dtype=torch.float32)
     _timed("dpt_tail_f32", 2.0 * N * H * W * (9 * C * 32 + 32 * od),
            lambda: _lib.call("vgpa_dpt_tail_f32", x, xt, yt, w1_packed, b1, w2, b2, preds, conf, N, h, w, C, H, W, od, _DPT_ACT[activation], _stream()))
+    return preds, conf
+
+
+def dualdpt_aux_tail_f32(x, w1_packed, b1, ln_w, ln_b, eps, w2, b2, tabs=None):
+    """The end of DualDPT's auxiliary branch (dualdpt.py:250-258) in one launch (csrc/dualdpt.hip): x [N,h,w,C] (+ tabs = (xtab [w,C/2], ytab [h,C/2]))
+    -> conv3x3 C -> 32, LayerNorm(32) per pixel, ReLU, 1x1 conv 32 -> od as (preds [N,h,w,od-1] linear, conf [N,h,w] = 1 + exp); w1_packed [3,3,C,32],
+    ln_w / ln_b [32], w2 [od,32]"""
+    xt, yt = tabs if tabs is not None else (None, None)
+    _heads_in(x, xt, yt, w1_packed, b1, ln_w, ln_b, w2, b2)
+    N, h, w, C = x.shape
+    od = w2.shape[0]
+    if tuple(w1_packed.shape) != (3, 3, C, 32) or tuple(w2.shape) != (od, 32) or C % 16 or not 2 <= od <= 8:
+        raise RuntimeError("dualdpt_aux_tail_f32: weights do not fit the input")
+    if b1.numel() != 32 or ln_w.numel() != 32 or ln_b.numel() != 32 or b2.numel() != od:
+        raise RuntimeError("dualdpt_aux_tail_f32: biases / LayerNorm parameters do not fit 32 hidden channels and the output width")
+    if xt is not None and (tuple(xt.shape) != (w, C // 2) or tuple(yt.shape) != (h, C // 2)):
+        raise RuntimeError("dualdpt_aux_tail_f32: embedding tables do not fit the map")
+    preds = torch.empty(N, h, w, od - 1, device=x.device, dtype=torch.float32)
+    conf = torch.empty(N, h, w, device=x.device, dtype=torch.float32)
+    _timed("dualdpt_aux_tail_f32", 2.0 * N * h * w * (9 * C * 32 + 32 * od),
+           lambda: _lib.call("vgpa_dualdpt_aux_tail_f32", x, xt, yt, w1_packed, b1, ln_w, ln_b, float(eps), w2, b2, preds, conf, N, h, w, C, od, _stream()))
     return preds, conf
 
 

@@ -3,11 +3,10 @@
 contract and the same `compute_metrics` dispatch by metric name ("Consistency_Score" -> (score, motion_norm) tuple,
 "MVCS" -> needs depths / intrinsics / extrinsics, anything else -> compute(gt=, rep=)).
 
-What is NOT here: Depth Anything 3's DualDPT depth head (`depth` / `conf`) with its input resizing, and video
-decoding.  VGGT itself -- DINOv2 patch embedding, aggregator, camera head, depth and point heads -- is `videogpa_amd.vggt.VGGT` (pass it
-as `vggt_model=VGGT(...)`; any other `model(images) -> predictions` works the same way).  Of DA3, `videogpa_amd.da3.DA3Cameras` runs
-the backbone's tokens and the cameras (`extrinsics` / `intrinsics`) on the device; until the depth head is here a "da3" `backbone_fn`
-still brings the whole network.  They are passed in:
+What is NOT here: the input resizing of Depth Anything 3's api.py (cv2), and video decoding.  VGGT itself -- DINOv2
+patch embedding, aggregator, camera head, depth and point heads -- is `videogpa_amd.vggt.VGGT` (pass it as `vggt_model=VGGT(...)`; any
+other `model(images) -> predictions` works the same way).  Depth Anything 3 -- backbone, DualDPT depth head, camera decoder -- is
+`videogpa_amd.da3.DepthAnything3Net` (pass it as `da3_model=...` with frames already sized to multiples of 14).  Anything else is passed in:
   * `frame_sampler(video_path, n_frames) -> uint8 [T,H,W,3]`      (utils/video_utils.py:19-44, decord + cv2 upstream)
   * backbone "vggt":  `backbone_fn(frames) -> dict` with the keys utils/model_utils.py:89-122 returns
       images [T,3,H,W] in [0,1], world_points_from_depth [T,H,W,3], depth_conf [T,H,W], depth, and either
@@ -27,13 +26,17 @@ from . import scorer
 
 
 class VideoProcessor:
-    def __init__(self, metrics, model_name=None, device=None, backbone=None, backbone_fn=None, frame_sampler=None, vggt_model=None):
+    def __init__(self, metrics, model_name=None, device=None, backbone=None, backbone_fn=None, frame_sampler=None, vggt_model=None, da3_model=None):
         """First four arguments as the reference's (pipelines/process_video.py:17-29).  Where the reference loads VGGT-1B / DA3 weights
         itself, this class takes `backbone_fn` (and `frame_sampler` for paths): third-party networks and video decoding stay the caller's.
         `vggt_model(images [1,T,3,h,518]) -> predictions` is the bare VGGT network: with it the wrapper of utils/model_utils.py:89-122
-        (device preprocessing in front, batch squeeze and pose decoding behind) runs here instead of inside `backbone_fn`."""
+        (device preprocessing in front, batch squeeze and pose decoding behind) runs here instead of inside `backbone_fn`.
+        `da3_model(x [1,T,3,H,W], aux=False) -> {depth, depth_conf, extrinsics, intrinsics}` is the bare Depth Anything 3 network
+        (videogpa_amd.da3.DepthAnything3Net): with it the normalisation in front and the batch squeeze behind run here (`_run_da3`)."""
         if vggt_model is not None and backbone_fn is None:
             backbone_fn = lambda frames: self._run_vggt(vggt_model, frames)
+        if da3_model is not None and backbone_fn is None:
+            backbone_fn = lambda frames: self._run_da3(da3_model, frames)
         self.device = device or "cuda"
         self.metrics = metrics
         self.backbone = self._resolve_backbone(backbone, model_name)
@@ -89,6 +92,33 @@ class VideoProcessor:
         if "world_points" in preds:       # :116-117
             preds["world_points_from_depth"] = preds["world_points"]
         return preds
+
+    def _run_da3(self, model, frames):
+        """depth_anything_3/api.py:133-273 around the network, without its cv2 input resizing: uint8 frames [T,H,W,3] (array, tensor or list), H and W
+        multiples of 14 -> ImageNet normalisation on the device, the forward under no_grad + bf16 autocast with aux=False (the scorer reads depth and
+        conf only), and an object with what `_build_da3_predictions` reads, as device tensors: .processed_images [T,H,W,3] (the input frames), .depth
+        [T,H,W], .conf [T,H,W], .extrinsics [T,3,4], .intrinsics [T,3,3]"""
+        import types
+        dev = torch.device(self.device)
+        if isinstance(frames, (list, tuple)):
+            frames = torch.stack([torch.as_tensor(np.asarray(f) if not torch.is_tensor(f) else f) for f in frames])
+        frames = torch.as_tensor(np.asarray(frames) if not torch.is_tensor(frames) else frames)
+        if frames.ndim != 4 or frames.shape[-1] != 3 or frames.dtype != torch.uint8:
+            raise ValueError(f"da3_model takes uint8 frames [T,H,W,3], got {frames.dtype} {tuple(frames.shape)}")
+        H, W = frames.shape[1:3]
+        if H % 14 or W % 14:
+            raise ValueError(f"da3_model takes frames sized to multiples of 14, got {H} x {W}: the input resizing of depth_anything_3/api.py "
+                             "(cv2) is the caller's")
+        if hasattr(model, "to") and hasattr(model, "eval"):
+            model = model.to(dev).eval()
+        frames = frames.to(dev)
+        mean = torch.tensor([0.485, 0.456, 0.406], device=dev).view(1, 3, 1, 1)
+        std = torch.tensor([0.229, 0.224, 0.225], device=dev).view(1, 3, 1, 1)
+        x = ((frames.permute(0, 3, 1, 2).float() / 255.0 - mean) / std).unsqueeze(0).contiguous()
+        with torch.no_grad(), torch.autocast(dev.type, dtype=torch.bfloat16, enabled=dev.type == "cuda"):
+            out = model(x, aux=False)
+        return types.SimpleNamespace(processed_images=frames, depth=out["depth"].squeeze(0), conf=out["depth_conf"].squeeze(0),
+                                     extrinsics=out["extrinsics"].squeeze(0), intrinsics=out["intrinsics"].squeeze(0))
 
     def _process_vggt(self, frames, thresholds):
         preds = dict(self.backbone_fn(frames))

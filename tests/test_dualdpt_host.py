@@ -180,3 +180,36 @@ def test_ops_fail_loudly_without_gpu():
     m = small_net().to(torch.bfloat16)
     with torch.no_grad(), pytest.raises(RuntimeError, match="no CPU fallback"):
         m(torch.zeros(1, 2, 3, 42, 56, dtype=torch.bfloat16))
+
+
+def test_state_dict_order_is_the_one_before_the_shared_head():
+    """`state_dict()` key ORDER (the tests seed states from it) and shapes of both DPT heads and of VGGT at the reduced sizes against
+    tests/golden/state_dict_order.json: the `[[key, shape], ...]` lists of `state_dict().items()` as the commit before videogpa_amd/dpt.py gave them
+    (written from an export of that commit with the constructor arguments used below; 585 entries, hence a fixture and not a literal).  The three
+    presets on the meta device: backbone, head, camera decoder in that order, the head's names in the fixture's order, and for DA3-Large names and
+    shapes equal to the reference's lists (tests/golden/da3_names.json, dualdpt_names.json; those files are sorted, so they bound the set only)."""
+    import test_vggt_heads_host as V
+    from videogpa_amd.da3 import DepthAnything3Net, DualDPT
+    from videogpa_amd.vggt import DPTHead, VGGT
+    want = json.load(open(os.path.join(GOLDEN, "state_dict_order.json")))
+    ordered = lambda m: [[k, list(v.shape)] for k, v in m.state_dict().items()]
+    small = dict(aggregator_kwargs=dict(depth=4, num_heads=1), camera_kwargs=dict(trunk_depth=1, num_heads=2), dpt_kwargs=V.DPT_CFG_64)
+    got = {"DPTHead.depth": DPTHead(output_dim=2, activation="exp", **V.DPT_CFG), "DPTHead.point": DPTHead(output_dim=4, activation="inv_log", **V.DPT_CFG),
+           "DualDPT": DualDPT(**R.CFG), "VGGT": VGGT(img_size=28, patch_size=14, embed_dim=64, patch_embed="conv", **small)}
+    assert sorted(got) == sorted(want)
+    for name, module in got.items():
+        assert ordered(module) == want[name], name
+    meta, _ = load_golden()
+    assert dict(want["DualDPT"]) == meta["shapes"]
+    heads = torch.load(os.path.join(GOLDEN, "vggt_heads.pt"))["state"]
+    assert dict(want["DPTHead.depth"]) == {k: list(v.shape) for k, v in heads.items()}
+    names, head_names = json.load(open(os.path.join(GOLDEN, "da3_names.json"))), json.load(open(os.path.join(GOLDEN, "dualdpt_names.json")))
+    for preset in DepthAnything3Net.presets():
+        with torch.device("meta"):
+            keys = ordered(DepthAnything3Net.from_preset(preset))
+        groups = [k.split(".")[0] for k, _ in keys]
+        assert [g for i, g in enumerate(groups) if i == 0 or g != groups[i - 1]] == ["backbone", "head", "cam_dec"], preset
+        assert [k[len("head."):] for k, _ in keys if k.startswith("head.")] == [k for k, _ in want["DualDPT"]], preset
+        if preset == "da3-large":
+            assert dict(keys) == {**{"backbone." + k: v for k, v in names["backbone"].items()}, **{"head." + k: v for k, v in head_names.items()},
+                                  **{"cam_dec." + k: v for k, v in names["cam_dec"].items()}}

@@ -3,7 +3,12 @@
 //   CV_TAIL      the end of vggt's DPTHead: bilinear loader (+ embedding), epilogue bias + ReLU, 1x1 conv 32 -> od, activate_head
 //   CV_AUX_TAIL  the end of DA3's auxiliary branch (dualdpt.py:250-258): the loader reads the map as it is (+ embedding, zero padding), the epilogue
 //                is bias, LayerNorm over the 32 hidden channels of the pixel, ReLU, 1x1 conv 32 -> od, linear preds and conf = 1 + exp
-// The GEMM view, the tile shapes and the LDS layout are described at the top of vggt_heads.hip.
+//
+// GEMM view of the convolution: M = N * Ho * Wo output pixels (flat, so H and W are arbitrary), N = Cout, K = taps * Cin walked tap-major in
+// chunks of 16 channels.  A workgroup (4 waves) owns 128 pixels x BN channels; every thread owns ONE pixel of the A tile for the whole K loop
+// (its (n, y, x) is decoded once) and fetches 2 x 16 bytes of it per chunk, the next chunk's global loads are in flight while the MFMAs of
+// the current one run from LDS.  Both LDS tiles are k-major with a row stride = 32 (mod 64) dwords: lane l reads [k = l >> 5][l & 31], so
+// the two k rows of one ds_read fall into disjoint bank halves.  Both tails reuse the tiles' LDS for their 128 x 32 hidden values, [pixel][33].
 #pragma once
 #include "common.h"
 
@@ -63,6 +68,13 @@ __device__ __forceinline__ Lerp lerp_of(int dst, float scale, int in) {
     r.l0 = 1.0f - r.l1;
     return r;
 }
+// v + the 0.1-scaled UV embedding of pixel (y, x), channels c .. c + 3: the x half from xtab [W][half], the y half from ytab [H][half], where
+// half = C / 2 is a multiple of 4, so a float4 lies in one of the two
+__device__ __forceinline__ float4 embed4(float4 v, const float* __restrict__ xtab, const float* __restrict__ ytab, int half, int y, int x, int c) {
+    const float4 e = c < half ? *reinterpret_cast<const float4*>(xtab + (size_t)x * half + c)
+                              : *reinterpret_cast<const float4*>(ytab + (size_t)y * half + (c - half));
+    return make_float4(v.x + e.x, v.y + e.y, v.z + e.z, v.w + e.w);
+}
 // four channels of the interpolated (+ embedded) map at output pixel (oy, ox); base = frame n of the [h,w,C] source
 __device__ __forceinline__ float4 sample4(const float* __restrict__ base, int h, int w, int C, float sy, float sx, int oy, int ox, int c,
                                           const float* __restrict__ xtab, const float* __restrict__ ytab) {
@@ -72,14 +84,8 @@ __device__ __forceinline__ float4 sample4(const float* __restrict__ base, int h,
     const float4 v00 = *reinterpret_cast<const float4*>(r0 + (size_t)lx.i0 * C), v01 = *reinterpret_cast<const float4*>(r0 + (size_t)lx.i1 * C);
     const float4 v10 = *reinterpret_cast<const float4*>(r1 + (size_t)lx.i0 * C), v11 = *reinterpret_cast<const float4*>(r1 + (size_t)lx.i1 * C);
     const float4 top = f4_fma(lx.l0, v00, f4_scale(lx.l1, v01)), bot = f4_fma(lx.l0, v10, f4_scale(lx.l1, v11));
-    float4 v = f4_fma(ly.l0, top, f4_scale(ly.l1, bot));
-    if (xtab) {
-        const int half = C >> 1;
-        const float4 e = c < half ? *reinterpret_cast<const float4*>(xtab + (size_t)ox * half + c)
-                                  : *reinterpret_cast<const float4*>(ytab + (size_t)oy * half + (c - half));
-        v = make_float4(v.x + e.x, v.y + e.y, v.z + e.z, v.w + e.w);
-    }
-    return v;
+    const float4 v = f4_fma(ly.l0, top, f4_scale(ly.l1, bot));
+    return xtab ? embed4(v, xtab, ytab, C >> 1, oy, ox, c) : v;
 }
 
 template <int WM, int WN, int TM, int TN, int MODE>
@@ -126,15 +132,11 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
             const int half = a.Cin >> 1;
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
-                const int c = c0 + 4 * (jq + 2 * i);                          // Cin / 2 is a multiple of 8: a float4 lies in one half of the embedding
+                const int c = c0 + 4 * (jq + 2 * i);
                 float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
                 if (in) {
                     v = *reinterpret_cast<const float4*>(src + 4 * (jq + 2 * i));
-                    if (a.xtab) {
-                        const float4 e = c < half ? *reinterpret_cast<const float4*>(a.xtab + (size_t)ix * half + c)
-                                                  : *reinterpret_cast<const float4*>(a.ytab + (size_t)iy * half + (c - half));
-                        v = make_float4(v.x + e.x, v.y + e.y, v.z + e.z, v.w + e.w);
-                    }
+                    if (a.xtab) v = embed4(v, a.xtab, a.ytab, half, iy, ix, c);
                 }
                 ra[i] = v;
             }
@@ -236,66 +238,56 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
                 }
             }
         }
-    } else if constexpr (MODE == CV_AUX_TAIL) {
-        // hidden = conv + b1 -> LDS [pixel][33]; then one thread per pixel: LayerNorm over its 32 values (mean and the biased variance of the
-        // centred values by pairwise sums, so 32 equal values give variance 0 exactly), ReLU, the 1x1 conv 32 -> od, conf = 1 + exp
-        float* Hs = lds;
-        const float bv = a.bias[l31];
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            Hs[row * 33 + l31] = acc[0][0][r] + bv;
-        }
-        __syncthreads();
-        if (tid < CV_BM && p0 + tid < a.M) {
-            const int64_t q = p0 + tid;
-            float h[32], t[32];
-#pragma unroll
-            for (int c = 0; c < 32; ++c) t[c] = h[c] = Hs[tid * 33 + c];
-#pragma unroll
-            for (int n = 16; n >= 1; n >>= 1)
-#pragma unroll
-                for (int c = 0; c < n; ++c) t[c] += t[c + n];
-            const float mean = t[0] * (1.0f / 32.0f);
-#pragma unroll
-            for (int c = 0; c < 32; ++c) {
-                h[c] -= mean;
-                t[c] = h[c] * h[c];
-            }
-#pragma unroll
-            for (int n = 16; n >= 1; n >>= 1)
-#pragma unroll
-                for (int c = 0; c < n; ++c) t[c] += t[c + n];
-            const float rstd = rsqrtf(t[0] * (1.0f / 32.0f) + a.eps);
-#pragma unroll
-            for (int c = 0; c < 32; ++c) h[c] = fmaxf(h[c] * rstd * a.ln_w[c] + a.ln_b[c], 0.f);
-            for (int o = 0; o < a.od; ++o) {
-                float s = 0.f;
-#pragma unroll
-                for (int c = 0; c < 32; ++c) s = fmaf(a.w2[o * 32 + c], h[c], s);
-                s += a.b2[o];
-                if (o == a.od - 1) a.conf[q] = 1.0f + expf(s);
-                else a.preds[(size_t)q * (a.od - 1) + o] = s;
-            }
-        }
     } else {
-        // hidden = relu(conv + b1) -> LDS [pixel][33]; then one thread per pixel: the 1x1 conv 32 -> od and activate_head
+        // hidden = conv + b1 (CV_TAIL: its ReLU) -> LDS [pixel][33]
         float* Hs = lds;
         const float bv = a.bias[l31];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const int row = wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * lh;
-            Hs[row * 33 + l31] = fmaxf(acc[0][0][r] + bv, 0.f);
+            const float v = acc[0][0][r] + bv;
+            Hs[row * 33 + l31] = MODE == CV_TAIL ? fmaxf(v, 0.f) : v;
         }
         __syncthreads();
-        if (tid < CV_BM && p0 + tid < a.M) {
+        if (tid < CV_BM && p0 + tid < a.M) {                                  // one thread per pixel
             const int64_t q = p0 + tid;
+            [[maybe_unused]] float h[32];                                       // CV_AUX_TAIL: the normalised hidden values; CV_TAIL projects straight from LDS
+            if constexpr (MODE == CV_AUX_TAIL) {
+                // LayerNorm over the pixel's 32 values (mean and the biased variance of the centred values by pairwise sums, so 32 equal
+                // values give variance 0 exactly), then ReLU
+                float t[32];
+#pragma unroll
+                for (int c = 0; c < 32; ++c) t[c] = h[c] = Hs[tid * 33 + c];
+#pragma unroll
+                for (int n = 16; n >= 1; n >>= 1)
+#pragma unroll
+                    for (int c = 0; c < n; ++c) t[c] += t[c + n];
+                const float mean = t[0] * (1.0f / 32.0f);
+#pragma unroll
+                for (int c = 0; c < 32; ++c) {
+                    h[c] -= mean;
+                    t[c] = h[c] * h[c];
+                }
+#pragma unroll
+                for (int n = 16; n >= 1; n >>= 1)
+#pragma unroll
+                    for (int c = 0; c < n; ++c) t[c] += t[c + n];
+                const float rstd = rsqrtf(t[0] * (1.0f / 32.0f) + a.eps);
+#pragma unroll
+                for (int c = 0; c < 32; ++c) h[c] = fmaxf(h[c] * rstd * a.ln_w[c] + a.ln_b[c], 0.f);
+            }
+            // the 1x1 conv 32 -> od: the last output is conf = 1 + exp, the others are preds, written as they are (CV_AUX_TAIL) or through
+            // activate_head (CV_TAIL)
             for (int o = 0; o < a.od; ++o) {
                 float s = 0.f;
 #pragma unroll
-                for (int c = 0; c < 32; ++c) s = fmaf(a.w2[o * 32 + c], Hs[tid * 33 + c], s);
+                for (int c = 0; c < 32; ++c) {
+                    if constexpr (MODE == CV_AUX_TAIL) s = fmaf(a.w2[o * 32 + c], h[c], s);
+                    else s = fmaf(a.w2[o * 32 + c], Hs[tid * 33 + c], s);
+                }
                 s += a.b2[o];
                 if (o == a.od - 1) a.conf[q] = 1.0f + expf(s);
+                else if constexpr (MODE == CV_AUX_TAIL) a.preds[(size_t)q * (a.od - 1) + o] = s;
                 else a.preds[(size_t)q * (a.od - 1) + o] = a.act == 0 ? expf(s) : copysignf(expm1f(fabsf(s)), s);
             }
         }
@@ -303,6 +295,22 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
 }
 
 static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// The checks and the ConvArgs fill that the two tail entry points share: x [N,h,w,C] read on an [N,H,W] output grid, 32 hidden channels, od outputs.
+// An entry adds its own checks and fields (activation and scales; LayerNorm parameters) and launches.
+static int32_t tail_args(ConvArgs& a, const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* w2,
+                         const float* b2, float* preds, float* conf, int64_t N, int64_t h, int64_t w, int64_t C, int64_t H, int64_t W, int32_t od) {
+    if (!x || !w1_packed || !b1 || !w2 || !b2 || !preds || !conf || N <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 15))
+        return VGPA_ERR_INVALID;
+    if ((xtab == nullptr) != (ytab == nullptr) || od < 2 || od > 8) return VGPA_ERR_INVALID;
+    if (h > (1 << 20) || w > (1 << 20) || H > (1 << 20) || W > (1 << 20) || C > (1 << 20)) return VGPA_ERR_INVALID;
+    if (!aligned16(x) || !aligned16(w1_packed) || !aligned16(xtab) || !aligned16(ytab)) return VGPA_ERR_INVALID;
+    a.x = x; a.w = w1_packed; a.bias = b1; a.xtab = xtab; a.ytab = ytab; a.w2 = w2; a.b2 = b2; a.preds = preds; a.conf = conf;
+    a.N = (int)N; a.H = (int)h; a.W = (int)w; a.Ho = (int)H; a.Wo = (int)W; a.Cin = (int)C; a.Cout = 32; a.ksize = 3; a.stride = 1;
+    a.od = od;
+    a.M = N * H * W;
+    return VGPA_OK;
+}
 
 template <int MODE>
 static int32_t conv_launch(const ConvArgs& a, hipStream_t stream) {

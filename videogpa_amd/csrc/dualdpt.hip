@@ -12,17 +12,10 @@ extern "C" {
 int32_t vgpa_dualdpt_aux_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* ln_w,
                                   const float* ln_b, float eps, const float* w2, const float* b2, float* preds, float* conf, int64_t N, int64_t h,
                                   int64_t w, int64_t C, int32_t output_dim, hipStream_t stream) {
-    if (!x || !w1_packed || !b1 || !ln_w || !ln_b || !w2 || !b2 || !preds || !conf || N <= 0 || h <= 0 || w <= 0 || C <= 0 || (C & 15))
-        return VGPA_ERR_INVALID;
-    if ((xtab == nullptr) != (ytab == nullptr) || output_dim < 2 || output_dim > 8 || !(eps >= 0.f)) return VGPA_ERR_INVALID;
-    if (h > (1 << 20) || w > (1 << 20) || C > (1 << 20)) return VGPA_ERR_INVALID;
-    if (!aligned16(x) || !aligned16(w1_packed) || !aligned16(xtab) || !aligned16(ytab)) return VGPA_ERR_INVALID;
     ConvArgs a = {};
-    a.x = x; a.w = w1_packed; a.bias = b1; a.xtab = xtab; a.ytab = ytab; a.w2 = w2; a.b2 = b2; a.preds = preds; a.conf = conf;
+    const int32_t rc = tail_args(a, x, xtab, ytab, w1_packed, b1, w2, b2, preds, conf, N, h, w, C, h, w, output_dim);
+    if (rc != VGPA_OK || !ln_w || !ln_b || !(eps >= 0.f)) return VGPA_ERR_INVALID;
     a.ln_w = ln_w; a.ln_b = ln_b; a.eps = eps;
-    a.N = (int)N; a.H = (int)h; a.W = (int)w; a.Ho = (int)h; a.Wo = (int)w; a.Cin = (int)C; a.Cout = 32; a.ksize = 3; a.stride = 1;
-    a.od = output_dim;
-    a.M = N * h * w;
     return conv_launch<CV_AUX_TAIL>(a, stream);
 }
 

@@ -10,11 +10,7 @@
 //   upsample_kernel                 NHWC align_corners=True bilinear resize (+ the same separable embedding)
 //   attn_small_kernel               fp32 softmax attention of the camera trunk, S <= 128 tokens, one workgroup per (batch, head)
 //
-// The convolution core lives in conv_mfma.h (csrc/dualdpt.hip instantiates a third mode of it).  GEMM view of the convolution: M = N * Ho * Wo output pixels (flat, so H and W are arbitrary), N = Cout, K = taps * Cin walked tap-major in
-// chunks of 16 channels.  A workgroup (4 waves) owns 128 pixels x BN channels; every thread owns ONE pixel of the A tile for the whole K loop
-// (its (n, y, x) is decoded once) and fetches 2 x 16 bytes of it per chunk, the next chunk's global loads are in flight while the MFMAs of
-// the current one run from LDS.  Both LDS tiles are k-major with a row stride = 32 (mod 64) dwords: lane l reads [k = l >> 5][l & 31], so
-// the two k rows of one ds_read fall into disjoint bank halves.
+// The convolution core, with its GEMM view, tile shapes and LDS layout, lives in conv_mfma.h (csrc/dualdpt.hip instantiates a third mode of it).
 #include "conv_mfma.h"
 
 __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__ x, int h, int w, int C, int Ho, int Wo, float sy, float sx,
@@ -120,18 +116,12 @@ int32_t vgpa_conv1x1_f32(const float* x, const float* w_packed, const float* bia
 int32_t vgpa_dpt_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* w2,
                           const float* b2, float* preds, float* conf, int64_t N, int64_t h, int64_t w, int64_t C, int64_t H, int64_t W,
                           int32_t output_dim, int32_t activation, hipStream_t stream) {
-    if (!x || !w1_packed || !b1 || !w2 || !b2 || !preds || !conf || N <= 0 || h <= 0 || w <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 15))
-        return VGPA_ERR_INVALID;
-    if ((xtab == nullptr) != (ytab == nullptr) || output_dim < 2 || output_dim > 8 || (activation != 0 && activation != 1)) return VGPA_ERR_INVALID;
-    if (h > (1 << 20) || w > (1 << 20) || H > (1 << 20) || W > (1 << 20) || C > (1 << 20)) return VGPA_ERR_INVALID;
-    if (!aligned16(x) || !aligned16(w1_packed) || !aligned16(xtab) || !aligned16(ytab)) return VGPA_ERR_INVALID;
     ConvArgs a = {};
-    a.x = x; a.w = w1_packed; a.bias = b1; a.xtab = xtab; a.ytab = ytab; a.w2 = w2; a.b2 = b2; a.preds = preds; a.conf = conf;
-    a.N = (int)N; a.H = (int)h; a.W = (int)w; a.Ho = (int)H; a.Wo = (int)W; a.Cin = (int)C; a.Cout = 32; a.ksize = 3; a.stride = 1;
-    a.od = output_dim; a.act = activation;
+    const int32_t rc = tail_args(a, x, xtab, ytab, w1_packed, b1, w2, b2, preds, conf, N, h, w, C, H, W, output_dim);
+    if (rc != VGPA_OK || (activation != 0 && activation != 1)) return VGPA_ERR_INVALID;
+    a.act = activation;
     a.sy = H > 1 ? (float)(h - 1) / (float)(H - 1) : 0.f;
     a.sx = W > 1 ? (float)(w - 1) / (float)(W - 1) : 0.f;
-    a.M = N * H * W;
     return conv_launch<CV_TAIL>(a, stream);
 }
 

@@ -7,8 +7,9 @@ runs for `depth` / `depth_conf` / `ray` / `ray_conf` / `extrinsics` / `intrinsic
     DinoV2                  depth_anything_3/model/dinov2/dinov2.py:22-64               (the network under `.pretrained`; "vits" | "vitb" | "vitl")
     CameraDec               depth_anything_3/model/cam_dec.py:19-45
     decode_cameras          da3.py:209-221, model/utils/transform.py:41-65, utils/geometry.py:55-59
-    DualDPT                 depth_anything_3/model/dualdpt.py:30-364, model/dpt.py (_make_scratch, _make_fusion_block): fp32 on the convolution kernels
-                            of csrc/vggt_heads.hip plus the auxiliary tail of csrc/dualdpt.hip
+    DualDPT                 depth_anything_3/model/dualdpt.py:30-364, model/dpt.py (_make_scratch, _make_fusion_block): the head shared with VGGT
+                            (videogpa_amd/dpt.py, fp32 on the convolution kernels of csrc/vggt_heads.hip) plus the auxiliary branch, whose tail is
+                            csrc/dualdpt.hip
     DepthAnything3Net       da3.py:40-221 without cam_enc, the GS heads, ray-pose and exported feature layers
     DA3Cameras              backbone + camera decoder only, for callers that want the cameras and bring no head
 
@@ -19,7 +20,6 @@ sits between the blocks is csrc/da3.hip: the selected view stays in a device buf
 decoder and the pose decoding compute in fp32 with autocast off, as upstream (da3.py:139).  Forward only."""
 import functools
 import itertools
-import os
 
 import torch
 import torch.nn as nn
@@ -27,6 +27,8 @@ import torch.nn.functional as F
 
 from . import ops
 from . import vggt
+from ._nn import _forward_only, read_checkpoint
+from .dpt import DPTBase
 from .transformer import _f32
 
 THRESH_FOR_REF_SELECTION = 3          # depth_anything_3/utils/constants.py:19
@@ -227,7 +229,7 @@ class DA3Cameras(nn.Module):
         return sorted(met)
 
     def forward(self, images, cam_token=None, ref_view_strategy="saddle_balanced"):
-        vggt._forward_only(self, images)
+        _forward_only(self, images)
         feats, _ = self.backbone(images, cam_token=cam_token, ref_view_strategy=ref_view_strategy)
         pose_enc = self.cam_dec(feats[-1][1])
         extrinsics, intrinsics = decode_cameras(pose_enc, images.shape[-2:])
@@ -259,155 +261,68 @@ class _Permute(nn.Module):
         return x.permute(*self.dims)
 
 
-class DualDPT(nn.Module):
-    """depth_anything_3/model/dualdpt.py:30-364 on the HIP kernels, channels-last from the tokens to the outputs, laid out as vggt.DPTHead:
+class DualDPT(DPTBase):
+    """depth_anything_3/model/dualdpt.py:30-364 on the shared head of videogpa_amd/dpt.py, with a second fusion chain and an auxiliary tail:
     `forward(feats, H, W, patch_start_idx, chunk_size=8, aux=True)` with `feats` = what DinoV2 returns (four (features [B,S,P,dim_in], camera token)
     pairs) -> an attribute-access dict {depth [B,S,H,W] (exp), depth_conf [B,S,H,W] (1 + exp), ray [B,S,8ph,8pw,6] (linear), ray_conf [B,S,8ph,8pw]
     (1 + exp)}, the key names from `head_names`.  aux=False (not upstream's) skips the auxiliary fusion chain, its five-convolution neck and its
     tail -- about half of the head -- and returns the first two keys only.  The modules hold the parameters under the reference's names and shapes
-    (`scratch.output_conv{1,2}_aux.{0,1,2}` included, which no forward reads); the arithmetic is
+    (`scratch.output_conv{1,2}_aux.{0,1,2}` included, which no forward reads).  The auxiliary branch is refinenet4..1_aux on the same four `rn`
+    maps, `output_conv1_aux.3` as five ops.conv3x3_f32, and ops.dualdpt_aux_tail_f32.  Every frame is computed independently of the others, so the
+    result does not depend on `chunk_size` (upstream chunks the flattened B*S when chunk_size < S)."""
 
-        LayerNorm (torch) -> projects.N, resize_layers.{0,1} as 1x1 convolutions (+ pixel shuffle) -> resize_layers.3 / layerN_rn /
-        ResidualConvUnits / output_conv1 / output_conv1_aux.3 as ops.conv3x3_f32 with ReLU, bias and residual adds fused -> out_conv BEFORE the
-        bilinear upsample (both linear, the interpolation weights sum to 1) -> ops.dpt_tail_f32 (main) and ops.dualdpt_aux_tail_f32 (auxiliary).
-
-    Unlike VGGT's head, a ResidualConvUnit's ReLU is not in place here: the tensor added back is x itself (relu_res=False), and the four `rn` maps
-    feed both fusion chains unchanged.  The UV embedding follows DA3's float32 angles (ops.uv_embed_tables(f32_angles=True)).  Every frame is
-    computed independently of the others, so the result does not depend on `chunk_size` (upstream chunks the flattened B*S when chunk_size < S).
-    fp32 whatever autocast says; forward only."""
-
-    _conv, _deconv = vggt.DPTHead._conv, vggt.DPTHead._deconv
+    RELU_RESIDUAL = False          # the two differences from vggt.DPTHead: see dpt.DPTBase
+    F32_ANGLES = True
 
     def __init__(self, dim_in, *, patch_size=14, output_dim=2, activation="exp", conf_activation="expp1", features=256,
                  out_channels=(256, 512, 1024, 1024), pos_embed=True, down_ratio=1, aux_pyramid_levels=4, aux_out1_conv_num=5,
                  head_names=("depth", "ray")):
-        super().__init__()
         if down_ratio != 1 or activation != "exp" or conf_activation != "expp1" or aux_pyramid_levels != 4 or aux_out1_conv_num != 5:
             raise NotImplementedError("DualDPT on the HIP path: down_ratio=1, activation='exp', conf_activation='expp1', aux_pyramid_levels=4, "
                                       "aux_out1_conv_num=5 (no DA3 configuration builds anything else)")
-        out_channels = list(out_channels)
-        if dim_in % 16 or features % 32 or len(out_channels) != 4 or any(c % 16 for c in out_channels) or not 2 <= output_dim <= 8:
-            raise NotImplementedError("DualDPT on the HIP path: four stages, dim_in and out_channels in multiples of 16, features in multiples of 32")
-        self.patch_size, self.activation, self.conf_activation, self.pos_embed, self.down_ratio = patch_size, activation, conf_activation, pos_embed, down_ratio
+        super().__init__(dim_in, patch_size, output_dim, activation, conf_activation, features, out_channels, pos_embed, down_ratio, chains=("", "_aux"))
         self.aux_levels, self.aux_out1_conv_num = aux_pyramid_levels, aux_out1_conv_num
         self.head_main, self.head_aux = head_names
         self.intermediate_layer_idx = (0, 1, 2, 3)
-        self.norm = nn.LayerNorm(dim_in)
-        self.projects = nn.ModuleList([nn.Conv2d(dim_in, oc, kernel_size=1, stride=1, padding=0) for oc in out_channels])
-        self.resize_layers = nn.ModuleList([
-            nn.ConvTranspose2d(out_channels[0], out_channels[0], kernel_size=4, stride=4, padding=0),
-            nn.ConvTranspose2d(out_channels[1], out_channels[1], kernel_size=2, stride=2, padding=0),
-            nn.Identity(),
-            nn.Conv2d(out_channels[3], out_channels[3], kernel_size=3, stride=2, padding=1)])
-        sc = self.scratch = nn.Module()
-        for i, c in enumerate(out_channels):
-            setattr(sc, f"layer{i + 1}_rn", nn.Conv2d(c, features, kernel_size=3, stride=1, padding=1, bias=False))
-        for suffix in ("", "_aux"):
-            for k in (1, 2, 3, 4):
-                setattr(sc, f"refinenet{k}{suffix}", vggt._FeatureFusionBlock(features, has_residual=k != 4))
         half = features // 2
         conv3 = lambda i, o: nn.Conv2d(i, o, kernel_size=3, stride=1, padding=1)
-        sc.output_conv1 = conv3(features, half)
-        sc.output_conv2 = nn.Sequential(conv3(half, 32), nn.ReLU(inplace=True), nn.Conv2d(32, output_dim, kernel_size=1, stride=1, padding=0))
+        sc = self.scratch
         sc.output_conv1_aux = nn.ModuleList([nn.Sequential(conv3(features, half), conv3(half, features), conv3(features, half), conv3(half, features),
                                                            conv3(features, half)) for _ in range(self.aux_levels)])
         sc.output_conv2_aux = nn.ModuleList([nn.Sequential(conv3(half, 32), _Permute((0, 2, 3, 1)), nn.LayerNorm(32), _Permute((0, 3, 1, 2)),
                                                            nn.ReLU(inplace=True), nn.Conv2d(32, 7, kernel_size=1, stride=1, padding=0))
                                              for _ in range(self.aux_levels)])
-        self._packed = vggt._PackedCache()
-        self._tabs = {}
 
-    def _embed(self, width, height, channels, aspect, device):
-        key = (width, height, channels, aspect, str(device))
-        if key not in self._tabs:
-            if len(self._tabs) > 64:
-                self._tabs.clear()
-            self._tabs[key] = ops.uv_embed_tables(width, height, channels, aspect, device, f32_angles=True)
-        return self._tabs[key]
-
-    def _vec(self, name, *params):
-        """small parameters as fp32 contiguous tensors (the 1x1 weights as [od, 32])"""
-        return self._packed.get(name, list(params), lambda: tuple(p.detach().float().reshape(-1, 32).contiguous() if p.ndim == 4 else
-                                                                  p.detach().float().contiguous() for p in params))
-
-    # ---- forward
     def forward(self, feats, H, W, patch_start_idx, chunk_size=8, aux=True):
         tokens = [f[0] for f in feats]
         if len(tokens) != 4:
             raise ValueError(f"DualDPT reads four (features, camera token) pairs, got {len(tokens)}")
-        vggt._forward_only(self, *tokens)
+        _forward_only(self, *tokens)
         B, S, N, C = tokens[0].shape
         if H % self.patch_size or W % self.patch_size or N - patch_start_idx != (H // self.patch_size) * (W // self.patch_size):
             raise ValueError(f"DualDPT: {N - patch_start_idx} patch tokens do not make the {H // self.patch_size} x {W // self.patch_size} grid of a "
                              f"{H} x {W} frame (sizes in multiples of {self.patch_size})")
         with torch.autocast(tokens[0].device.type, enabled=False):
-            flat = [t.reshape(B * S, N, C) for t in tokens]
+            flat = [t.reshape(B * S, N, C)[:, patch_start_idx:] for t in tokens]
             if chunk_size is None or chunk_size >= S:
-                parts = [self._forward_impl(flat, H, W, patch_start_idx, aux)]
+                parts = [self._forward_impl(flat, H, W, aux)]
             else:
                 assert chunk_size > 0
-                parts = [self._forward_impl([t[s0:s0 + chunk_size] for t in flat], H, W, patch_start_idx, aux) for s0 in range(0, B * S, chunk_size)]
+                parts = [self._forward_impl([t[s0:s0 + chunk_size] for t in flat], H, W, aux) for s0 in range(0, B * S, chunk_size)]
             out = {k: (parts[0][k] if len(parts) == 1 else torch.cat([p[k] for p in parts], dim=0)) for k in parts[0]}
             return _AttrDict({k: v.reshape(B, S, *v.shape[1:]) for k, v in out.items()})
 
-    def _rcu(self, name, unit, x, extra=None):
-        """conv2(relu(conv1(relu(x)))) + x (+ extra): two launches; x is left as it is"""
-        w1, b1 = self._conv(name + ".conv1", unit.conv1)
-        w2, b2 = self._conv(name + ".conv2", unit.conv2)
-        t = ops.conv3x3_f32(x, w1, b1, relu_in=True)
-        return ops.conv3x3_f32(t, w2, b2, res=x, res2=extra, relu_in=True, relu_res=False)
-
-    def _fuse(self, name, x0, x1, size):
-        block = getattr(self.scratch, name)
-        out = self._rcu(name + ".resConfUnit1", block.resConfUnit1, x1, extra=x0) if block.has_residual else x0
-        out = self._rcu(name + ".resConfUnit2", block.resConfUnit2, out)
-        out = ops.conv1x1_f32(out, *self._conv(name + ".out_conv", block.out_conv))
-        return ops.upsample_bilinear_ac_f32(out, size[0], size[1])
-
-    def _chain(self, rn, suffix):
-        """refinenet4..1 (suffix "") or refinenet4..1_aux on the four rn maps; refinenet1 upsamples by scale_factor=2"""
-        out = self._fuse("refinenet4" + suffix, rn[3], None, rn[2].shape[1:3])
-        out = self._fuse("refinenet3" + suffix, out, rn[2], rn[1].shape[1:3])
-        out = self._fuse("refinenet2" + suffix, out, rn[1], rn[0].shape[1:3])
-        return self._fuse("refinenet1" + suffix, out, rn[0], (2 * rn[0].shape[1], 2 * rn[0].shape[2]))
-
-    def _forward_impl(self, flat, H, W, patch_start_idx, aux):
-        ph, pw = H // self.patch_size, W // self.patch_size
-        n = flat[0].shape[0]
-        feats = []
-        for i, layer_idx in enumerate(self.intermediate_layer_idx):
-            x = flat[layer_idx][:, patch_start_idx:].float()
-            x = F.layer_norm(x, self.norm.normalized_shape, self.norm.weight.float(), self.norm.bias.float(), self.norm.eps).contiguous()
-            x = ops.conv1x1_f32(x, *self._conv(f"projects.{i}", self.projects[i])).reshape(n, ph, pw, -1)
-            if self.pos_embed:
-                x = ops.upsample_bilinear_ac_f32(x, ph, pw, self._embed(pw, ph, x.shape[-1], W / H, x.device))
-            layer = self.resize_layers[i]
-            if isinstance(layer, nn.ConvTranspose2d):
-                k, oc = layer.kernel_size[0], layer.out_channels
-                x = ops.conv1x1_f32(x, *self._deconv(f"resize_layers.{i}", layer)).reshape(n, ph, pw, k, k, oc)
-                x = x.permute(0, 1, 3, 2, 4, 5).reshape(n, ph * k, pw * k, oc).contiguous()
-            elif isinstance(layer, nn.Conv2d):
-                x = ops.conv3x3_f32(x, *self._conv(f"resize_layers.{i}", layer), stride=2)
-            feats.append(x)
-        sc = self.scratch
-        rn = [ops.conv3x3_f32(f, self._conv(f"layer{i + 1}_rn", getattr(sc, f"layer{i + 1}_rn"))[0]) for i, f in enumerate(feats)]
-        del feats
-        # main branch: output_conv1 at the fused resolution, then upsample to (14ph, 14pw) + embedding + output_conv2 + activations in one launch
-        out = ops.conv3x3_f32(self._chain(rn, ""), *self._conv("output_conv1", sc.output_conv1))
-        Ho, Wo = ph * self.patch_size, pw * self.patch_size
-        w1, b1 = self._conv("output_conv2.0", sc.output_conv2[0])
-        w2, b2 = self._vec("output_conv2.2", sc.output_conv2[2].weight, sc.output_conv2[2].bias)
-        tabs = self._embed(Wo, Ho, out.shape[-1], W / H, out.device) if self.pos_embed else None
-        preds, conf = ops.dpt_tail_f32(out, Ho, Wo, w1, b1, w2, b2, activation=self.activation, tabs=tabs)
+    def _forward_impl(self, tokens, H, W, aux):
+        rn, ph, pw, aspect = self._pyramid(tokens, H, W)
+        preds, conf = self._main_tail(list(rn), ph, pw, aspect)                     # a list of its own: the auxiliary chain reads the maps again
         result = {self.head_main: preds.squeeze(-1) if preds.shape[-1] == 1 else preds, f"{self.head_main}_conf": conf}
-        del out, preds, conf
         if aux:
-            # auxiliary branch: its own fusion chain, the last level's five plain convolutions, then embedding + conv + LayerNorm + ReLU + 1x1
+            # its own fusion chain, the last level's five plain convolutions, then embedding + conv + LayerNorm + ReLU + 1x1 in one launch
             a = self._chain(rn, "_aux")
             last = self.aux_levels - 1
-            for j, conv in enumerate(sc.output_conv1_aux[last]):
+            for j, conv in enumerate(self.scratch.output_conv1_aux[last]):
                 a = ops.conv3x3_f32(a, *self._conv(f"output_conv1_aux.{last}.{j}", conv))
-            seq = sc.output_conv2_aux[last]
+            seq = self.scratch.output_conv2_aux[last]
             w1, b1 = self._conv(f"output_conv2_aux.{last}.0", seq[0])
             ln_w, ln_b = self._vec(f"output_conv2_aux.{last}.2", seq[2].weight, seq[2].bias)
             w2, b2 = self._vec(f"output_conv2_aux.{last}.5", seq[5].weight, seq[5].bias)
@@ -426,23 +341,6 @@ _PRESETS = {
     "da3-large": dict(net=dict(name="vitl", out_layers=[11, 15, 19, 23], alt_start=8, qknorm_start=8, rope_start=8, cat_token=True),
                       head=dict(dim_in=2048, output_dim=2, features=256, out_channels=[256, 512, 1024, 1024]), cam_dec=dict(dim_in=2048)),
 }
-
-
-def _read_checkpoint(path):
-    """a state dict from the LOCAL file system (never the network), as vggt.VGGT.from_pretrained reads one: a directory holding model.safetensors or
-    model.pt, or such a file"""
-    path = os.fspath(path)
-    if os.path.isdir(path):
-        found = [f for f in ("model.safetensors", "model.pt") if os.path.isfile(os.path.join(path, f))]
-        if not found:
-            raise FileNotFoundError(f"{path}: neither model.safetensors nor model.pt (from_pretrained reads local checkpoints only)")
-        path = os.path.join(path, found[0])
-    elif not os.path.isfile(path):
-        raise FileNotFoundError(f"{path}: no such checkpoint file or directory (from_pretrained reads local checkpoints only)")
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        return load_file(path)
-    return torch.load(path, map_location="cpu", weights_only=True)
 
 
 class DepthAnything3Net(nn.Module):
@@ -474,7 +372,7 @@ class DepthAnything3Net(nn.Module):
         """A DA3 checkpoint from the LOCAL file system (never the network): `path` is a directory holding model.safetensors or model.pt, or such a
         file; `preset` names its configuration."""
         model = cls.from_preset(preset)
-        model.load_state_dict(_read_checkpoint(path), strict=True)
+        model.load_state_dict(read_checkpoint(path), strict=True)
         return model.eval()
 
     def load_state_dict(self, state_dict, strict=True, **kw):
@@ -503,7 +401,7 @@ class DepthAnything3Net(nn.Module):
             raise NotImplementedError("use_ray_pose: the ray-based pose estimation is not built (cameras come from cam_dec)")
         if export_feat_layers is not None and len(export_feat_layers):
             raise NotImplementedError("export_feat_layers: auxiliary feature maps are not built (no VideoGPA path asks for them)")
-        vggt._forward_only(self, x)
+        _forward_only(self, x)
         feats, _ = self.backbone(x, cam_token=None, ref_view_strategy=ref_view_strategy)
         H, W = x.shape[-2:]
         with torch.autocast(x.device.type, enabled=False):

@@ -16,7 +16,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .vggt import _PackedCache
+from ._nn import _PackedCache, read_state_file as _read
 
 # torchvision `vgg16().features` indices of the convolutions of the five slices (relu1_2, relu2_2, relu3_3, relu4_3, relu5_3) and their widths
 SLICES = ((0, 2), (5, 7), (10, 12, 14), (17, 19, 21), (24, 26, 28))
@@ -55,13 +55,6 @@ class _VGG16Slices(nn.Module):
 
     def convs(self):
         return [[getattr(getattr(self, f"slice{k + 1}"), str(i)) for i in idx] for k, idx in enumerate(SLICES)]
-
-
-def _read(path):
-    if path.endswith(".safetensors"):
-        from safetensors.torch import load_file
-        return load_file(path)
-    return torch.load(path, map_location="cpu", weights_only=True)
 
 
 class LPIPS(nn.Module):

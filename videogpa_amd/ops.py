@@ -1298,14 +1298,14 @@ def rope2d_tables(pos, head_dim=64, frequency=100.0):
     return ang.cos().contiguous(), ang.sin().contiguous()
 
 
-# ---- VGGT prediction heads (csrc/vggt_heads.hip): fp32, channels-last, forward only ------------------------------------------------------
+# ---- prediction heads of VGGT and Depth Anything 3 (csrc/vggt_heads.hip, csrc/dualdpt.hip): fp32, channels-last, forward only ----------------
 def _heads_in(*ts):
     for t in ts:
         if t is None:
             continue
         _req(t, torch.float32)
         if torch.is_grad_enabled() and t.requires_grad:
-            raise RuntimeError("the VGGT head kernels are forward only: call them under torch.no_grad()")
+            raise RuntimeError("the fp32 head kernels are forward only: call them under torch.no_grad()")
 
 
 def pack_conv_weight(w):
@@ -1382,19 +1382,25 @@ def upsample_bilinear_ac_f32(x, H, W, tabs=None):
 _DPT_ACT = {"exp": 0, "inv_log": 1}
 
 
+def _tail_fits(name, x, H, W, w1_packed, w2, xt, yt, grid):
+    """the shape checks the two tails share: x [N,h,w,C], w1_packed [3,3,C,32], w2 [od,32], the tables on the [H,W] output grid"""
+    C, od = x.shape[3], w2.shape[0]
+    if tuple(w1_packed.shape) != (3, 3, C, 32) or tuple(w2.shape) != (od, 32) or C % 16:
+        raise RuntimeError(f"{name}: weights do not fit the input")
+    if xt is not None and (tuple(xt.shape) != (W, C // 2) or tuple(yt.shape) != (H, C // 2)):
+        raise RuntimeError(f"{name}: embedding tables do not fit the {grid}")
+
+
 def dpt_tail_f32(x, H, W, w1_packed, b1, w2, b2, activation="exp", tabs=None):
-    """The end of DPTHead._forward_impl in one launch: x [N,h,w,C] -> (preds [N,H,W,output_dim-1], conf [N,H,W]); w1_packed [3,3,C,32],
-    w2 [output_dim,32]; confidence activation expp1"""
+    """The main end of the DPT heads (dpt.DPTBase._main_tail) in one launch: x [N,h,w,C] -> (preds [N,H,W,output_dim-1], conf [N,H,W]);
+    w1_packed [3,3,C,32], w2 [output_dim,32]; confidence activation expp1"""
     xt, yt = tabs if tabs is not None else (None, None)
     _heads_in(x, xt, yt, w1_packed, b1, w2, b2)
     if activation not in _DPT_ACT:
         raise NotImplementedError(f"dpt_tail_f32: activation {activation!r} (exp and inv_log are built)")
     N, h, w, C = x.shape
     od = w2.shape[0]
-    if tuple(w1_packed.shape) != (3, 3, C, 32) or w2.shape[1] != 32 or C % 16:
-        raise RuntimeError("dpt_tail_f32: weights do not fit the input")
-    if xt is not None and (tuple(xt.shape) != (W, C // 2) or tuple(yt.shape) != (H, C // 2)):
-        raise RuntimeError("dpt_tail_f32: embedding tables do not fit the output")
+    _tail_fits("dpt_tail_f32", x, H, W, w1_packed, w2, xt, yt, "output")
     preds = torch.empty(N, H, W, od - 1, device=x.device, dtype=torch.float32)
     conf = torch.empty(N, H, W, device=x.device, dtype=torch.float32)
     _timed("dpt_tail_f32", 2.0 * N * H * W * (9 * C * 32 + 32 * od),
@@ -1410,12 +1416,11 @@ def dualdpt_aux_tail_f32(x, w1_packed, b1, ln_w, ln_b, eps, w2, b2, tabs=None):
     _heads_in(x, xt, yt, w1_packed, b1, ln_w, ln_b, w2, b2)
     N, h, w, C = x.shape
     od = w2.shape[0]
-    if tuple(w1_packed.shape) != (3, 3, C, 32) or tuple(w2.shape) != (od, 32) or C % 16 or not 2 <= od <= 8:
+    if not 2 <= od <= 8:
         raise RuntimeError("dualdpt_aux_tail_f32: weights do not fit the input")
+    _tail_fits("dualdpt_aux_tail_f32", x, h, w, w1_packed, w2, xt, yt, "map")
     if b1.numel() != 32 or ln_w.numel() != 32 or ln_b.numel() != 32 or b2.numel() != od:
         raise RuntimeError("dualdpt_aux_tail_f32: biases / LayerNorm parameters do not fit 32 hidden channels and the output width")
-    if xt is not None and (tuple(xt.shape) != (w, C // 2) or tuple(yt.shape) != (h, C // 2)):
-        raise RuntimeError("dualdpt_aux_tail_f32: embedding tables do not fit the map")
     preds = torch.empty(N, h, w, od - 1, device=x.device, dtype=torch.float32)
     conf = torch.empty(N, h, w, device=x.device, dtype=torch.float32)
     _timed("dualdpt_aux_tail_f32", 2.0 * N * h * w * (9 * C * 32 + 32 * od),

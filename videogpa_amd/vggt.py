@@ -29,17 +29,19 @@ The prediction heads are reference-held too and sit below the aggregator (fp32, 
 tests/golden/vggt_heads.pt, tests/test_gpu_vggt_heads.py):
 
     CameraHead               vggt/heads/camera_head.py:19-149 (trunk of head_dim-128 blocks without QK-norm on the small fp32 attention)
-    DPTHead                  vggt/heads/dpt_head.py:21-484    (channels-last; every convolution is the fp32-MFMA implicit GEMM, the full-resolution
-                                                                end of the head is one fused launch)
+    DPTHead                  vggt/heads/dpt_head.py:21-484    (the head shared with Depth Anything 3, videogpa_amd/dpt.py: channels-last, every
+                                                                convolution the fp32-MFMA implicit GEMM, the full-resolution end one fused launch;
+                                                                this file adds the constructor's refusals and the chunking along S)
     VGGT                     vggt/models/vggt.py:17-96        (aggregator + camera / depth / point heads; no track head)"""
 import math
-import os
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import ops
+from ._nn import _PackedCache, _forward_only, read_checkpoint
+from .dpt import DPTBase
 from .transformer import _f32
 
 
@@ -180,27 +182,6 @@ def slice_expand_and_flatten(token_tensor, B, S):
 
 
 # ---------------------------------------------------------------------------------------------------------------- DINOv2 patch embedding
-def _forward_only(module, *tensors):
-    if torch.is_grad_enabled() and (any(p.requires_grad for p in module.parameters()) or any(t.requires_grad for t in tensors)):
-        raise RuntimeError(f"{type(module).__name__} is forward only (no backward kernels): call it under torch.no_grad()")
-
-
-class _PackedCache:
-    """fp32 kernel-layout copies of parameters, rebuilt when a parameter's `_version`, storage or device changes"""
-
-    def __init__(self):
-        self._c = {}
-
-    def get(self, key, params, make):
-        tag = tuple((p._version, p.data_ptr(), str(p.device), p.dtype) for p in params)
-        hit = self._c.get(key)
-        if hit is None or hit[0] != tag:
-            with torch.no_grad():
-                hit = (tag, make())
-            self._c[key] = hit
-        return hit[1]
-
-
 class DinoAttention(nn.Module):
     """vggt/layers/attention.py:21-93 as DINOv2 builds it (MemEffAttention without xFormers = Attention): no QK-norm, no RoPE, head_dim 64.  The
     parameters only live here; DinoBlock runs them."""
@@ -615,90 +596,18 @@ class CameraHead(nn.Module):
         return out
 
 
-class _ResidualConvUnit(nn.Module):
-    def __init__(self, features):
-        super().__init__()
-        self.conv1 = nn.Conv2d(features, features, kernel_size=3, stride=1, padding=1, bias=True)
-        self.conv2 = nn.Conv2d(features, features, kernel_size=3, stride=1, padding=1, bias=True)
-
-
-class _FeatureFusionBlock(nn.Module):
-    def __init__(self, features, has_residual=True):
-        super().__init__()
-        self.out_conv = nn.Conv2d(features, features, kernel_size=1, stride=1, padding=0, bias=True)
-        if has_residual:
-            self.resConfUnit1 = _ResidualConvUnit(features)
-        self.has_residual = has_residual
-        self.resConfUnit2 = _ResidualConvUnit(features)
-
-
-class DPTHead(nn.Module):
-    """vggt/heads/dpt_head.py:21-484 on the HIP kernels, channels-last from the tokens to the predictions: `forward(aggregated_tokens_list,
-    images [B,S,3,H,W], patch_start_idx, frames_chunk_size=8) -> (preds [B,S,H,W,output_dim-1], conf [B,S,H,W])`.  The modules below only
-    hold the parameters under the reference's names and shapes (a reference state dict loads by name); the arithmetic is
-
-        LayerNorm (torch) -> projects.N, resize_layers.{0,1} as 1x1 convolutions (+ pixel shuffle) -> resize_layers.3 / layerN_rn /
-        ResidualConvUnits / output_conv1 as ops.conv3x3_f32 with ReLU, bias and residual adds fused -> out_conv BEFORE the bilinear
-        upsample (both linear, the interpolation weights sum to 1: a quarter of the pixels) -> ops.dpt_tail_f32.
-
-    A ResidualConvUnit's ReLU is in-place upstream, so the tensor it adds back is relu(x), not x (dpt_head.py:366-386): relu_res.
-    fp32 whatever autocast says; forward only."""
+class DPTHead(DPTBase):
+    """vggt/heads/dpt_head.py:21-484 on the shared head of videogpa_amd/dpt.py (RELU_RESIDUAL and F32_ANGLES as defined there: VGGT's in-place
+    ReLU, float64 embedding angles): `forward(aggregated_tokens_list, images [B,S,3,H,W], patch_start_idx, frames_chunk_size=8) ->
+    (preds [B,S,H,W,output_dim-1], conf [B,S,H,W])`, per batch row in chunks of frames_chunk_size frames along S."""
 
     def __init__(self, dim_in, patch_size=14, output_dim=4, activation="inv_log", conf_activation="expp1", features=256,
                  out_channels=(256, 512, 1024, 1024), intermediate_layer_idx=(4, 11, 17, 23), pos_embed=True, feature_only=False, down_ratio=1):
-        super().__init__()
         if feature_only or down_ratio != 1 or conf_activation != "expp1" or activation not in ("exp", "inv_log"):
             raise NotImplementedError("DPTHead on the HIP path: feature_only=False, down_ratio=1, conf_activation='expp1', activation 'exp' | 'inv_log'")
-        if dim_in % 16 or features % 32 or any(c % 16 for c in out_channels) or len(out_channels) != 4:
-            raise NotImplementedError("DPTHead on the HIP path: four stages, channel counts in multiples of 16")
-        out_channels = list(out_channels)
-        self.patch_size, self.activation, self.conf_activation, self.pos_embed = patch_size, activation, conf_activation, pos_embed
-        self.feature_only, self.down_ratio, self.intermediate_layer_idx = feature_only, down_ratio, list(intermediate_layer_idx)
-        self.norm = nn.LayerNorm(dim_in)
-        self.projects = nn.ModuleList([nn.Conv2d(dim_in, oc, kernel_size=1, stride=1, padding=0) for oc in out_channels])
-        self.resize_layers = nn.ModuleList([
-            nn.ConvTranspose2d(out_channels[0], out_channels[0], kernel_size=4, stride=4, padding=0),
-            nn.ConvTranspose2d(out_channels[1], out_channels[1], kernel_size=2, stride=2, padding=0),
-            nn.Identity(),
-            nn.Conv2d(out_channels[3], out_channels[3], kernel_size=3, stride=2, padding=1)])
-        self.scratch = nn.Module()
-        for i, c in enumerate(out_channels):
-            setattr(self.scratch, f"layer{i + 1}_rn", nn.Conv2d(c, features, kernel_size=3, stride=1, padding=1, bias=False))
-        self.scratch.refinenet1 = _FeatureFusionBlock(features)
-        self.scratch.refinenet2 = _FeatureFusionBlock(features)
-        self.scratch.refinenet3 = _FeatureFusionBlock(features)
-        self.scratch.refinenet4 = _FeatureFusionBlock(features, has_residual=False)
-        self.scratch.output_conv1 = nn.Conv2d(features, features // 2, kernel_size=3, stride=1, padding=1)
-        self.scratch.output_conv2 = nn.Sequential(nn.Conv2d(features // 2, 32, kernel_size=3, stride=1, padding=1), nn.ReLU(inplace=True),
-                                                  nn.Conv2d(32, output_dim, kernel_size=1, stride=1, padding=0))
-        self._packed = _PackedCache()
-        self._tabs = {}
+        super().__init__(dim_in, patch_size, output_dim, activation, conf_activation, features, out_channels, pos_embed, down_ratio)
+        self.feature_only, self.intermediate_layer_idx = feature_only, list(intermediate_layer_idx)
 
-    # ---- kernel-layout parameters
-    def _conv(self, name, conv):
-        """-> (weight [kh][kw][Cin][Cout] (a 1x1 as [Cin][Cout]), bias fp32 | None)"""
-        def make():
-            w = ops.pack_conv_weight(conv.weight)
-            return (w[0, 0].contiguous() if w.shape[0] == 1 else w), (None if conv.bias is None else conv.bias.detach().float().contiguous())
-        return self._packed.get(name, [conv.weight] + ([] if conv.bias is None else [conv.bias]), make)
-
-    def _deconv(self, name, conv):
-        """ConvTranspose2d with kernel = stride k: weight [Cin, Cout, k, k] -> [Cin][(a, b, Cout)], the bias repeated per (a, b)"""
-        def make():
-            k = conv.kernel_size[0]
-            w = conv.weight.detach().float().permute(0, 2, 3, 1).reshape(conv.in_channels, k * k * conv.out_channels).contiguous()
-            return w, conv.bias.detach().float().repeat(k * k).contiguous()
-        return self._packed.get(name, [conv.weight, conv.bias], make)
-
-    def _embed(self, width, height, channels, aspect, device):
-        key = (width, height, channels, aspect, str(device))
-        if key not in self._tabs:
-            if len(self._tabs) > 64:
-                self._tabs.clear()
-            self._tabs[key] = ops.uv_embed_tables(width, height, channels, aspect, device)
-        return self._tabs[key]
-
-    # ---- forward
     def forward(self, aggregated_tokens_list, images, patch_start_idx, frames_chunk_size=8):
         _forward_only(self, images, *[aggregated_tokens_list[i] for i in self.intermediate_layer_idx])
         B, S, _, H, W = images.shape
@@ -710,56 +619,11 @@ class DPTHead(nn.Module):
                      for s0 in range(0, S, frames_chunk_size)]
             return torch.cat([p[0] for p in parts], dim=1), torch.cat([p[1] for p in parts], dim=1)
 
-    def _rcu(self, name, unit, x, extra=None):
-        """conv2(relu(conv1(relu(x)))) + relu(x) (+ extra): two launches"""
-        w1, b1 = self._conv(name + ".conv1", unit.conv1)
-        w2, b2 = self._conv(name + ".conv2", unit.conv2)
-        t = ops.conv3x3_f32(x, w1, b1, relu_in=True)
-        return ops.conv3x3_f32(t, w2, b2, res=x, res2=extra, relu_in=True, relu_res=True)
-
-    def _fuse(self, name, block, x0, x1, size):
-        out = self._rcu(name + ".resConfUnit1", block.resConfUnit1, x1, extra=x0) if block.has_residual else x0
-        out = self._rcu(name + ".resConfUnit2", block.resConfUnit2, out)
-        out = ops.conv1x1_f32(out, *self._conv(name + ".out_conv", block.out_conv))
-        return ops.upsample_bilinear_ac_f32(out, size[0], size[1])
-
     def _forward_impl(self, aggregated_tokens_list, hw, patch_start_idx, s0, s1):
-        H, W = hw
-        ph, pw = H // self.patch_size, W // self.patch_size
-        feats = []
-        for i, layer_idx in enumerate(self.intermediate_layer_idx):
-            x = aggregated_tokens_list[layer_idx][:, s0:s1, patch_start_idx:].float()
-            B, S = x.shape[:2]
-            x = F.layer_norm(x.reshape(B * S, ph * pw, x.shape[-1]), self.norm.normalized_shape, self.norm.weight.float(), self.norm.bias.float(),
-                             self.norm.eps).contiguous()
-            x = ops.conv1x1_f32(x, *self._conv(f"projects.{i}", self.projects[i])).reshape(B * S, ph, pw, -1)
-            if self.pos_embed:
-                x = ops.upsample_bilinear_ac_f32(x, ph, pw, self._embed(pw, ph, x.shape[-1], W / H, x.device))
-            layer = self.resize_layers[i]
-            if isinstance(layer, nn.ConvTranspose2d):
-                k, oc = layer.kernel_size[0], layer.out_channels
-                x = ops.conv1x1_f32(x, *self._deconv(f"resize_layers.{i}", layer)).reshape(B * S, ph, pw, k, k, oc)
-                x = x.permute(0, 1, 3, 2, 4, 5).reshape(B * S, ph * k, pw * k, oc).contiguous()
-            elif isinstance(layer, nn.Conv2d):
-                x = ops.conv3x3_f32(x, *self._conv(f"resize_layers.{i}", layer), stride=2)
-            feats.append(x)
-        sc = self.scratch
-        rn = [ops.conv3x3_f32(f, self._conv(f"layer{i + 1}_rn", getattr(sc, f"layer{i + 1}_rn"))[0]) for i, f in enumerate(feats)]
-        del feats
-        out = self._fuse("refinenet4", sc.refinenet4, rn[3], None, rn[2].shape[1:3])
-        out = self._fuse("refinenet3", sc.refinenet3, out, rn[2], rn[1].shape[1:3])
-        out = self._fuse("refinenet2", sc.refinenet2, out, rn[1], rn[0].shape[1:3])
-        out = self._fuse("refinenet1", sc.refinenet1, out, rn[0], (2 * rn[0].shape[1], 2 * rn[0].shape[2]))
-        del rn
-        out = ops.conv3x3_f32(out, *self._conv("output_conv1", sc.output_conv1))
-        Ho, Wo = ph * self.patch_size, pw * self.patch_size
-        w1, b1 = self._conv("output_conv2.0", sc.output_conv2[0])
-        w2, b2 = self._packed.get("output_conv2.2", [sc.output_conv2[2].weight, sc.output_conv2[2].bias],
-                                  lambda: (sc.output_conv2[2].weight.detach().float().reshape(-1, 32).contiguous(),
-                                           sc.output_conv2[2].bias.detach().float().contiguous()))
-        tabs = self._embed(Wo, Ho, out.shape[-1], W / H, out.device) if self.pos_embed else None
-        preds, conf = ops.dpt_tail_f32(out, Ho, Wo, w1, b1, w2, b2, activation=self.activation, tabs=tabs)
-        return preds.view(B, S, Ho, Wo, -1), conf.view(B, S, Ho, Wo)
+        tokens = [aggregated_tokens_list[i][:, s0:s1, patch_start_idx:].float() for i in self.intermediate_layer_idx]
+        B, S = tokens[0].shape[:2]
+        preds, conf = self._main_tail(*self._pyramid([t.reshape(B * S, -1, t.shape[-1]) for t in tokens], *hw))
+        return preds.view(B, S, *preds.shape[1:]), conf.view(B, S, *conf.shape[1:])
 
 
 class VGGT(nn.Module):
@@ -790,19 +654,7 @@ class VGGT(nn.Module):
     def from_pretrained(cls, path, **kwargs):
         """A VGGT checkpoint from the LOCAL file system (never the network): `path` is a directory holding model.safetensors or model.pt, or such a
         file; **kwargs reach the constructor (none for VGGT-1B).  `track_head.*` keys are dropped; everything else must match by name."""
-        path = os.fspath(path)
-        if os.path.isdir(path):
-            found = [f for f in ("model.safetensors", "model.pt") if os.path.isfile(os.path.join(path, f))]
-            if not found:
-                raise FileNotFoundError(f"{path}: neither model.safetensors nor model.pt (from_pretrained reads local checkpoints only)")
-            path = os.path.join(path, found[0])
-        elif not os.path.isfile(path):
-            raise FileNotFoundError(f"{path}: no such checkpoint file or directory (from_pretrained reads local checkpoints only)")
-        if path.endswith(".safetensors"):
-            from safetensors.torch import load_file
-            state = load_file(path)
-        else:
-            state = torch.load(path, map_location="cpu", weights_only=True)
+        state = read_checkpoint(path)
         model = cls(**kwargs)
         model.load_state_dict(state, strict=True)
         return model.eval()

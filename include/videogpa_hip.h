@@ -82,6 +82,19 @@ int32_t vgpa_residual_ln_bwd(const void* dn, const void* x_new, const float* mea
                              const float* gate_t, int64_t gate_stride, const void* dres, int64_t B, int64_t S, int64_t D,
                              int64_t text_len, void* dx, void* dy, int64_t dy_stride /* row stride of dy, >= D */,
                              vgpa_stream_t stream);
+/* the same two passes with the result that feeds a frozen fp8 GEMM written ONLY as its e4m3 operand (no bf16 copy reaches memory):
+ *   fwd_q8: n  -> q8 [B*S, D] bytes + q8_scale [B*S] fp32;   bwd_q8: dy = bf16(gate*dx) -> dy_q8 [B*S, D] bytes + dy_scale [B*S] fp32 (both required)
+ * scale = rowmax / 448 (1 for an all-zero row), q = e4m3(bf16 value / scale), RNE, saturating: the bits of the bf16 entry followed by
+ * vgpa_quant_fp8_rows.  x_new / mean / rstd / dx exactly as the bf16 entries write them; D % 8 == 0, D <= 4096. */
+int32_t vgpa_residual_ln_fwd_q8(const void* x, const void* y, const float* gate_v, const float* gate_t, int64_t gate_stride,
+                                const float* ln_w, const float* ln_b, const float* shift_v, const float* scale1p_v,
+                                const float* shift_t, const float* scale1p_t, int64_t mod_stride, int64_t B, int64_t S, int64_t D,
+                                int64_t text_len, float eps, void* x_new, void* q8, float* q8_scale, float* mean, float* rstd,
+                                vgpa_stream_t stream);
+int32_t vgpa_residual_ln_bwd_q8(const void* dn, const void* x_new, const float* mean, const float* rstd, const float* ln_w,
+                                const float* scale1p_v, const float* scale1p_t, int64_t mod_stride, const float* gate_v,
+                                const float* gate_t, int64_t gate_stride, const void* dres, int64_t B, int64_t S, int64_t D,
+                                int64_t text_len, void* dx, void* dy_q8, float* dy_scale, vgpa_stream_t stream);
 /* out = x + gate[range] * y (x NULL: out = gate * y, the backward of the y branch) */
 int32_t vgpa_gate_residual(const void* x, const void* y, const float* gate_v, const float* gate_t, int64_t mod_stride,
                            int64_t B, int64_t S, int64_t D, int64_t text_len, void* out, vgpa_stream_t stream);

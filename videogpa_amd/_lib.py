@@ -28,6 +28,8 @@ SIGNATURES = {
     "vgpa_ln_modulate_bwd": (I32, [P, P, P, P, P, P, P, I64, I64, I64, I64, I64, P, P, P]),
     "vgpa_residual_ln_fwd": (I32, [P, P, P, P, I64, P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, P, P, I64, P, P, P]),
     "vgpa_residual_ln_bwd": (I32, [P, P, P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, I64, P]),
+    "vgpa_residual_ln_fwd_q8": (I32, [P, P, P, P, I64, P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, P, P, P, P, P, P]),
+    "vgpa_residual_ln_bwd_q8": (I32, [P, P, P, P, P, P, P, I64, P, P, I64, P, I64, I64, I64, I64, P, P, P, P]),
     "vgpa_gate_residual": (I32, [P, P, P, P, I64, I64, I64, I64, I64, P, P]),
     "vgpa_gelu_tanh_fwd": (I32, [P, I64, P, P]),
     "vgpa_gelu_tanh_bwd": (I32, [P, P, I64, P, P]),

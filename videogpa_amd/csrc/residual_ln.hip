@@ -48,11 +48,15 @@ __device__ __forceinline__ void params_global(const RLParams& P, int b, bool is_
 // All global loads of a row are issued back to back into packed registers BEFORE anything depends on them (branches
 // inside the chunk loop would otherwise serialise them behind s_waitcnt vmcnt(0)); HAS_Y / HAS_DRES are compile-time and
 // the home / slow-path choice is hoisted to one wave-uniform branch per row.
-template <int NV, bool HAS_Y>
+// Q8: n leaves as the e4m3 operand of the fp8 feed-forward GEMM (q8 [rows, D] bytes + one fp32 scale per row, common.h) and as nothing else: the wave
+// holds the whole row, so the row maximum is a wave_max and the bf16-rounded n replaces v in its registers -- bit-identical to n_out followed by
+// vgpa_quant_fp8_rows.  n_out / n_stride are unused then; q8 / q8_scale are unused (NULL) otherwise.
+template <int NV, bool HAS_Y, bool Q8 = false>
 __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_fwd_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ y, RLParams P,
                                                                          int text_len, int S, int D, int64_t rows, float eps,
                                                                          bf16_t* __restrict__ x_new, bf16_t* __restrict__ n_out, int64_t n_stride,
-                                                                         float* __restrict__ mean_out, float* __restrict__ rstd_out) {
+                                                                         float* __restrict__ mean_out, float* __restrict__ rstd_out,
+                                                                         uint8_t* __restrict__ q8, float* __restrict__ q8_scale) {
     extern __shared__ __attribute__((aligned(16))) float sp[];   // [3][D]: alpha, beta, gate of the home range
     float* s_alpha = sp; float* s_beta = sp + D; float* s_gate = sp + 2 * D;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -110,6 +114,7 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_fwd_kernel(const bf
         }
         const float rstd = rsqrtf(wave_sum(sq) / (float)D + eps);
         if (lane == 0 && mean_out) { mean_out[row] = mean; rstd_out[row] = rstd; }
+        float amax = 0.f;
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             const int i0 = (c * 64 + lane) * 8;
@@ -119,18 +124,36 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_fwd_kernel(const bf
                 load8<VGPA_DTYPE_F32>(s_beta + i0, 0, be);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) o[j] = (v[c][j] - mean) * rstd * a[j] + be[j];
-                *reinterpret_cast<u32x4_t*>(n_out + (size_t)row * n_stride + i0) = pack8(o);
+                if (Q8) {
+                    unpack8(pack8(o), v[c]);   // the bf16 n this row would have had in HBM
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(v[c][j]));
+                } else {
+                    *reinterpret_cast<u32x4_t*>(n_out + (size_t)row * n_stride + i0) = pack8(o);
+                }
+            }
+        }
+        if (Q8) {
+            const float sc = e4m3_row_scale(wave_max(amax));
+            if (lane == 0) q8_scale[row] = sc;
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+                const int i0 = (c * 64 + lane) * 8;
+                if (i0 < D) store8_e4m3(q8 + (size_t)row * D, i0, v[c], sc);
             }
         }
     }
 }
 
-template <int NV, bool HAS_DRES, bool HAS_DY>
+// Q8 (with HAS_DY): dy = bf16(gate * dx) leaves as e4m3 bytes + one fp32 scale per row only (the operand of the fp8 dX GEMM behind it); the chunks wait
+// packed (one u32x4_t each) until the row maximum is known.  dy / dy_stride are unused then; q8 / q8_scale are unused (NULL) otherwise.
+template <int NV, bool HAS_DRES, bool HAS_DY, bool Q8 = false>
 __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_bwd_kernel(const bf16_t* __restrict__ dn, const bf16_t* __restrict__ xn,
                                                                          const float* __restrict__ mean_in, const float* __restrict__ rstd_in,
                                                                          RLParams P, int text_len, int S, int D, int64_t rows,
                                                                          const bf16_t* __restrict__ dres, bf16_t* __restrict__ dx,
-                                                                         bf16_t* __restrict__ dy, int64_t dy_stride) {
+                                                                         bf16_t* __restrict__ dy, int64_t dy_stride,
+                                                                         uint8_t* __restrict__ q8, float* __restrict__ q8_scale) {
     extern __shared__ __attribute__((aligned(16))) float sp[];   // [2][D]: alpha, gate
     float* s_alpha = sp; float* s_gate = sp + D;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -177,6 +200,14 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_bwd_kernel(const bf
             }
         }
         const float c1 = wave_sum(s1) / (float)D, c2 = wave_sum(s2) / (float)D;
+        u32x4_t dyp[Q8 ? NV : 1];
+        float amax = 0.f;
+        if (Q8) {
+            // hipcc otherwise keeps the first loop's unpacked fp32 g / xhat alive for this one (the unpack is common to both): with dyp on top the row
+            // no longer fits two waves' registers.  Opaque to the optimiser, no instruction: the second loop unpacks again.
+#pragma unroll
+            for (int c = 0; c < NV; ++c) asm volatile("" : "+v"(dnp[c]), "+v"(xp[c]));
+        }
 #pragma unroll
         for (int c = 0; c < NV; ++c) {
             const int i0 = (c * 64 + lane) * 8;
@@ -198,7 +229,27 @@ __global__ __launch_bounds__(64 * RL_WAVES) void residual_ln_bwd_kernel(const bf
                 if (HAS_DY) {
 #pragma unroll
                     for (int j = 0; j < 8; ++j) o[j] = gt[j] * o[j];
-                    *reinterpret_cast<u32x4_t*>(dy + (size_t)row * dy_stride + i0) = pack8(o);
+                    if (Q8) {
+                        dyp[c] = pack8(o);
+                        unpack8(dyp[c], o);
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) amax = fmaxf(amax, fabsf(o[j]));
+                    } else {
+                        *reinterpret_cast<u32x4_t*>(dy + (size_t)row * dy_stride + i0) = pack8(o);
+                    }
+                }
+            }
+        }
+        if (Q8) {
+            const float sc = e4m3_row_scale(wave_max(amax));
+            if (lane == 0) q8_scale[row] = sc;
+#pragma unroll
+            for (int c = 0; c < NV; ++c) {
+                const int i0 = (c * 64 + lane) * 8;
+                if (i0 < D) {
+                    float o[8];
+                    unpack8(dyp[c], o);
+                    store8_e4m3(q8 + (size_t)row * D, i0, o, sc);
                 }
             }
         }
@@ -225,9 +276,33 @@ int32_t vgpa_residual_ln_fwd(const void* x, const void* y, const float* gate_v, 
     const dim3 grid((unsigned)(B * ((text_len + RL_ROWS - 1) / RL_ROWS + (S - text_len + RL_ROWS - 1) / RL_ROWS)));   // range-aligned blocks
     const size_t shmem = (size_t)3 * D * sizeof(float);
 #define FWD_ARGS grid, dim3(64 * RL_WAVES), shmem, stream, (const bf16_t*)x, (const bf16_t*)y, P, (int)text_len, (int)S, (int)D, rows, eps, \
-                 (bf16_t*)x_new, (bf16_t*)n_out, n_stride, mean, rstd
+                 (bf16_t*)x_new, (bf16_t*)n_out, n_stride, mean, rstd, (uint8_t*)nullptr, (float*)nullptr
     if (y) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, true>), FWD_ARGS)); }
     else { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, false>), FWD_ARGS)); }
+#undef FWD_ARGS
+    VGPA_CHECK_LAUNCH();
+    return VGPA_OK;
+}
+
+// vgpa_residual_ln_fwd with n written ONLY as the e4m3 operand of the fp8 GEMM that consumes it: q8 [B*S, D] bytes, q8_scale [B*S] fp32
+// (scale = rowmax|n| / 448, 1 for an all-zero row; the same bits as n_out followed by vgpa_quant_fp8_rows).  x_new / mean / rstd as there.
+int32_t vgpa_residual_ln_fwd_q8(const void* x, const void* y, const float* gate_v, const float* gate_t, int64_t gate_stride, const float* ln_w,
+                                const float* ln_b, const float* shift_v, const float* scale1p_v, const float* shift_t, const float* scale1p_t,
+                                int64_t mod_stride, int64_t B, int64_t S, int64_t D, int64_t text_len, float eps, void* x_new, void* q8,
+                                float* q8_scale, float* mean, float* rstd, hipStream_t stream) {
+    if (!x || !ln_w || !ln_b || !q8 || !q8_scale) return VGPA_ERR_INVALID;
+    if (B <= 0 || S <= 0 || D <= 0 || D % 8 != 0 || D > 4096 || text_len < 0 || text_len > S) return VGPA_ERR_INVALID;
+    if (y && (!gate_v || !x_new || (text_len > 0 && !gate_t))) return VGPA_ERR_INVALID;
+    if (shift_v && (!scale1p_v || (text_len > 0 && (!shift_t || !scale1p_t)))) return VGPA_ERR_INVALID;
+    if ((mean == nullptr) != (rstd == nullptr)) return VGPA_ERR_INVALID;
+    RLParams P = {ln_w, ln_b, shift_v, scale1p_v, shift_t, scale1p_t, mod_stride, y ? gate_v : nullptr, y ? gate_t : nullptr, gate_stride};
+    const int64_t rows = B * S;
+    const dim3 grid((unsigned)(B * ((text_len + RL_ROWS - 1) / RL_ROWS + (S - text_len + RL_ROWS - 1) / RL_ROWS)));   // range-aligned blocks
+    const size_t shmem = (size_t)3 * D * sizeof(float);
+#define FWD_ARGS grid, dim3(64 * RL_WAVES), shmem, stream, (const bf16_t*)x, (const bf16_t*)y, P, (int)text_len, (int)S, (int)D, rows, eps, \
+                 (bf16_t*)x_new, (bf16_t*)nullptr, (int64_t)0, mean, rstd, (uint8_t*)q8, q8_scale
+    if (y) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, true, true>), FWD_ARGS)); }
+    else { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_fwd_kernel<NV, false, true>), FWD_ARGS)); }
 #undef FWD_ARGS
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
@@ -248,11 +323,33 @@ int32_t vgpa_residual_ln_bwd(const void* dn, const void* x_new, const float* mea
     const dim3 grid((unsigned)(B * ((text_len + RL_ROWS - 1) / RL_ROWS + (S - text_len + RL_ROWS - 1) / RL_ROWS)));   // range-aligned blocks
     const size_t shmem = (size_t)2 * D * sizeof(float);
 #define BWD_ARGS grid, dim3(64 * RL_WAVES), shmem, stream, (const bf16_t*)dn, (const bf16_t*)x_new, mean, rstd, P, (int)text_len, (int)S, (int)D, \
-                 rows, (const bf16_t*)dres, (bf16_t*)dx, (bf16_t*)dy, dy_stride
+                 rows, (const bf16_t*)dres, (bf16_t*)dx, (bf16_t*)dy, dy_stride, (uint8_t*)nullptr, (float*)nullptr
     if (dres && dy) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, true, true>), BWD_ARGS)); }
     else if (dres) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, true, false>), BWD_ARGS)); }
     else if (dy) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, false, true>), BWD_ARGS)); }
     else { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, false, false>), BWD_ARGS)); }
+#undef BWD_ARGS
+    VGPA_CHECK_LAUNCH();
+    return VGPA_OK;
+}
+
+// vgpa_residual_ln_bwd with dy = bf16(gate[range]*dx) written ONLY as e4m3: dy_q8 [B*S, D] bytes, dy_scale [B*S] fp32 (as vgpa_quant_fp8_rows of dy).
+int32_t vgpa_residual_ln_bwd_q8(const void* dn, const void* x_new, const float* mean, const float* rstd, const float* ln_w, const float* scale1p_v,
+                                const float* scale1p_t, int64_t mod_stride, const float* gate_v, const float* gate_t, int64_t gate_stride,
+                                const void* dres, int64_t B, int64_t S, int64_t D, int64_t text_len, void* dx, void* dy_q8, float* dy_scale,
+                                hipStream_t stream) {
+    if (!dn || !x_new || !mean || !rstd || !ln_w || !dx || !dy_q8 || !dy_scale) return VGPA_ERR_INVALID;
+    if (B <= 0 || S <= 0 || D <= 0 || D % 8 != 0 || D > 4096 || text_len < 0 || text_len > S) return VGPA_ERR_INVALID;
+    if (!gate_v || (text_len > 0 && !gate_t)) return VGPA_ERR_INVALID;
+    if (scale1p_v && text_len > 0 && !scale1p_t) return VGPA_ERR_INVALID;
+    RLParams P = {ln_w, nullptr, nullptr, scale1p_v, nullptr, scale1p_t, mod_stride, gate_v, gate_t, gate_stride};
+    const int64_t rows = B * S;
+    const dim3 grid((unsigned)(B * ((text_len + RL_ROWS - 1) / RL_ROWS + (S - text_len + RL_ROWS - 1) / RL_ROWS)));   // range-aligned blocks
+    const size_t shmem = (size_t)2 * D * sizeof(float);
+#define BWD_ARGS grid, dim3(64 * RL_WAVES), shmem, stream, (const bf16_t*)dn, (const bf16_t*)x_new, mean, rstd, P, (int)text_len, (int)S, (int)D, \
+                 rows, (const bf16_t*)dres, (bf16_t*)dx, (bf16_t*)nullptr, (int64_t)0, (uint8_t*)dy_q8, dy_scale
+    if (dres) { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, true, true, true>), BWD_ARGS)); }
+    else { ROW_DISPATCH_NV(D, VGPA_LAUNCH((residual_ln_bwd_kernel<NV, false, true, true>), BWD_ARGS)); }
 #undef BWD_ARGS
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;

@@ -824,6 +824,93 @@ def frozen_linear_fp8(x, W, bias):
     return _Fp8FrozenLinearFn.apply(x, W, bias)
 
 
+class _FfnTailFp8Fn(torch.autograd.Function):
+    """The tail of a CogVideoX block with e4m3 operands in its frozen feed-forward, as ONE autograd node (autograd cannot carry an e4m3 tensor between nodes):
+        x1 = x + gates1 * a ;  n2 = norm2(x1) modulated  -> e4m3 by the residual+LN kernel itself (vgpa_residual_ln_fwd_q8)
+        f  = W2 gelu_tanh(W1 n2 + b1) + b2                  -> both products on the vendor fp8 GEMM, the GELU writes its own e4m3 operand (csrc/fp8.hip)
+        x2 = x1 + gates2 * f ;  n_next = next norm of x2    -> the bf16 residual+LN pass as before: n_next feeds a LoRA-carrying projection (n_pad)
+    Backward: vgpa_residual_ln_bwd_q8 (dx1 in bf16, gates2 * dx1 as e4m3) -> fp8 GEMM with W2^T -> GELU backward -> fp8 GEMM with W1^T -> the bf16
+    residual+LN backward, which adds the residual path's gradient (dres) and writes the attention output's gradient with its LoRA tail (dy_pad).
+    Every e4m3 operand is bit-identical to its bf16 producer followed by quant_fp8_rows, so the node equals residual_ln -> frozen_linear_fp8 ->
+    gelu_tanh -> frozen_linear_fp8 -> residual_ln without the four bf16 round trips through HBM.  Saves what that chain saves."""
+
+    @staticmethod
+    def forward(ctx, x, a, gates1, ln_w, ln_b, mod2, W1, b1, W2, b2, gates2, nxt_w, nxt_b, nxt_mod, nxt_eps, text_len, eps, n_pad, dy_pad):
+        _req(x, torch.bfloat16), _req(a, torch.bfloat16), _req(gates1, torch.float32), _req(gates2, torch.float32)
+        _req(ln_w, torch.float32), _req(ln_b, torch.float32), _req(nxt_w, torch.float32), _req(nxt_b, torch.float32)
+        B, S, D = x.shape
+        rows, dev = B * S, x.device
+        keep = any(ctx.needs_input_grad)          # forward-only (no_grad): no LN statistics, nothing saved
+        w1, w2 = Fp8Weight.of(W1), Fp8Weight.of(W2)
+        x1 = torch.empty_like(x)
+        hq = torch.empty(rows, D, dtype=torch.float8_e4m3fn, device=dev)
+        hs = torch.empty(rows, 1, dtype=torch.float32, device=dev)
+        mean1 = torch.empty(B, S, dtype=torch.float32, device=dev) if keep else None
+        rstd1 = torch.empty_like(mean1) if keep else None
+        sv, s1v, st, s1t, mstride = _mod_ptrs(mod2)
+        _timed("residual_ln_fwd_fp8", 7.0 * rows * D,
+               lambda: _lib.call("vgpa_residual_ln_fwd_q8", x, a, gates1[:, 0], gates1[:, 1], gates1.stride(0), ln_w, ln_b, sv, s1v, st, s1t, mstride,
+                                 B, S, D, text_len, float(eps), x1, hq, hs, mean1, rstd1, _stream()), "byte")
+        u = _fp8_gemm(hq, hs, w1.q, w1.s, b1)
+        del hq, hs
+        gq, gs = gelu_tanh_fwd_q8(u)
+        f = _fp8_gemm(gq, gs, w2.q, w2.s, b2)
+        del gq, gs
+        x2 = torch.empty_like(x)
+        n = _padded_empty((B, S), D, n_pad, x.dtype, dev) if n_pad else _empty_rows(x.shape, x.dtype, dev)
+        mean2 = torch.empty(B, S, dtype=torch.float32, device=dev) if keep else None
+        rstd2 = torch.empty_like(mean2) if keep else None
+        nv, n1v, nt, n1t, nstride = _mod_ptrs(nxt_mod)
+        _timed("residual_ln_fwd", 8.0 * rows * D,
+               lambda: _lib.call("vgpa_residual_ln_fwd", x1, f, gates2[:, 0], gates2[:, 1], gates2.stride(0), nxt_w, nxt_b, nv, n1v, nt, n1t, nstride,
+                                 B, S, D, text_len, float(nxt_eps), x2, n, D + n_pad, mean2, rstd2, _stream()), "byte")
+        if keep:
+            ctx.save_for_backward(x1, mean1, rstd1, u, x2, mean2, rstd2, ln_w, mod2, gates1, nxt_w, nxt_mod, gates2)
+            ctx.w, ctx.text_len, ctx.dy_pad = (w1, w2), text_len, dy_pad
+        return x2, n
+
+    @staticmethod
+    def backward(ctx, dx2, dn):
+        x1, mean1, rstd1, u, x2, mean2, rstd2, ln_w, mod2, gates1, nxt_w, nxt_mod, gates2 = ctx.saved_tensors
+        w1, w2 = ctx.w
+        B, S, D = x1.shape
+        rows, dev = B * S, x1.device
+        dn = torch.zeros_like(x2) if dn is None else dn.contiguous()
+        dres = None if dx2 is None else dx2.contiguous()
+        dx1 = torch.empty_like(x1)
+        dfq = torch.empty(rows, D, dtype=torch.float8_e4m3fn, device=dev)
+        dfs = torch.empty(rows, 1, dtype=torch.float32, device=dev)
+        _, n1v, _, n1t, nstride = _mod_ptrs(nxt_mod)
+        _timed("residual_ln_bwd_fp8", (7.0 + (2.0 if dres is not None else 0.0)) * rows * D,
+               lambda: _lib.call("vgpa_residual_ln_bwd_q8", dn, x2, mean2, rstd2, nxt_w, n1v, n1t, nstride, gates2[:, 0], gates2[:, 1], gates2.stride(0),
+                                 dres, B, S, D, ctx.text_len, dx1, dfq, dfs, _stream()), "byte")
+        dg = _fp8_gemm(dfq, dfs, w2.qt, w2.st)
+        del dfq, dfs
+        duq, dus = gelu_tanh_bwd_q8(u, dg)
+        del dg
+        dh = _fp8_gemm(duq, dus, w1.qt, w1.st)
+        del duq, dus
+        dx = torch.empty_like(x1)
+        dyp = ctx.dy_pad
+        da = _padded_empty((B, S), D, dyp, x1.dtype, dev) if dyp else _empty_rows(x1.shape, x1.dtype, dev)
+        _, s1v, _, s1t, mstride = _mod_ptrs(mod2)
+        _timed("residual_ln_bwd", 10.0 * rows * D,
+               lambda: _lib.call("vgpa_residual_ln_bwd", dh, x1, mean1, rstd1, ln_w, s1v, s1t, mstride, gates1[:, 0], gates1[:, 1], gates1.stride(0),
+                                 dx1, B, S, D, ctx.text_len, dx, da, D + dyp, _stream()), "byte")
+        return (dx, da) + (None,) * 17
+
+
+def ffn_tail_fp8(x, a, gates1, ln_w, ln_b, mod2, W1, b1, W2, b2, gates2, nxt_w, nxt_b, nxt_mod=None, nxt_eps=1e-5, text_len=0, eps=1e-5, n_pad=0, dy_pad=0):
+    """-> (x_out, n_next) of a CogVideoX block given its attention output `a`: gated residual + norm2, the frozen feed-forward on e4m3 operands written by
+    their producers, gated residual + the next normalisation (see _FfnTailFp8Fn).  W1 [inner, D] / W2 [D, inner] and their biases are frozen."""
+    if W1.requires_grad or W2.requires_grad or (b1 is not None and b1.requires_grad) or (b2 is not None and b2.requires_grad):
+        raise RuntimeError("videogpa_amd: the fp8 path is for frozen projections only")
+    if W1.shape[0] > 16384:
+        raise RuntimeError(f"ffn_tail_fp8: the GELU -> e4m3 kernels hold one feed-forward row per workgroup, inner <= 16384; got {W1.shape[0]}")
+    return _FfnTailFp8Fn.apply(x, a, gates1, ln_w, ln_b, mod2, W1, b1, W2, b2, gates2, nxt_w, nxt_b, nxt_mod, nxt_eps, int(text_len), eps, int(n_pad),
+                               int(dy_pad))
+
+
 class _LinearLoraExtFn(torch.autograd.Function):
     """y = x W^T + b (+ LoRA when `enabled`), W / b frozen; see LoraExt.  x / dy are used in place when they are the heads of
     padded buffers (produced by ops.residual_ln / qknorm_attention with n_pad / o_pad / grad pads), copied into one otherwise.

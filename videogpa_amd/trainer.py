@@ -40,6 +40,7 @@ DEFAULT_CONFIG: Dict[str, Any] = {
     "lean_activations": "auto",
     "metric_name": "consistency_score", "min_gap": 0.05, "motion_threshold": 1e-3,
     "log_every_n_steps": 10,
+    "fp8_ffn": False,                         # opt-in: the frozen feed-forward on OCP-e4m3 operands (CogVideoXTransformer3DModel.enable_fp8); the reference runs it in bf16
     "tuned_gemms": True,                      # pick the hipBLASLt solutions of videogpa_amd/tuned/ (ops.use_tuned_gemms); False = the library's default heuristic
     "seed": 0,                                # (t, eps) stream = seed + rank: every rank draws its own
 }
@@ -100,6 +101,8 @@ class CogVideoXDPOTrainer(nn.Module):
         cfg["lean_activations"] = self._lean_setting(cfg.get("lean_activations", "auto"))
         if cfg["lean_activations"] is True:
             self.transformer.enable_lean_activations(True)       # this package's transformer only (AttributeError on anything else: say so loudly)
+        if cfg.get("fp8_ffn", False):
+            self.transformer.enable_fp8(True)                    # this package's transformer only, as above
         self.ref_transformer = None
         if separate_ref:  # the reference's layout: a second frozen copy (:110-111)
             import copy

@@ -278,6 +278,7 @@ class CogVideoXBlock(nn.Module):
         self.norm2 = CogVideoXLayerNormZero(time_embed_dim, dim, affine, eps)
         self.ff = FeedForward(dim, 4 * dim)
         self.eps = eps
+        self.fp8_ffn = False                  # CogVideoXTransformer3DModel.enable_fp8()
 
     def modulations(self, temb):
         """((mod1, gates1), (mod2, gates2)) of this block for one conditioning embedding."""
@@ -286,6 +287,14 @@ class CogVideoXBlock(nn.Module):
     def norm1_params(self):
         return _f32(self.norm1.norm.weight), _f32(self.norm1.norm.bias)
 
+    def _frozen_ff(self):
+        """the two feed-forward projections for the e4m3 path, which has no LoRA form: the reference's adapters sit on to_q / to_k / to_v / to_out.0 only"""
+        f0, f2 = self.ff.net[0].proj, self.ff.net[2]
+        for name, m in (("ff.net.0.proj", f0), ("ff.net.2", f2)):
+            if hasattr(m, "base_layer"):
+                raise RuntimeError(f"videogpa_amd: enable_fp8 runs the feed-forward on e4m3 operands, frozen projections only; {name} is LoRA-wrapped")
+        return f0, f2
+
     def forward(self, x, n, gates1, mod2, gates2, text_len, rope, nxt_w, nxt_b, nxt_mod, nxt_eps, nxt_pad=0, lean=None):
         """x: residual stream; n = norm1(x) already modulated (produced by the previous block's fused residual+LN pass).
         Returns (x_out, n_next) where n_next is the NEXT normalisation (next block's norm1, or the model's norm_final)
@@ -293,6 +302,10 @@ class CogVideoXBlock(nn.Module):
         next block's q/k/v projection wants behind n_next (Attention.pads).  lean = (ln_w, ln_b, mod) of THIS block's norm1: n is then not kept
         for the backward but made again from x (AttentionCore.forward)."""
         a = self.attn1(n, text_len, rope, None if lean is None else (x, lean[0], lean[1], lean[2], self.eps))
+        if self.fp8_ffn:
+            f0, f2 = self._frozen_ff()
+            return ops.ffn_tail_fp8(x, a, gates1, _f32(self.norm2.norm.weight), _f32(self.norm2.norm.bias), mod2, f0.weight, f0.bias, f2.weight, f2.bias,
+                                    gates2, nxt_w, nxt_b, nxt_mod, nxt_eps, text_len, self.eps, n_pad=nxt_pad, dy_pad=self.attn1.pads()[1])
         x, n2 = ops.residual_ln(x, a, gates1, _f32(self.norm2.norm.weight), _f32(self.norm2.norm.bias), mod2, text_len, self.eps,
                                 dy_pad=self.attn1.pads()[1])
         u = ops.frozen_linear(n2, self.ff.net[0].proj.weight, self.ff.net[0].proj.bias)
@@ -345,6 +358,17 @@ class CogVideoXTransformer3DModel(nn.Module):
         fourth block (bench.py --config cfg4).  Results are bit-identical either way (the output's res8 bytes for the backward's delta are kept in
         both modes)."""
         self.lean_activations = bool(enabled)
+
+    def enable_fp8(self, enabled=True):
+        """Opt-in, off by default: the frozen feed-forward of every block (8 D^2 of a block's 12 D^2 linear FLOPs per token) takes OCP-e4m3 operands --
+        per-row dynamic activation scales written by the producing row kernels (csrc/residual_ln.hip, csrc/fp8.hip), per-output-row weight scales,
+        fp32 accumulation, bf16 out, forward and dX on the vendor's fp8 GEMM (ops.ffn_tail_fp8).  The reference computes these products in bf16: this
+        is a deliberate deviation (DESIGN section 5 has the measured distance).  The attention and the LoRA-carrying projections stay bf16.  Costs one
+        byte per element for W and W^T of both projections (151 MB per block at D = 3072), made at the first call.  enable_fp8(False) restores the
+        bf16 path bit for bit."""
+        for blk in self.transformer_blocks:
+            blk.fp8_ffn = bool(enabled)
+        return self
 
     def set_precise_delta(self, mode="int8"):
         """what every attention of THIS model keeps of its output beyond the bf16 rounding for the backward's delta: "int8" (default: one byte per

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import attn_tol
+import row_tol
 from attn_ref64 import attn_ref64
 from attn_tol import lse2_tol
 from oracle import cogvideox as ocv
@@ -156,6 +157,10 @@ def test_gate_residual_and_gelu(ops):
     o.backward(dev(do))
     orf.backward(do.double())
     assert (ud.grad.double().cpu() - ur.grad).abs().max().item() < 0.03
+    # per element: the bf16 half ulp of each result plus the counted fp32 error (tests/row_tol.py), where 0.04 absolute said nothing about the small outputs
+    val, der = row_tol.gelu_ref64(u, do)
+    assert not row_tol.judge("gelu", o.detach().cpu(), val, row_tol.gelu_fwd_tol(u, val))
+    assert not row_tol.judge("dgelu", ud.grad.cpu(), der, row_tol.gelu_bwd_tol(u, do, der))
 
 
 # ------------------------------------------------------------------------------------------ attention

@@ -1,7 +1,9 @@
-"""fp64 references, per-element bounds and float32 restatements of the small kernels of the CogVideoX training step: QK-norm + RoPE
-(csrc/qknorm.hip), gelu_tanh (csrc/norm.hip), the DPO error reduction (csrc/dpo_loss.hip), AdamW and the gradient norm (csrc/adamw.hip).
+"""fp64 references, per-element bounds and float32 restatements of the small kernels of the training steps: QK-norm + RoPE
+(csrc/qknorm.hip), gelu_tanh (csrc/norm.hip), the DPO error reduction (csrc/dpo_loss.hip), AdamW and the gradient norm (csrc/adamw.hip), and the
+one-wave-per-row norm kernels over csrc/row_ln.h: CogVideoX LayerNorm + modulation with and without the residual add (csrc/norm.hip, csrc/residual_ln.hip),
+Wan LayerNorm + per-token modulation, RMS-norm + RoPE and the gated residual add (csrc/wan.hip).
 tests/test_row_tol_host.py shows on the CPU that the restatements stay inside the bounds and that wrong variants do not;
-tests/test_gpu_step_kernels.py holds the device to the same bounds.  No number below was fitted to a device result.
+tests/test_gpu_step_kernels.py and tests/test_gpu_row_kernels.py hold the device to the same bounds.  No number below was fitted to a device result.
 
 Units.  u = 2^-24 is the unit roundoff of fp32 (half an ulp, relative): one correctly rounded fp32 operation is off by at most u |result|.  The hardware
 exp2 / rcp / rsq are 1 ulp = 2u (CDNA ISA: V_EXP_F32, V_RCP_F32, V_RSQ_F32).  hipcc contracts a*b+c into one FMA where it likes: that only removes
@@ -67,7 +69,42 @@ AdamW (adamw_kernel; header comment of csrc/adamw.hip: clip_grad_norm_ then torc
 grad_norm (sumsq_partial_kernel): per iteration four squares and three adds (4u), one add into the accumulator per iteration (k u, k = iterations per thread incl.
     the scalar tail), fp64 from there; the square root halves it, the (float) cast adds 1u:   |norm - ref| <= ((4 + k) / 2 + 1) u ref
 
-gate_residual and the noise kernels are bit-exact with a torch expression; they need no bound."""
+Row kernels (one wave per row of D <= 4096 columns, NV = ceil(D / 512) chunks of 64 lanes x 8).  The summation constants of the 64-wide vector become functions of D:
+    sum     a lane adds its 8 NV values serially (8 NV - 1 additions, fewer in a partly filled last chunk), wave_sum adds six times (offsets 32..1):
+            C_SUM(D) = 8 NV + 5 additions behind every element
+    mean    the division by (float)D 1u:  |d mean| <= C_MEAN(D) u mean|x|,   C_MEAN(D) = 8 NV + 6                      (14 at NV 1, 70 at NV 8)
+    rstd    x - mean 1u, the squares 2u + 1u, their sum C_SUM u, / D 1u: (C_MEAN + 3) u relative on the variance; + eps 1u; rsq 2u:
+            C_RSTD(D) = (C_MEAN + 3) / 2 + 1/2 + 2 = C_MEAN(D) / 2 + 4.   The mean's own error d enters the variance as d^2 (sum of deviations = 0): relative to
+            var + eps that is (C_MEAN u K)^2, K = mean|x| rstd as above -- nothing on ordinary rows, kept because a constant row has K = |c| eps^-1/2
+    xhat    (x - mean) [1u] rstd [C_RSTD u + 1u]:  e_xhat = u ((C_RSTD + 2) |xhat_d| + C_MEAN K) + (C_MEAN u K)^2 / 2 |xhat_d|.  On a constant row xhat = 0
+            and the K term is the whole bound: the device's xhat there is (c - mean') rstd, the mean's rounding times eps^-1/2
+  CogVideoX forward (ln_modulate_fwd_kernel, residual_ln_fwd_kernel):  alpha = w s1p [1u], beta = b s1p [1u] + shift [1u of the sum], n = xhat alpha + beta
+            rest_d = e_xhat |alpha_d| + u (|xhat_d alpha_d| [alpha] + |xhat_d alpha_d| [product] + |b_d s1p_d| + |beta_d| + |n_d| [sum]);   tol = bf16_tol(n, rest)
+            mean and rstd are outputs and are judged with the two bounds above.  x' = bf16(x + bf16(gate y)) is a torch expression, bit for bit
+  LayerNorm backward (ln_modulate_bwd_kernel, residual_ln_bwd_kernel, wan_ln_mod_bwd_kernel):  dx = [dres +] rstd (g - c1 - xhat c2) FROM THE fp32 mean / rstd THE FORWARD
+            WROTE: they are the kernel's inputs, so the reference takes them as given and no K term appears.  g arrives with cg u |g| (CogVideoX: alpha 1u, dy alpha 1u:
+            cg = 2, 0 without modulation; Wan: 1 + scale 1u, the product 1u, the product with w 1u)
+    xhat    (x - mean) [1u] rstd [1u]: 2u |xhat|
+    c1      (cg + C_MEAN) u mean|g|.      c2: terms (cg + 2 + 1) u, sum and division C_MEAN u:  (cg + 3 + C_MEAN) u mean|g xhat|
+    dx      rstd [cg u |g| + d c1 + u |g - c1| + |xhat| d c2 + 3u |xhat c2| + u |g - c1 - xhat c2|] + u |d| (the product with rstd) [+ u |dres + d|]
+            stored as bf16 (CogVideoX: bf16_tol) or as fp32 (Wan: the rest itself).  dy = bf16(gate dx) resp. dy_prev = bf16(dx gate_prev[g]) is one fp32 product of the
+            STORED dx and one rounding: bit for bit with torch given the device's dx
+  Wan forward (wan_ln_mod_fwd_kernel):  o = xhat, [round_bf16], o w + b, o (1 + scale[g]) + shift[g].  The reference is the unrounded expression; every step maps (v, e) to
+            round_xhat   e + half_ulp_bf16(|v| + e)
+            affine       e |w| + u |v w| + u |v w + b|
+            modulation   e |1 + s| + 2u |v (1 + s)| (1 + s and the product) + u |v (1 + s) + shift|
+            and the store is bf16_tol(ref, e), or e + u |ref| for the fp32 result.  A missing round_xhat stays inside that bound (its half ulp is part of it), so the
+            device test also holds bf16((x - mean') rstd'), two exactly rounded fp32 operations from the device's own mean' and rstd', bit for bit
+  RMS-norm + RoPE (wan_rms_rope_*_kernel):  the squares 1u, sum and division C_MEAN u, + eps 1u, rsq 2u:  rs is off by C_RMS(D) = C_MEAN(D) / 2 + 3 (judged as rstd_out)
+    forward n = bf16(u rs): e = (C_RMS + 1) u |n| + its half ulp;  y = bf16(n w): e |w| + u |n w| + its half ulp;  rotation (a, b) -> (a cos - b sin, a sin + b cos):
+            e_a |cos| + e_b |sin| + 2u (|a cos| + |b sin|);  store.  Without tables y is the output (its half ulp is the store's) and must also equal
+            bf16(bf16(u rs') w) formed in torch fp32 from the device's rs', bit for bit
+    backward du = bf16(rs (dn - n m)), dn = w R^T dout [cg = 3: rotation 2u, w 1u, of G = (|a cos| + |b sin|) |w|; 1 without tables], n = u rs [1u], m = mean(dn n):
+            d m = (cg + 2 + C_MEAN) u mean(G |n|);   rest = rs [cg u G + |n| d m + 2u |n m| + u |dn - n m|] + u |du|,  from the rs the forward wrote
+  gate_residual (Wan, fp32):  x + y gate[g] is a product and an add or one FMA: 2u (|x| + |y g|).  gate_bwd is one product and one rounding: bit for bit.
+
+The CogVideoX gate_residual, x' of the residual + LayerNorm pass, dy = bf16(gate dx), the Wan gate_bwd and the noise kernels are bit-exact with a torch expression;
+they need no bound."""
 import math
 
 import numpy as np
@@ -610,3 +647,451 @@ def adamw_state(n, seed=0):
     z = slice(n // 3, n // 3 + max(1, n // 8))
     gr[z], m[z], v[z] = 0, 0, 0
     return p, gr, m, v, z
+
+
+# ------------------------------------------------------------------------------------------ one-wave-per-row norm kernels (csrc/row_ln.h and its three users)
+def nv_of(D):
+    return -(-D // 512)
+
+
+def c_sum(D):
+    """fp32 additions behind one element of a row sum: 8 NV - 1 serial per lane, six in wave_sum"""
+    return 8.0 * nv_of(D) + 5.0
+
+
+def c_mean(D):
+    return c_sum(D) + 1.0
+
+
+def c_rstd(D):
+    return c_mean(D) / 2.0 + 4.0
+
+
+def c_rms(D):
+    return c_mean(D) / 2.0 + 3.0
+
+
+def _eps32(eps):
+    return float(np.float32(eps))
+
+
+def row_stats64(x, eps):
+    """x [..., D] -> mean, rstd [..., 1], xhat, K = mean|x| rstd   (fp64, eps as the float the C entry receives)"""
+    x = _t64(x)
+    mean = x.mean(-1, keepdim=True)
+    d = x - mean
+    rstd = (d.pow(2).mean(-1, keepdim=True) + _eps32(eps)).rsqrt()
+    return mean, rstd, d * rstd, x.abs().mean(-1, keepdim=True) * rstd
+
+
+def stats_tols(x, eps):
+    """bounds of the mean / rstd outputs ([..., 1]) and of the computed xhat ([..., D]) of a LayerNorm forward"""
+    D = x.shape[-1]
+    _, rstd, xh, K = row_stats64(x, eps)
+    second = 0.5 * (c_mean(D) * U * K) ** 2
+    tol_mean = c_mean(D) * U * _t64(x).abs().mean(-1, keepdim=True)
+    tol_rstd = rstd * (c_rstd(D) * U + second)
+    e_xhat = U * ((c_rstd(D) + 2.0) * xh.abs() + c_mean(D) * K) + second * xh.abs()
+    return tol_mean, tol_rstd, e_xhat
+
+
+def cog_rows(tab_v, tab_t, B, S, Lt, wrong=None):
+    """per-range [B, D] tables -> [B, S, D]: rows s < Lt take the text table.  wrong "text_first_video": the first video row of every sample takes the text table"""
+    s = torch.arange(S, device=tab_v.device)
+    text = s < (Lt + 1 if wrong == "text_first_video" and 0 < Lt < S else Lt)
+    return torch.where(text[None, :, None], tab_t[:, None, :], tab_v[:, None, :])
+
+
+def cog_ln_fwd_ref64(xn, w, b, s1p, shift, eps):
+    """xn [B,S,D] the LayerNorm input; s1p / shift [B,S,D] (cog_rows) or None -> n, mean, rstd fp64"""
+    mean, rstd, xh, _ = row_stats64(xn, eps)
+    alpha = _t64(w) if s1p is None else _t64(w) * _t64(s1p)
+    beta = _t64(b) if s1p is None else _t64(b) * _t64(s1p) + _t64(shift)
+    return xh * alpha + beta, mean.squeeze(-1), rstd.squeeze(-1)
+
+
+def cog_ln_fwd_tol(xn, w, b, s1p, shift, eps, ref_n):
+    """-> bounds of n (bf16 store), mean, rstd"""
+    tol_mean, tol_rstd, e_xh = stats_tols(xn, eps)
+    _, _, xh, _ = row_stats64(xn, eps)
+    w, b = _t64(w), _t64(b)
+    if s1p is None:
+        alpha, e_alpha, e_beta = w, 0.0, 0.0
+    else:
+        alpha = w * _t64(s1p)
+        e_alpha = U * alpha.abs()
+        e_beta = U * ((b * _t64(s1p)).abs() + (b * _t64(s1p) + _t64(shift)).abs())
+    rest = e_xh * alpha.abs() + xh.abs() * e_alpha + U * (xh * alpha).abs() + e_beta + U * ref_n.abs()
+    return bf16_tol(ref_n, rest), tol_mean.squeeze(-1), tol_rstd.squeeze(-1)
+
+
+def ln_bwd_ref64(g, x, mean, rstd, dres=None):
+    """g = the incoming gradient times the affine (fp64, [..., D]); mean / rstd [...] as the forward wrote them -> rstd (g - c1 - xhat c2) [+ dres]"""
+    g, mean, rstd = _t64(g), _t64(mean).unsqueeze(-1), _t64(rstd).unsqueeze(-1)
+    xh = (_t64(x) - mean) * rstd
+    c1, c2 = g.mean(-1, keepdim=True), (g * xh).mean(-1, keepdim=True)
+    d = rstd * (g - c1 - xh * c2)
+    return d if dres is None else d + _t64(dres)
+
+
+def ln_bwd_rest(g, x, mean, rstd, cg, dres=None):
+    """fp32 error of ln_bwd_ref64's expression; cg u |g| is the error g arrives with"""
+    D = x.shape[-1]
+    g, mean, rstd = _t64(g), _t64(mean).unsqueeze(-1), _t64(rstd).unsqueeze(-1)
+    xh = (_t64(x) - mean) * rstd
+    c1, c2 = g.mean(-1, keepdim=True), (g * xh).mean(-1, keepdim=True)
+    e_c1 = (cg + c_mean(D)) * g.abs().mean(-1, keepdim=True)
+    e_c2 = (cg + 3.0 + c_mean(D)) * (g * xh).abs().mean(-1, keepdim=True)
+    inner = g - c1 - xh * c2
+    e = cg * g.abs() + e_c1 + (g - c1).abs() + xh.abs() * e_c2 + 3.0 * (xh * c2).abs() + inner.abs()
+    rest = U * rstd.abs() * (e + inner.abs())
+    if dres is not None:
+        rest = rest + U * (rstd * inner + _t64(dres)).abs()
+    return rest
+
+
+def wan_ln_fwd_ref64(x, gid, w, b, shift, scale, eps):
+    """x [rows, D]; shift / scale [G, D] views of the table, gid [rows] or None (row 0) -> out, mean, rstd fp64 (round_xhat is not part of the reference)"""
+    mean, rstd, o, _ = row_stats64(x, eps)
+    if w is not None:
+        o = o * _t64(w) + _t64(b)
+    if scale is not None:
+        gi = torch.zeros(x.shape[0], dtype=torch.long, device=x.device) if gid is None else gid.long()
+        o = o * (1.0 + _t64(scale)[gi]) + _t64(shift)[gi]
+    return o, mean.squeeze(-1), rstd.squeeze(-1)
+
+
+def wan_ln_fwd_tol(x, gid, w, b, shift, scale, eps, round_xhat, ref, out_bf16=True):
+    tol_mean, tol_rstd, e = stats_tols(x, eps)
+    _, _, v, _ = row_stats64(x, eps)
+    if round_xhat:
+        e = e + half_ulp_bf16(v.abs() + e)
+    if w is not None:
+        w, b = _t64(w), _t64(b)
+        e = e * w.abs() + U * (v * w).abs() + U * (v * w + b).abs()
+        v = v * w + b
+    if scale is not None:
+        gi = torch.zeros(x.shape[0], dtype=torch.long, device=x.device) if gid is None else gid.long()
+        s1 = 1.0 + _t64(scale)[gi]
+        e = e * s1.abs() + 2.0 * U * (v * s1).abs() + U * (v * s1 + _t64(shift)[gi]).abs()
+    tol = bf16_tol(ref, e) if out_bf16 else e + U * ref.abs()
+    return tol, tol_mean.squeeze(-1), tol_rstd.squeeze(-1)
+
+
+def wan_ln_bwd_g64(dy, gid, w, scale):
+    """-> g = dy (1 + scale[g]) w in fp64 and cg, the roundings it carries in the kernel (1 + scale, the product; the product with w)"""
+    g, cg = _t64(dy), 0.0
+    if scale is not None:
+        gi = torch.zeros(dy.shape[0], dtype=torch.long, device=dy.device) if gid is None else gid.long()
+        g, cg = g * (1.0 + _t64(scale)[gi]), cg + 2.0
+    if w is not None:
+        g, cg = g * _t64(w), cg + 1.0
+    return g, cg
+
+
+def _rope_rows(cos, sin, rows, L, D, head_dim, device):
+    """tables [L, head_dim / 2] -> per-row, per-pair [rows, D / 2] fp64"""
+    r = torch.arange(rows, device=device) % L
+    rep = D // head_dim
+    return _t64(cos).to(device)[r].repeat(1, rep), _t64(sin).to(device)[r].repeat(1, rep)
+
+
+def _rot64(y, cs, sn, transpose=False):
+    a, b = y[:, 0::2], y[:, 1::2]
+    if transpose:
+        return torch.stack([a * cs + b * sn, -a * sn + b * cs], -1).flatten(1)
+    return torch.stack([a * cs - b * sn, a * sn + b * cs], -1).flatten(1)
+
+
+def rms_rope_ref64(u, w, cos, sin, L, head_dim, eps):
+    """u [rows, D] -> out, rs fp64: u rs w rotated, nothing rounded"""
+    u = _t64(u)
+    rs = (u.pow(2).mean(-1, keepdim=True) + _eps32(eps)).rsqrt()
+    y = u * rs * _t64(w)
+    if cos is not None:
+        y = _rot64(y, *_rope_rows(cos, sin, u.shape[0], L, u.shape[1], head_dim, u.device))
+    return y, rs.squeeze(-1)
+
+
+def rms_rope_fwd_tol(u, w, cos, sin, L, head_dim, eps, ref):
+    """n = bf16(u rs) and y = bf16(n w) each add their half ulp; the rotation carries both through |cos|, |sin|; then the store"""
+    u, w = _t64(u), _t64(w)
+    D = u.shape[1]
+    rs = (u.pow(2).mean(-1, keepdim=True) + _eps32(eps)).rsqrt()
+    n = u * rs
+    e = (c_rms(D) + 1.0) * U * n.abs()
+    e = e + half_ulp_bf16(n.abs() + e)
+    e = e * w.abs() + U * (n * w).abs()
+    tol_rs = (c_rms(D) * U * rs).squeeze(-1)
+    if cos is None:
+        return bf16_tol(ref, e), tol_rs
+    y = n * w
+    e = e + half_ulp_bf16(y.abs() + e)
+    cs, sn = (t.abs() for t in _rope_rows(cos, sin, u.shape[0], L, D, head_dim, u.device))
+    ya, yb, ea, eb = y[:, 0::2].abs(), y[:, 1::2].abs(), e[:, 0::2], e[:, 1::2]
+    rest = torch.stack([ea * cs + eb * sn + 2.0 * U * (ya * cs + yb * sn), ea * sn + eb * cs + 2.0 * U * (ya * sn + yb * cs)], -1).flatten(1)
+    return bf16_tol(ref, rest), tol_rs
+
+
+def rms_rope_bwd_ref64(dout, u, rs, w, cos, sin, L, head_dim):
+    """du = rs (dn - n mean(dn n)), dn = w R^T dout, n = u rs, from the fp32 rs the forward wrote"""
+    dn, u, rs = _t64(dout), _t64(u), _t64(rs).unsqueeze(-1)
+    if cos is not None:
+        dn = _rot64(dn, *_rope_rows(cos, sin, u.shape[0], L, u.shape[1], head_dim, u.device), transpose=True)
+    dn = dn * _t64(w)
+    n = u * rs
+    return rs * (dn - n * (dn * n).mean(-1, keepdim=True))
+
+
+def rms_rope_bwd_tol(dout, u, rs, w, cos, sin, L, head_dim, ref):
+    g, u, rs, w = _t64(dout), _t64(u), _t64(rs).unsqueeze(-1), _t64(w)
+    D = u.shape[1]
+    if cos is None:
+        dn, G, cg = g * w, (g * w).abs(), 1.0
+    else:
+        cs, sn = _rope_rows(cos, sin, u.shape[0], L, D, head_dim, u.device)
+        dn = _rot64(g, cs, sn, transpose=True) * w
+        a, b = g[:, 0::2].abs(), g[:, 1::2].abs()
+        G, cg = torch.stack([a * cs.abs() + b * sn.abs(), a * sn.abs() + b * cs.abs()], -1).flatten(1) * w.abs(), 3.0
+    n = u * rs
+    m = (dn * n).mean(-1, keepdim=True)
+    e_m = (cg + 2.0 + c_mean(D)) * (G * n.abs()).mean(-1, keepdim=True)
+    inner = dn - n * m
+    rest = U * rs * (cg * G + n.abs() * e_m + 2.0 * (n * m).abs() + inner.abs()) + U * ref.abs()
+    return bf16_tol(ref, rest)
+
+
+def wan_gate_ref64(x, y, gid, gate):
+    """x + y gate[g] fp64 and its bound 2u (|x| + |y g|): a product and an add, or one FMA"""
+    p = _t64(y)
+    if gate is not None:
+        gi = torch.zeros(y.shape[0], dtype=torch.long, device=y.device) if gid is None else gid.long()
+        p = p * _t64(gate)[gi]
+    ref = p if x is None else _t64(x) + p
+    return ref, 2.0 * U * (p.abs() + (0.0 if x is None else _t64(x).abs()))
+
+
+# ---- float32 restatements of the row kernels
+def _row_sum_f32(t, D, wrong=None):
+    """t [rows, D] float32 -> the row sums [rows, 1] in a wave's order (lane l adds elements (64 c + l) 8 .. + 7 of chunk c = 0 .. NV - 1 serially, then
+    v += shfl_xor(v, 32 .. 1)), divided by D.  wrong "mask8": the last valid group of eight is left out; "div_nv": divided by 512 NV"""
+    rows, NV = t.shape[0], nv_of(D)
+    pad = np.zeros((rows, NV * 512), np.float32)              # adding the +0 padding is exact
+    pad[:, :D] = t
+    if wrong == "mask8":
+        pad[:, D - 8:D] = 0
+    pad = pad.reshape(rows, NV, 64, 8)
+    acc = np.zeros((rows, 64), np.float32)
+    for c in range(NV):
+        for j in range(8):
+            acc = acc + pad[:, c, :, j]
+    lane = np.arange(64)
+    for m in (32, 16, 8, 4, 2, 1):
+        acc = acc + acc[:, lane ^ m]
+    return (acc[:, :1] / np.float32(512 * NV if wrong == "div_nv" else D)).astype(np.float32)
+
+
+def _ln_stats_f32(x, eps, wrong=None):
+    """x [rows, D] float32 -> mean, rstd [rows, 1]: the exact two-pass form of the kernels"""
+    D = x.shape[1]
+    mean = _row_sum_f32(x, D, wrong)
+    d = x - mean
+    var = _row_sum_f32(d * d, D, wrong)
+    return mean, (_ONE / np.sqrt(var + np.float32(eps))).astype(np.float32)
+
+
+def cog_ln_fwd_f32(xn, w, b, s1p, shift, eps, wrong=None):
+    """xn [B,S,D]; s1p / shift [B,S,D] or None -> n (bf16 values), mean, rstd [B,S] float32"""
+    shape = xn.shape
+    x = f32(xn).reshape(-1, shape[-1])
+    mean, rstd = _ln_stats_f32(x, eps, wrong)
+    if s1p is None:
+        alpha, beta = f32(w), f32(b)
+    else:
+        s = f32(s1p).reshape(x.shape)
+        alpha, beta = f32(w) * s, f32(b) * s + f32(shift).reshape(x.shape)
+    n = (x - mean) * rstd * alpha + beta
+    return bf16_round(n).reshape(shape), mean.reshape(shape[:-1]), rstd.reshape(shape[:-1])
+
+
+def ln_bwd_f32(g, x, mean, rstd, dres=None, wrong=None):
+    """g [rows, D] float32 (already times the affine) -> rstd (g - c1 - xhat c2) [+ dres], float32, unrounded.  wrong "no_c1": without c1"""
+    D = x.shape[1]
+    mean, rstd = f32(mean).reshape(-1, 1), f32(rstd).reshape(-1, 1)
+    xh = (x - mean) * rstd
+    c1 = _row_sum_f32(g, D, wrong)
+    c2 = _row_sum_f32(g * xh, D, wrong)
+    if wrong == "no_c1":
+        c1 = np.zeros_like(c1)
+    d = rstd * (g - c1 - xh * c2)
+    return d if dres is None else f32(dres).reshape(d.shape) + d
+
+
+def cog_ln_bwd_f32(dn, xn, mean, rstd, w, s1p, dres=None, wrong=None):
+    """-> dx (bf16 values) [B,S,D]"""
+    shape = xn.shape
+    alpha = f32(w) if s1p is None else f32(w) * f32(s1p).reshape(-1, shape[-1])
+    g = f32(dn).reshape(-1, shape[-1]) * alpha
+    return bf16_round(ln_bwd_f32(g, f32(xn).reshape(-1, shape[-1]), mean, rstd, dres, wrong)).reshape(shape)
+
+
+def _gid_np(gid, rows, wrong=None):
+    gi = np.zeros(rows, np.int64) if gid is None else np.asarray(gid.cpu() if torch.is_tensor(gid) else gid).astype(np.int64)
+    if wrong == "gid_neighbour" and rows > 1:                    # one row reads its neighbour's group
+        r = rows // 2
+        gi = gi.copy()
+        gi[r] = gi[r - 1]
+    return gi
+
+
+def wan_ln_fwd_f32(x, gid, w, b, shift, scale, eps, round_xhat, out_bf16=True, wrong=None):
+    x = f32(x)
+    mean, rstd = _ln_stats_f32(x, eps, wrong)
+    o = (x - mean) * rstd
+    if round_xhat and wrong != "no_round":
+        o = bf16_round(o)
+    if w is not None:
+        o = o * f32(w) + f32(b)
+    if scale is not None:
+        gi = _gid_np(gid, x.shape[0], wrong)
+        o = o * (_ONE + f32(scale)[gi]) + f32(shift)[gi]
+    return (bf16_round(o) if out_bf16 else o), mean[:, 0], rstd[:, 0]
+
+
+def wan_ln_bwd_f32(dy, x, mean, rstd, gid, w, scale, dres=None, wrong=None):
+    """-> dx float32.  wrong "scale_no1p": scale where 1 + scale belongs"""
+    g, x = f32(dy), f32(x)
+    if scale is not None:
+        s = f32(scale)[_gid_np(gid, x.shape[0], wrong)]
+        g = g * (s if wrong == "scale_no1p" else _ONE + s)
+    if w is not None:
+        g = g * f32(w)
+    return ln_bwd_f32(g, x, mean, rstd, dres, wrong)
+
+
+def _rope_rows_f32(cos, sin, rows, L, D, head_dim, wrong=None):
+    r = np.arange(rows)
+    r = np.minimum(r, L - 1) if wrong == "row_no_mod" else r % L          # `row` in place of `row % L` (clamped here to the table a device would run past)
+    rep = D // head_dim
+    return np.tile(f32(cos)[r], (1, rep)), np.tile(f32(sin)[r], (1, rep))
+
+
+def rms_rope_fwd_f32(u, w, cos, sin, L, head_dim, eps, wrong=None):
+    """-> out (bf16 values), rs [rows] float32.  wrong "per_head": the mean of squares taken over each head"""
+    u, w = f32(u), f32(w)
+    rows, D = u.shape
+    if wrong == "per_head":
+        uh = u.reshape(rows * (D // head_dim), head_dim)
+        ms = np.repeat(_row_sum_f32(uh * uh, head_dim).reshape(rows, D // head_dim), head_dim, axis=1)
+    else:
+        ms = _row_sum_f32(u * u, D, wrong)
+    rs = (_ONE / np.sqrt(ms + np.float32(eps))).astype(np.float32)
+    y = bf16_round(bf16_round(u * rs) * w)
+    if cos is not None:
+        cs, sn = _rope_rows_f32(cos, sin, rows, L, D, head_dim, wrong)
+        a, b = y[:, 0::2], y[:, 1::2]
+        y = np.stack([a * cs - b * sn, a * sn + b * cs], -1).reshape(rows, D)
+    return bf16_round(y), rs[:, 0]
+
+
+def rms_rope_bwd_f32(dout, u, rs, w, cos, sin, L, head_dim, wrong=None):
+    """-> du (bf16 values).  wrong "no_transpose": the forward's rotation applied to the gradient"""
+    dn, u, w, rs = f32(dout), f32(u), f32(w), f32(rs).reshape(-1, 1)
+    rows, D = u.shape
+    if cos is not None:
+        cs, sn = _rope_rows_f32(cos, sin, rows, L, D, head_dim, wrong)
+        a, b = dn[:, 0::2], dn[:, 1::2]
+        if wrong == "no_transpose":
+            dn = np.stack([a * cs - b * sn, a * sn + b * cs], -1).reshape(rows, D)
+        else:
+            dn = np.stack([a * cs + b * sn, -a * sn + b * cs], -1).reshape(rows, D)
+    dn = dn * w
+    n = u * rs
+    m = _row_sum_f32(dn * n, D, wrong)
+    return bf16_round(rs * (dn - n * m))
+
+
+def wan_gate_f32(x, y, gid, gate, wrong=None):
+    p = f32(y)
+    if gate is not None:
+        p = p * f32(gate)[_gid_np(gid, p.shape[0], wrong)]
+    return p if x is None else f32(x) + p
+
+
+# ---- cases shared by tests/test_row_tol_host.py and tests/test_gpu_row_kernels.py
+ROW_WIDTHS = [8, 512, 520, 1024, 1288, 2048, 2560, 3072, 3080, 4088, 4096]          # NV 1, 1, 2, 2, 3, 4, 5, 6, 7, 8, 8: full and partly filled last chunks alternate
+COG_LAYOUTS = [(2, 37, 6), (3, 70, 33), (2, 33, 0), (2, 33, 33), (3, 5, 2)]          # (B, S, text_len)
+WAN_LN_WIDTHS, WAN_LN_ROWS = [8, 264, 520, 3072, 4088, 4096], [1, 5, 9]
+RMS_SHAPES = [(264, 24), (264, 8), (520, 40), (3072, 128), (4096, 128)]               # (D, head_dim)
+RMS_L, RMS_B = 7, 3
+_GID_CYCLE = [2, 0, 1, 0, 2, 1, 1, 2, 0]
+
+
+def cog_layouts(D):
+    """the two large layouts at every width, the three small ones where a row is cheap"""
+    return COG_LAYOUTS if D <= 1288 else COG_LAYOUTS[:2]
+
+
+def plant_rows(x2):
+    """x2 [rows, D] float, in place; -> the planted row indices.  Last row: values of 0.01 and a single 200 in the last valid group of eight columns; row 0
+    (from two rows): the constant 0.3, variance 0; row 1 (from three rows): zeros"""
+    rows, D = x2.shape
+    x2[rows - 1] *= 0.005
+    x2[rows - 1, D - 3] = 200.0
+    idx = [rows - 1]
+    if rows >= 2:
+        x2[0] = 0.3
+        idx.append(0)
+    if rows >= 3:
+        x2[1] = 0.0
+        idx.append(1)
+    return idx
+
+
+def cog_case(B, S, Lt, D, seed=0):
+    """x, y, dn, dres bf16 [B,S,D] (x = 2 randn + 0.3 with plant_rows, y zero in the planted rows so that they reach the LayerNorm), gates [B,2,D] = (video, text),
+    mod [B,4,D] = (shift_v, 1 + scale_v, shift_t, 1 + scale_t), w, b"""
+    g = torch.Generator().manual_seed(7919 * seed + 131 * B + 17 * S + 3 * Lt + D)
+    x = torch.randn(B, S, D, generator=g) * 2 + 0.3
+    y = torch.randn(B, S, D, generator=g)
+    y.view(-1, D)[plant_rows(x.view(-1, D))] = 0
+    gates = torch.randn(B, 2, D, generator=g)
+    w, b = 1 + 0.2 * torch.randn(D, generator=g), 0.2 * torch.randn(D, generator=g)
+    mod = 0.3 * torch.randn(B, 4, D, generator=g)
+    mod[:, 1] += 1
+    mod[:, 3] += 1
+    dn, dres = (torch.randn(B, S, D, generator=g).to(torch.bfloat16) for _ in range(2))
+    return dict(x=x.to(torch.bfloat16), y=y.to(torch.bfloat16), gates=gates, w=w, b=b, mod=mod, dn=dn, dres=dres)
+
+
+def cog_x_new(c, B, S, Lt):
+    """bf16(x + bf16(gate y)): the torch expression the forward's residual stream must equal bit for bit"""
+    gfull = cog_rows(c["gates"][:, 0], c["gates"][:, 1], B, S, Lt)
+    return c["x"] + (gfull * c["y"].float()).to(torch.bfloat16)
+
+
+def wan_ln_case(rows, D, xdt=torch.float32, seed=0):
+    """x [rows, D] of xdt with plant_rows; gid over 3 groups, not monotone; tab [3,6,D] (0.5 randn: columns 2 gate, 3 shift, 4 scale, 5 gate_prev); w, b;
+    y bf16 (zero in the planted rows); dy bf16 and fp32; dres fp32"""
+    g = torch.Generator().manual_seed(104729 * seed + 31 * rows + D + (5 if xdt == torch.float32 else 0))
+    x = torch.randn(rows, D, generator=g) * 2 + 0.3
+    y = torch.randn(rows, D, generator=g)
+    y[plant_rows(x)] = 0
+    gid = torch.tensor([_GID_CYCLE[i % 9] for i in range(rows)], dtype=torch.int32)
+    tab = 0.5 * torch.randn(3, 6, D, generator=g)
+    w, b = torch.randn(D, generator=g), torch.randn(D, generator=g)
+    dy32 = torch.randn(rows, D, generator=g)
+    dres = torch.randn(rows, D, generator=g)
+    return dict(x=x.to(xdt), y=y.to(torch.bfloat16), gid=gid, tab=tab, w=w, b=b, dy=dy32.to(torch.bfloat16), dy32=dy32, dres=dres)
+
+
+def rms_case(D, head_dim, seed=0):
+    """u, dout bf16 [RMS_B RMS_L, D] (u with plant_rows), w bf16, cos / sin [RMS_L, head_dim / 2] of random angles"""
+    rows = RMS_B * RMS_L
+    g = torch.Generator().manual_seed(15485863 * seed + D + head_dim)
+    u = torch.randn(rows, D, generator=g) * 2 + 0.3
+    plant_rows(u)
+    w = (1 + 0.2 * torch.randn(D, generator=g)).to(torch.bfloat16)
+    ang = 2 * math.pi * torch.rand(RMS_L, head_dim // 2, generator=g)
+    dout = torch.randn(rows, D, generator=g).to(torch.bfloat16)
+    return dict(u=u.to(torch.bfloat16), w=w, cos=ang.cos().contiguous(), sin=ang.sin().contiguous(), dout=dout)

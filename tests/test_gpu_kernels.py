@@ -129,6 +129,27 @@ def test_ln_modulate_fwd_bwd(ops, D, text_len, impl):
     # plain LN (no modulation)
     y2 = lnm(dev(x), dev(w), dev(b), None, 0, 1e-5)
     assert (y2.double().cpu() - n.detach()).abs().max().item() < 0.03
+    # per element (tests/row_tol.py): the bf16 half ulp of each result plus the counted fp32 error; mean and rstd are judged too, and the gradient is held to the
+    # expression evaluated from them.  The C entry behind `lnm` is called once more for them: the same kernel on the same input writes the same bits
+    from videogpa_amd import _lib
+    md, st = dev(mod), torch.cuda.current_stream().cuda_stream
+    mean, rstd, n2 = torch.empty(B, S, device="cuda"), torch.empty(B, S, device="cuda"), torch.empty_like(y)
+    if impl == "fused":
+        _lib.call("vgpa_residual_ln_fwd", xd.detach(), None, None, None, 0, dev(w), dev(b), md[:, 0], md[:, 1], md[:, 2], md[:, 3], md.stride(0), B, S, D, text_len, 1e-5,
+                  None, n2, D, mean, rstd, st)
+    else:
+        _lib.call("vgpa_ln_modulate_fwd", xd.detach(), dev(w), dev(b), md[:, 0], md[:, 1], md[:, 2], md[:, 3], md.stride(0), B, S, D, text_len, 1e-5, n2, mean, rstd, st)
+    assert torch.equal(n2, y.detach())
+    s1p, shf = row_tol.cog_rows(mod[:, 1], mod[:, 3], B, S, text_len), row_tol.cog_rows(mod[:, 0], mod[:, 2], B, S, text_len)
+    ref = row_tol.cog_ln_fwd_ref64(x, w, b, s1p, shf, 1e-5)
+    tols = row_tol.cog_ln_fwd_tol(x, w, b, s1p, shf, 1e-5, ref[0])
+    for name, got, r, t in zip(("n", "mean", "rstd"), (y.detach().cpu(), mean.cpu(), rstd.cpu()), ref, tols):
+        assert not row_tol.judge(f"ln_modulate {name}", got, r, t)
+    gg = dy.double() * w.double() * s1p.double()
+    gref = row_tol.ln_bwd_ref64(gg, x, mean.cpu(), rstd.cpu())
+    assert not row_tol.judge("ln_modulate dx", xd.grad.cpu(), gref, row_tol.bf16_tol(gref, row_tol.ln_bwd_rest(gg, x, mean.cpu(), rstd.cpu(), 2.0)))
+    pref = row_tol.cog_ln_fwd_ref64(x, w, b, None, None, 1e-5)
+    assert not row_tol.judge("plain LN", y2.cpu(), pref[0], row_tol.cog_ln_fwd_tol(x, w, b, None, None, 1e-5, pref[0])[0])
 
 
 def test_gate_residual_and_gelu(ops):
@@ -505,6 +526,10 @@ def test_ln_modulate_max_width_and_batch_boundaries(ops):
     sc = torch.cat([mod[:, 3:4].expand(B, Lt, D), mod[:, 1:2].expand(B, S - Lt, D)], 1).double()
     sh = torch.cat([mod[:, 2:3].expand(B, Lt, D), mod[:, 0:1].expand(B, S - Lt, D)], 1).double()
     assert (y.double().cpu() - (n * sc + sh)).abs().max().item() < 0.04
+    # per element (tests/row_tol.py), where 0.04 absolute said nothing about which modulation row a token took; this test's tables hold scale, not 1 + scale
+    s1p, shf = row_tol.cog_rows(mod[:, 1], mod[:, 3], B, S, Lt), row_tol.cog_rows(mod[:, 0], mod[:, 2], B, S, Lt)
+    ref = row_tol.cog_ln_fwd_ref64(x, w, b, s1p, shf, 1e-5)
+    assert not row_tol.judge("ln_modulate D 4096", y.cpu(), ref[0], row_tol.cog_ln_fwd_tol(x, w, b, s1p, shf, 1e-5, ref[0])[0])
 
 
 @pytest.mark.parametrize("B,S,D,Lt", [(2, 37, 128, 6), (1, 300, 3072, 226), (3, 21, 512, 0), (2, 33, 256, 33)])

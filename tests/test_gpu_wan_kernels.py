@@ -522,6 +522,22 @@ def test_wan_ln_mod_forward_backward(xdt, affine, mod, rnd):
     assert xg.grad.dtype == xdt
     tol = 1e-5 if xdt == torch.float32 else 2 ** -8
     assert (xg.grad.double() - xr.grad).abs().max().item() <= tol * xr.grad.abs().max().item()
+    # per element (tests/row_tol.py): the reference is the unrounded expression, round_xhat's half ulp is part of the bound; mean and rstd are judged, and the
+    # gradient is held to the expression evaluated from them.  The C entry is called once more for them: the same kernel on the same input writes the same bits
+    import row_tol
+    from videogpa_amd import _lib
+    a = (x, gid if mod else None, w, b, tab[:, 3] if mod else None, tab[:, 4] if mod else None, 1e-6)
+    mean, rstd, o2 = torch.empty(rows, device="cuda"), torch.empty(rows, device="cuda"), torch.empty_like(out)
+    _lib.call("vgpa_wan_ln_mod_fwd", x, 0 if xdt == torch.float32 else 1, None, None, None, a[1], w, b, a[4], a[5], tab.stride(0), rows, C, 1e-6, int(rnd), o2, 1, C,
+              None, None, mean, rstd, torch.cuda.current_stream().cuda_stream)
+    assert torch.equal(o2, out.detach())
+    ref = row_tol.wan_ln_fwd_ref64(*a)
+    tols = row_tol.wan_ln_fwd_tol(*a, rnd, ref[0])
+    for name, got, r, t in zip(("out", "mean", "rstd"), (out.detach(), mean, rstd), ref, tols):
+        assert not row_tol.judge(f"wan ln_mod {name}", got, r, t)
+    g64, cg = row_tol.wan_ln_bwd_g64(dy, a[1], w, a[5])
+    gref, rest = row_tol.ln_bwd_ref64(g64, x, mean, rstd), row_tol.ln_bwd_rest(g64, x, mean, rstd, cg)
+    assert not row_tol.judge("wan ln_mod dx", xg.grad, gref, rest if xdt == torch.float32 else row_tol.bf16_tol(gref, rest))
 
 
 @pytest.mark.parametrize("rows,C", [(5, 264), (9, 3072), (6, 4096)])
@@ -640,6 +656,18 @@ def test_wan_rms_rope_forward_backward(rope):
     r.backward(dout.double())
     assert (out.double() - r.detach()).abs().max().item() <= 1.5 * 2 ** -8 * r.detach().abs().max().item()      # two bf16 roundings + the output's
     assert (ug.grad.double() - ur.grad).abs().max().item() <= 2.5 * 2 ** -8 * ur.grad.abs().max().item()
+    # per element (tests/row_tol.py): each intermediate bf16 rounding's half ulp carried through |w|, |cos|, |sin|; rstd judged; the gradient from the device's rstd
+    import row_tol
+    from videogpa_amd import _lib
+    u2, d2, st = u.view(B * L, C), dout.view(B * L, C), torch.cuda.current_stream().cuda_stream
+    rs, o2 = torch.empty(B * L, device="cuda"), torch.empty_like(u2)
+    _lib.call("vgpa_wan_rms_rope_fwd", u2, C, w, cos, sin, L, d, B * L, C, 1e-6, o2, C, rs, st)
+    assert torch.equal(o2, out.detach().view(B * L, C))
+    ref, rs_ref = row_tol.rms_rope_ref64(u2, w, cos, sin, L, d, 1e-6)
+    tol, tol_rs = row_tol.rms_rope_fwd_tol(u2, w, cos, sin, L, d, 1e-6, ref)
+    assert not row_tol.judge("rms_rope out", o2, ref, tol) and not row_tol.judge("rms_rope rstd", rs, rs_ref, tol_rs)
+    gref = row_tol.rms_rope_bwd_ref64(d2, u2, rs, w, cos, sin, L, d)
+    assert not row_tol.judge("rms_rope du", ug.grad.view(B * L, C), gref, row_tol.rms_rope_bwd_tol(d2, u2, rs, w, cos, sin, L, d, gref))
 
 
 # ------------------------------------------------------------------------------------------------ fp8 operands (csrc/fp8.hip)

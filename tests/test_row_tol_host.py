@@ -1,4 +1,4 @@
-"""tests/row_tol.py on the CPU: on every input family of tests/test_gpu_step_kernels.py, at its shapes, the float32 restatement of each kernel stays inside
+"""tests/row_tol.py on the CPU: on every input family of tests/test_gpu_step_kernels.py and tests/test_gpu_row_kernels.py, at its shapes, the float32 restatement of each kernel stays inside
 the bound around the fp64 reference -- and `judge` REJECTS deliberately wrong restatements, which is how a reader checks that the device tests can fail.
 No mutated kernel is ever built.  `-s` prints, per kernel and family, the largest error of the restatement over its bound."""
 import numpy as np
@@ -212,3 +212,239 @@ def test_judge_reports_where_and_treats_nan_as_outside():
     msgs = R.judge("x", got, ref, torch.full_like(ref, 0.5))
     assert msgs[0].startswith("x: 2 of 6") and any("x[1, 2]" in m for m in msgs) and any("x[0, 1]: got 1, want 0, bound 0.5" in m for m in msgs)
     assert R.judge("x", ref, ref, 0.0) == []
+
+
+# ------------------------------------------------------------------------------------------ one-wave-per-row norm kernels
+def _ratio(got, ref, tol):
+    return R.worst(got, ref, tol)[0]
+
+
+def _cog_tabs(c, B, S, Lt, mod, wrong=None):
+    if not mod:
+        return None, None
+    m = c["mod"]
+    return R.cog_rows(m[:, 1], m[:, 3], B, S, Lt, wrong), R.cog_rows(m[:, 0], m[:, 2], B, S, Lt, wrong)
+
+
+def _cog_fwd(c, B, S, Lt, mod, with_y, eps=1e-5, wrong=None):
+    """-> problems, worst ratios (n, mean, rstd), xn, restatement's mean / rstd"""
+    xn = R.cog_x_new(c, B, S, Lt) if with_y else c["x"]
+    s1p, shift = _cog_tabs(c, B, S, Lt, mod)
+    ref = R.cog_ln_fwd_ref64(xn, c["w"], c["b"], s1p, shift, eps)
+    tols = R.cog_ln_fwd_tol(xn, c["w"], c["b"], s1p, shift, eps, ref[0])
+    got = R.cog_ln_fwd_f32(xn, c["w"], c["b"], *_cog_tabs(c, B, S, Lt, mod, wrong), eps, wrong)
+    bad = [m for i, n in enumerate(("n", "mean", "rstd")) for m in R.judge(f"cog fwd {n}", got[i], ref[i], tols[i])]
+    return bad, [_ratio(got[i], ref[i], tols[i]) for i in range(3)], xn, got[1], got[2]
+
+
+def _cog_bwd(c, B, S, Lt, mod, xn, mean, rstd, dres, wrong=None):
+    s1p, _ = _cog_tabs(c, B, S, Lt, mod)
+    alpha = c["w"].double() if s1p is None else c["w"].double() * s1p.double()
+    g = c["dn"].double() * alpha
+    ref = R.ln_bwd_ref64(g, xn, mean, rstd, dres)
+    tol = R.bf16_tol(ref, R.ln_bwd_rest(g, xn, mean, rstd, 2.0 if mod else 0.0, dres))
+    got = R.cog_ln_bwd_f32(c["dn"], xn, mean, rstd, c["w"], s1p, dres, wrong)
+    return R.judge("cog bwd dx", got, ref, tol), _ratio(got, ref, tol)
+
+
+@pytest.mark.parametrize("D", R.ROW_WIDTHS)
+def test_cog_ln_restatements_inside_bounds(D):
+    worst = np.zeros(4)
+    for B, S, Lt in R.cog_layouts(D):
+        c = R.cog_case(B, S, Lt, D)
+        for mod in (True, False):
+            for with_y in (True, False):
+                bad, r, xn, mean, rstd = _cog_fwd(c, B, S, Lt, mod, with_y)
+                assert not bad, bad
+                worst[:3] = np.maximum(worst[:3], r)
+            for dres in (c["dres"], None):
+                bad, r = _cog_bwd(c, B, S, Lt, mod, xn, mean, rstd, dres)
+                assert not bad, bad
+                worst[3] = max(worst[3], r)
+    print(f"cog LN D {D}: restatement / bound n {worst[0]:.3f} mean {worst[1]:.3f} rstd {worst[2]:.3f} dx {worst[3]:.3f}")
+
+
+def _wan_forms():
+    """(x dtype, affine, modulation, round_xhat, bf16 result): every combination the forward entry accepts without y"""
+    for xdt in (torch.float32, torch.bfloat16):
+        for affine in (False, True):
+            for mod in (False, True):
+                for rnd in (0, 1):
+                    yield xdt, affine, mod, rnd, True
+    yield torch.float32, False, True, 0, False
+    yield torch.float32, False, False, 0, False
+
+
+def _wan_fwd(c, affine, mod, rnd, out_bf16, x=None, eps=1e-6, wrong=None):
+    x = c["x"] if x is None else x
+    a = (x, c["gid"] if mod else None, c["w"] if affine else None, c["b"] if affine else None, c["tab"][:, 3] if mod else None, c["tab"][:, 4] if mod else None, eps)
+    ref = R.wan_ln_fwd_ref64(*a)
+    tols = R.wan_ln_fwd_tol(*a, rnd, ref[0], out_bf16)
+    got = R.wan_ln_fwd_f32(*a, rnd, out_bf16, wrong)
+    bad = [m for i, n in enumerate(("out", "mean", "rstd")) for m in R.judge(f"wan fwd {n}", got[i], ref[i], tols[i])]
+    return bad, max(_ratio(got[i], ref[i], tols[i]) for i in range(3)), got[1], got[2]
+
+
+def _wan_bwd(c, affine, mod, mean, rstd, dy, dres, wrong=None):
+    gid, w, scale = c["gid"] if mod else None, c["w"] if affine else None, c["tab"][:, 4] if mod else None
+    g, cg = R.wan_ln_bwd_g64(dy, gid, w, scale)
+    ref = R.ln_bwd_ref64(g, c["x"], mean, rstd, dres)
+    tol = R.ln_bwd_rest(g, c["x"], mean, rstd, cg, dres)
+    got = R.wan_ln_bwd_f32(dy, c["x"], mean, rstd, gid, w, scale, dres, wrong)
+    return R.judge("wan bwd dx", got, ref, tol), _ratio(got, ref, tol)
+
+
+@pytest.mark.parametrize("D", R.WAN_LN_WIDTHS)
+def test_wan_ln_restatements_inside_bounds(D):
+    wf = wb = 0.0
+    for rows in R.WAN_LN_ROWS:
+        for xdt, affine, mod, rnd, out_bf16 in _wan_forms():
+            c = R.wan_ln_case(rows, D, xdt)
+            bad, r, mean, rstd = _wan_fwd(c, affine, mod, rnd, out_bf16)
+            assert not bad, (rows, xdt, affine, mod, rnd, out_bf16, bad)
+            wf = max(wf, r)
+            if rnd:
+                continue
+            fp32_dy = not out_bf16
+            for dres in ((None,) if fp32_dy else (c["dres"], None)):
+                bad, r = _wan_bwd(c, affine, mod, mean, rstd, c["dy32"] if fp32_dy else c["dy"], dres)
+                assert not bad, (rows, xdt, affine, mod, bad)
+                wb = max(wb, r)
+    print(f"wan LN D {D}: restatement / bound forward {wf:.3f} backward {wb:.3f}")
+
+
+def _rms(c, D, hd, tables, eps=1e-6, wrong_f=None, wrong_b=None):
+    cos, sin = (c["cos"], c["sin"]) if tables else (None, None)
+    ref, rs_ref = R.rms_rope_ref64(c["u"], c["w"], cos, sin, R.RMS_L, hd, eps)
+    tol, tol_rs = R.rms_rope_fwd_tol(c["u"], c["w"], cos, sin, R.RMS_L, hd, eps, ref)
+    got, rs = R.rms_rope_fwd_f32(c["u"], c["w"], cos, sin, R.RMS_L, hd, eps, wrong_f)
+    rs_ok, _ = R.rms_rope_fwd_f32(c["u"], c["w"], cos, sin, R.RMS_L, hd, eps)[1], None
+    bad_f = R.judge("rms fwd out", got, ref, tol) + R.judge("rms fwd rs", rs, rs_ref, tol_rs)
+    gref = R.rms_rope_bwd_ref64(c["dout"], c["u"], rs_ok, c["w"], cos, sin, R.RMS_L, hd)
+    gtol = R.rms_rope_bwd_tol(c["dout"], c["u"], rs_ok, c["w"], cos, sin, R.RMS_L, hd, gref)
+    ggot = R.rms_rope_bwd_f32(c["dout"], c["u"], rs_ok, c["w"], cos, sin, R.RMS_L, hd, wrong_b)
+    return bad_f, R.judge("rms bwd du", ggot, gref, gtol), (_ratio(got, ref, tol), _ratio(rs, rs_ref, tol_rs), _ratio(ggot, gref, gtol))
+
+
+@pytest.mark.parametrize("D,hd", R.RMS_SHAPES)
+@pytest.mark.parametrize("tables", [True, False])
+def test_rms_rope_restatements_inside_bounds(tables, D, hd):
+    bad_f, bad_b, r = _rms(R.rms_case(D, hd), D, hd, tables)
+    print(f"rms_rope D {D} head_dim {hd} tables {tables}: restatement / bound out {r[0]:.3f} rstd {r[1]:.3f} du {r[2]:.3f}")
+    assert not bad_f and not bad_b, (bad_f, bad_b)
+
+
+@pytest.mark.parametrize("rows,D", [(5, 264), (9, 4096)])
+def test_wan_gate_restatement_inside_bound_and_neighbour_gid_rejected(rows, D):
+    c = R.wan_ln_case(rows, D)
+    ref, tol = R.wan_gate_ref64(c["x"], c["y"], c["gid"], c["tab"][:, 2])
+    assert not R.judge("gate", R.wan_gate_f32(c["x"], c["y"], c["gid"], c["tab"][:, 2]), ref, tol)
+    assert R.judge("gate", R.wan_gate_f32(c["x"], c["y"], c["gid"], c["tab"][:, 2], wrong="gid_neighbour"), ref, tol)
+
+
+# the widths at which the variant differs from the kernel: "div_nv" only where the last chunk is partly filled
+@pytest.mark.parametrize("wrong,D", [("mask8", 8), ("mask8", 520), ("mask8", 3080), ("mask8", 4096), ("div_nv", 8), ("div_nv", 520), ("div_nv", 1288),
+                                     ("div_nv", 3080), ("div_nv", 4088), ("text_first_video", 512), ("text_first_video", 4088)])
+def test_judge_rejects_wrong_cog_ln_forward(wrong, D):
+    """the last valid group of eight columns outside the sums; division by 512 NV; the text range's modulation on the first video row"""
+    B, S, Lt = R.COG_LAYOUTS[0]
+    c = R.cog_case(B, S, Lt, D)
+    assert not _cog_fwd(c, B, S, Lt, True, True)[0]
+    bad = _cog_fwd(c, B, S, Lt, True, True, wrong=wrong)[0]
+    print(*bad[:3], sep="\n")
+    assert bad
+
+
+@pytest.mark.parametrize("wrong,D", [("no_c1", 8), ("no_c1", 520), ("no_c1", 4096), ("mask8", 520), ("mask8", 4096), ("div_nv", 520), ("div_nv", 4088)])
+def test_judge_rejects_wrong_cog_ln_backward(wrong, D):
+    """c1 dropped; the last group of eight outside c1 and c2; division by 512 NV"""
+    B, S, Lt = R.COG_LAYOUTS[0]
+    c = R.cog_case(B, S, Lt, D)
+    _, _, xn, mean, rstd = _cog_fwd(c, B, S, Lt, True, True)
+    for dres in (c["dres"], None):
+        assert not _cog_bwd(c, B, S, Lt, True, xn, mean, rstd, dres)[0]
+        bad = _cog_bwd(c, B, S, Lt, True, xn, mean, rstd, dres, wrong=wrong)[0]
+        print(*bad[:2], sep="\n")
+        assert bad
+
+
+@pytest.mark.parametrize("wrong,D", [("mask8", 264), ("mask8", 4096), ("div_nv", 264), ("div_nv", 4088), ("gid_neighbour", 8), ("gid_neighbour", 3072)])
+def test_judge_rejects_wrong_wan_ln_forward(wrong, D):
+    for xdt in (torch.float32, torch.bfloat16):
+        c = R.wan_ln_case(9, D, xdt)
+        assert not _wan_fwd(c, True, True, 0, True)[0]
+        bad = _wan_fwd(c, True, True, 0, True, wrong=wrong)[0]
+        print(*bad[:2], sep="\n")
+        assert bad
+
+
+@pytest.mark.parametrize("wrong,D", [("scale_no1p", 8), ("scale_no1p", 4088), ("no_c1", 264), ("no_c1", 4096), ("mask8", 520), ("gid_neighbour", 264)])
+def test_judge_rejects_wrong_wan_ln_backward(wrong, D):
+    """scale where 1 + scale belongs; c1 dropped; the last group outside the sums; a neighbour's group"""
+    c = R.wan_ln_case(9, D)
+    _, _, mean, rstd = _wan_fwd(c, True, True, 0, True)
+    for dres in (c["dres"], None):
+        assert not _wan_bwd(c, True, True, mean, rstd, c["dy"], dres)[0]
+        assert _wan_bwd(c, True, True, mean, rstd, c["dy"], dres, wrong=wrong)[0]
+
+
+def test_bf16_output_bound_cannot_see_a_missing_xhat_rounding():
+    """why the device test also compares round_xhat bit for bit with bf16((x - mean) rstd) from the device's own mean and rstd: without the intermediate rounding the
+    output stays inside the bound (the reference is the unrounded expression and the rounding's half ulp is part of the tolerance)"""
+    c = R.wan_ln_case(9, 520)
+    assert not _wan_fwd(c, True, True, 1, True, wrong="no_round")[0]
+    a = (c["x"], None, None, None, None, None, 1e-6)
+    with_r, without = R.wan_ln_fwd_f32(*a, 1)[0], R.wan_ln_fwd_f32(*a, 1, wrong="no_round")[0]
+    assert np.array_equal(with_r, without)                 # and with nothing behind it the second rounding changes nothing: the bit-exact case has no affine ...
+    mean, rstd = R.wan_ln_fwd_f32(*a, 0)[1:]
+    assert np.array_equal(with_r, R.bf16_round((R.f32(c["x"]) - mean[:, None]) * rstd[:, None]))       # ... and is the two-operation fp32 expression
+
+
+@pytest.mark.parametrize("wrong,D,hd", [("mask8", 264, 24), ("mask8", 4096, 128), ("div_nv", 264, 8), ("div_nv", 520, 40), ("per_head", 264, 24),
+                                        ("per_head", 3072, 128), ("row_no_mod", 264, 8), ("row_no_mod", 4096, 128)])
+def test_judge_rejects_wrong_rms_rope_forward(wrong, D, hd):
+    """the last group outside the sum of squares; division by 512 NV; the mean of squares per head; table row `row` where `row % L` belongs"""
+    c = R.rms_case(D, hd)
+    assert not _rms(c, D, hd, True)[0]
+    bad = _rms(c, D, hd, True, wrong_f=wrong)[0]
+    print(*bad[:2], sep="\n")
+    assert bad
+
+
+@pytest.mark.parametrize("wrong,D,hd", [("no_transpose", 264, 24), ("no_transpose", 4096, 128), ("row_no_mod", 520, 40), ("mask8", 264, 8), ("div_nv", 520, 40)])
+def test_judge_rejects_wrong_rms_rope_backward(wrong, D, hd):
+    """the forward's rotation applied to the gradient; `row` for `row % L`; the last group outside mean(dn n); division by 512 NV"""
+    c = R.rms_case(D, hd)
+    assert not _rms(c, D, hd, True)[1]
+    assert _rms(c, D, hd, True, wrong_b=wrong)[1]
+
+
+def test_ln_bounds_are_not_the_old_absolute_ones():
+    """tests/test_gpu_kernels.py::test_ln_modulate_fwd_bwd allowed 0.03 absolute on the output and 2 % of the largest gradient + 1e-3: on that test's own inputs
+    (D = 3072, B = 2, S = 37, text_len = 5, randn) a LayerNorm whose sums leave out the last eight columns passes the first, and a backward without c1 passes the second.
+    Per element both are rejected."""
+    D, B, S, Lt = 3072, 2, 37, 5
+    g = torch.Generator().manual_seed(D)
+    x = torch.randn(B, S, D, generator=g).to(torch.bfloat16)
+    w, b = 1 + 0.1 * torch.randn(D, generator=g), 0.1 * torch.randn(D, generator=g)
+    mod = 0.3 * torch.randn(B, 4, D, generator=g)
+    mod[:, 1] += 1
+    mod[:, 3] += 1
+    dy = torch.randn(B, S, D, generator=g).to(torch.bfloat16)
+    s1p, shift = R.cog_rows(mod[:, 1], mod[:, 3], B, S, Lt), R.cog_rows(mod[:, 0], mod[:, 2], B, S, Lt)
+    ref = R.cog_ln_fwd_ref64(x, w, b, s1p, shift, 1e-5)
+    tols = R.cog_ln_fwd_tol(x, w, b, s1p, shift, 1e-5, ref[0])
+    ok, bad = R.cog_ln_fwd_f32(x, w, b, s1p, shift, 1e-5), R.cog_ln_fwd_f32(x, w, b, s1p, shift, 1e-5, wrong="mask8")
+    assert float((torch.as_tensor(bad[0]).double() - ref[0]).abs().max()) < 0.03                   # the old assertion accepts it
+    assert not R.judge("n", ok[0], ref[0], tols[0]) and R.judge("n", bad[0], ref[0], tols[0]) and R.judge("mean", bad[1], ref[1], tols[1])
+    gg = dy.double() * w.double() * s1p.double()
+    gref = R.ln_bwd_ref64(gg, x, ok[1], ok[2])
+    gtol = R.bf16_tol(gref, R.ln_bwd_rest(gg, x, ok[1], ok[2], 2.0))
+    gok, gbad = R.cog_ln_bwd_f32(dy, x, ok[1], ok[2], w, s1p), R.cog_ln_bwd_f32(dy, x, ok[1], ok[2], w, s1p, wrong="no_c1")
+    assert float((torch.as_tensor(gbad).double() - gref).abs().max()) < 0.02 * float(gref.abs().max()) + 1e-3       # the old assertion accepts it
+    assert not R.judge("dx", gok, gref, gtol) and len(R.judge("dx", gbad, gref, gtol)) > 1
+
+
+def test_row_sum_constants_count_the_kernel_loops():
+    assert [R.nv_of(D) for D in R.ROW_WIDTHS] == [1, 1, 2, 2, 3, 4, 5, 6, 7, 8, 8]
+    assert R.c_sum(64 * 8) == 7 + 6 and R.c_mean(4096) == 70 and R.c_rstd(512) == 11 and R.c_rms(4096) == 38

@@ -3,6 +3,11 @@
 
     python tools/gen_w1_asm.py            # rewrites videogpa_amd/csrc/w1_*_loop.inc
     python tools/gen_w1_asm.py --check    # exit 1 if a committed .inc differs from what this script generates
+    W1_KNOBS=lead=4,pad4=1 W1_ABLATE=nolds python tools/gen_w1_asm.py     # a re-tuned / ablated variant: names in KNOBS, ABLATIONS below
+
+Layout of this file: Emitter and schedule() place one straight-line stretch; W1Loop owns the ring protocol every loop shares (prologue, the
+phases of wait / barrier / LDS-DMA refill / body / count-and-branch, epilogue) and the half-step; each loop class below it states only what is
+its own -- register map, fragment addressing, MFMA list, VALU units, constants, clobber ranges.
 
 Why a generator: with one wave per SIMD nothing but the wave's own instruction order overlaps the matrix pipe with the
 VALU / LDS work, and hipcc's register allocator answers a 300+-register software pipeline with hundreds of tuple copies per
@@ -26,9 +31,36 @@ import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MFMA = "v_mfma_f32_32x32x16_bf16"
-# Timing-only ablations for tools/w1_variants.sh (results are WRONG with any of them): W1_ABLATE=novalu,nolds,nosync,nomfma
-ABLATE = set(x for x in os.environ.get("W1_ABLATE", "").split(",") if x)
-KNOB = {k: int(v) for k, v in (kv.split("=") for kv in os.environ.get("W1_KNOBS", "").split(",") if kv)}
+MFMA8 = "v_mfma_scale_f32_32x32x64_f8f6f4"
+# W1_KNOBS=name=int,...: re-tuned variants whose results stay right (tools/fwd_knob_ab.sh, x2_lead_sweep.sh, w1_variants.sh).  name: (product value, meaning)
+KNOBS = {"lead": (6, "the six bf16 attention loops request an LDS fragment this many MFMAs ahead of its first reader"),
+         "lead8": (6, "the same for the e4m3 forward"),
+         "mfsum": (1, "head_dim-64 forward: row sums on the matrix pipe (1) or as v_add_f32 (0); w1_fwd_knobs.inc tells the C++ shell"),
+         "pksum": (0, "head_dim-64 forward with mfsum=0: the two row-sum adds of a score pair as one v_pk_add_f32"),
+         "pad4": (0, "this many s_nop 0 in front of every loop label: shifts the loop body by 4 bytes per unit")}
+# W1_ABLATE=name,...: timing-only ablations for tools/w1_variants.sh (results are WRONG with any of them)
+ABLATIONS = {"novalu": "the attention loops lose their VALU stage (exp / mul / pack)",
+             "nolds": "no LDS fragment read is issued or waited for",
+             "nosync": "the attention loops lose their per-tile s_barrier",
+             "nomfma": "the attention loops lose their MFMAs"}
+
+
+def env_items(var, declared, valued):
+    """the comma-separated items of environment variable `var` (name=int if `valued`, else bare names); an undeclared name ends the script
+    here, before anything is generated or written (a mistyped knob would otherwise build the product loop and an A/B of it would read "flat")"""
+    items = [x for x in os.environ.get(var, "").split(",") if x]
+    def ok(x):
+        name, _, value = x.partition("=")
+        return (name in declared and value.lstrip("-").isdigit()) if valued else x in declared
+    bad = [x for x in items if not ok(x)]
+    if bad:
+        sys.exit(f"gen_w1_asm.py: {var} names {', '.join(bad)}; declared: {', '.join(declared)}" + (" (as name=integer)" if valued else ""))
+    return items
+
+
+ABLATE = set(env_items("W1_ABLATE", ABLATIONS, False))
+KNOB = {k: default for k, (default, _) in KNOBS.items()}
+KNOB.update((k, int(v)) for k, v in (kv.split("=") for kv in env_items("W1_KNOBS", KNOBS, True)))
 
 
 def vr(lo, n=1):
@@ -47,12 +79,6 @@ class Emitter:
         self.lgkm = []          # tags of outstanding LDS reads, oldest first
 
     def raw(self, text):
-        if KNOB.get("noexp") and text.startswith("v_exp_f32"):        # timing experiment: a plain VALU op in the place of every exp
-            text = text.replace("v_exp_f32", "v_mov_b32")
-        if KNOB.get("nomul") and (text.startswith("v_mul_f32") or text.startswith("v_add_f32")):
-            return
-        if KNOB.get("nocvt") and text.startswith("v_cvt_pk"):
-            return
         self.lines.append(text)
 
     def ds(self, text, tag):
@@ -113,7 +139,6 @@ def schedule(em, mfmas, frag_issue, frag_need, valu, lead, pre_issued=(), post_i
     per_gap = [0] * n
     # water-fill the VALU list over the gaps
     left = len(valu)
-    level = max(weights) if weights else 0
     target = -(-total // n)
     for g in range(n):
         room = max(target - weights[g], 0)
@@ -157,15 +182,162 @@ def schedule(em, mfmas, frag_issue, frag_need, valu, lead, pre_issued=(), post_i
         for _ in range(per_gap[i]):
             em.raw(valu[vk])
             vk += 1
-        for _ in range(KNOB.get("pad", 0)):      # timing experiment: idle issue slots in every MFMA gap
-            em.raw("s_nop 0")
-        if KNOB.get("nop7"):
-            em.raw("s_nop 7")
     assert vk == len(valu), (vk, len(valu))
 
 
+# ------------------------------------------------------------------------------------------------------- what every loop shares
+SAVE_M0, CNT, KREM, TMP = "%0", "%1", "%2", "%3"          # scalar operands of the asm statement: saved M0, tile counter; keys left, scratch (masked loops)
+KV = (("%[rk]", "%[kstep]"), ("%[rv]", "%[vstep]"))       # (buffer resource, per-tile source step) of the X and Y operand tiles of a ring slot
+QDO = (("%[rq]", "%[qstep]"), ("%[rdo]", "%[dstep]"))
+
+
+def vmov(em, regs, src):
+    for r in regs:
+        em.raw(f"v_mov_b32 v{r}, {src}")
+
+
+def dma_fill(voff, pieces, wbase="%[wbase]", stats=None):
+    """schedule()'s `fill_first` for one tile refill: per piece k = (resource, source step, LDS byte offset) the M0 write and, one gap later, the 1 KiB
+    LDS-DMA load through source offset v[voff + k] with that offset's advance; `stats` = LDS byte offset of the dK/dV loops' extra statistics dword."""
+    fill = []
+    for k, (rs, step, off) in enumerate(pieces):
+        fill.append([f"s_add_u32 m0, {wbase}, {off}"])
+        fill.append([f"buffer_load_dwordx4 v{voff + k}, {rs}, 0 offen lds", f"v_add_u32 v{voff + k}, {step}, v{voff + k}"])
+    if stats is not None:
+        v = voff + len(pieces)
+        fill.append([f"s_add_u32 m0, %[sbase], {stats}"])
+        fill.append([f"buffer_load_dword v{v}, %[rst], 0 offen lds", f"v_add_u32 v{v}, 256, v{v}"])
+    return fill
+
+
+class W1Loop:
+    """The pipeline skeleton: generate() is the whole ring protocol, half_step() one straight-line stretch of it.  A loop class sets the constants
+    below and provides issue_frag(), mfmas(), valu_ops() and init_regs(); GemmLoop (3 stages, its own k-step interleave) replaces phase()."""
+
+    LABEL = None              # label stem; NAME = the file stem (w1_NAME_loop.inc, w1_NAME_clobbers.inc); CLOBBER_V / CLOBBER_A = clobbered v / a ranges
+    STAGES = 4                # ring slots = unrolled phases of the loop body
+    SLOT = 16384              # bytes of a ring slot: X tile | Y tile, each brought as SLOT / 8192 pieces of 1 KiB per wave
+    AHEAD = 2                 # LDS-DMA refills the slot of tile i + AHEAD in phase i
+    VMCNT = None              # LDS-DMA loads that may still fly at the top of a phase: those of the tiles after this one
+    NACC = None               # a[0:NACC-1] start as 0
+    OPERANDS = KV
+    STATS = False             # a statistics dword rides along with every tile (LDS 1024 bytes per slot behind %[sbase])
+    MASKED = False            # keys past the end are masked: KREM counts them down, mask_lines() in front of each half-step
+    TIMED = False             # s_memtime stamps around the loop (the -DW1_CLOCKS build reads them)
+    NOSYNC = True             # W1_ABLATE=nosync reaches this loop
+    FW = 4                    # registers per streamed fragment; fragment f lives at FR + FW (f % NFR)
+    PREFETCH_SLOT = 3         # ring slot the first stretch's C fragments come from: tile "-1", zero-filled by the caller (None: nothing prefetched)
+    EXTRA_NEED = {}           # non-fragment LDS reads of a half-step: tag -> index of the first MFMA that needs them
+    LEAD = KNOB["lead"]       # fragment reads are issued this many MFMAs ahead of their first use
+    T0 = HI = NINF = NEGM = None      # masked loops: first srcC tuple, lane-half key offset, -inf, -M[q_j]
+    MASK_ROW = [(r & 3) + 8 * (r >> 2) for r in range(16)]      # key (minus HI's lane-half share) that score register r of a 32-key block holds
+    MASK_TAIL = []
+
+    def frag_reg(self, f):
+        return self.FR + self.FW * (f % self.NFR)
+
+    def init_early(self, em):
+        pass
+
+    def init_regs(self, em):
+        pass
+
+    def init_srcc(self, em):
+        for j in range(2):                                        # srcC tuples = -M[q]
+            vmov(em, range(self.T0 + 16 * j, self.T0 + 16 * j + 16), f"v{self.NEGM + j}")
+
+    def issue_stats(self, em, f, slot, qb, tag):
+        """the "-lse" / "-delta" srcC tuples ("cs" -> v[CS:CS+15], "cd" -> v[CD:CD+15]) of the 32 rows of block qb, from the slot's statistics piece"""
+        for g in range(4):
+            off = slot * 1024 + 512 * qb + 256 * (g >> 1) + 32 * (g & 1) + (64 if f == "cd" else 0)
+            em.ds(f"ds_read_b128 {vr((self.CS if f == 'cs' else self.CD) + 4 * g, 4)}, v{self.SB} offset:{off}", tag)
+
+    def mask_lines(self, kb, ph):
+        """srcC tuples for a 32-key block kb with fewer than 32 valid keys left (skipped while 64 or more remain): key 32 kb + MASK_ROW[r] + v[HI] of
+        this lane's score register r counts only if it is below KREM"""
+        label = f"L_{self.LABEL}_m{2 * ph + kb}_%="
+        out = [f"s_cmp_ge_i32 {KREM}, 64", f"s_cbranch_scc1 {label}"]
+        for r in range(16):
+            out += [f"s_sub_i32 {TMP}, {KREM}, {32 * kb + self.MASK_ROW[r]}", f"v_cmp_lt_i32 vcc, v{self.HI}, {TMP}"]
+            out += [f"v_cndmask_b32 v{self.T0 + 16 * j + r}, v{self.NINF}, v{self.NEGM + j}, vcc" for j in range(2)]
+        return out + self.MASK_TAIL + [f"{label}:"]
+
+    def fill(self, ph):
+        slot = (ph + self.AHEAD) & 3
+        pieces = [(rs, step, slot * self.SLOT + o * (self.SLOT // 2) + 1024 * i)
+                  for o, (rs, step) in enumerate(self.OPERANDS) for i in range(self.SLOT // 8192)]
+        return dma_fill(self.VOFF, pieces, stats=slot * 1024 if self.STATS else None)
+
+    def half_step(self, em, slotA, kbA, slotC, kbC, pa, nxt, fill_first=(), raw_after=None):
+        """C reads its packed operand [pa] (tile slotC, block kbC); A writes the scores [pa] (tile slotA, block kbA); B works on [pa ^ 1].
+        nxt = (slotC, kbC) of the following stretch, whose first four fragments are requested in the last four gaps (their ring positions are free
+        by then) under the tag ("n", f); this stretch renames the ones prefetched for it to plain f."""
+        ms = self.mfmas(pa, pa)
+        need = {}
+        for idx, (_, f) in enumerate(ms):           # first MFMA that reads each fragment
+            if f is not None and f not in need:
+                need[f] = idx
+        need.update(self.EXTRA_NEED)
+        post = [lambda f=f: self.issue_frag(em, f, 0, 0, nxt[0], nxt[1], tag=("n", f)) for f in range(4)]
+        em.retag({("n", f): f for f in range(4)})
+        valu = [] if "novalu" in ABLATE else self.valu_ops(pa ^ 1)
+        schedule(em, ms, lambda f: self.issue_frag(em, f, slotA, kbA, slotC, kbC), need, valu, self.LEAD,
+                 pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill_first, raw_after=raw_after)
+
+    def phase(self, em, ph):
+        """tile ph's two 32-row half-steps; the refill of tile ph + 2's slot is issued inside the first gaps"""
+        sp = (ph - 1) & 3
+        for kb, nxt in ((0, (sp, 1)), (1, (ph, 0))):
+            if self.MASKED:
+                for ln in self.mask_lines(kb, ph):
+                    em.raw(ln)
+            self.half_step(em, ph, kb, sp, kb, kb, nxt=nxt, fill_first=self.fill(ph) if kb == 0 else ())
+
+    def generate(self):
+        em = Emitter()
+        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
+        self.init_early(em)
+        em.raw(f"s_mov_b32 {CNT}, %[niter]")
+        if self.MASKED:
+            em.raw(f"s_mov_b32 {KREM}, %[krem]")
+        for i in range(self.NACC):
+            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
+        self.init_regs(em)
+        if self.PREFETCH_SLOT is not None:
+            for f in range(4):
+                self.issue_frag(em, f, 0, 0, self.PREFETCH_SLOT, 0, tag=("n", f))
+        if self.TIMED:
+            em.raw("s_memtime %[c0]")
+        for _ in range(KNOB["pad4"]):      # placement experiment (MI355X_MICROARCH.md "code-placement sensitivity")
+            em.raw("s_nop 0")
+        em.raw(f"L_{self.LABEL}_loop_%=:")
+        for ph in range(self.STAGES):
+            # tile i (ring slot ph) must have landed for every wave.  Every read of the slot about to be refilled has been waited for by its
+            # consumer MFMA, so after the barrier LDS-DMA may refill it (issued inside the phase's first gaps).
+            em.raw(f"s_waitcnt vmcnt({self.VMCNT})")
+            if not (self.NOSYNC and "nosync" in ABLATE):
+                em.raw("s_barrier")
+            self.phase(em, ph)
+            if self.MASKED:
+                em.raw(f"s_sub_i32 {KREM}, {KREM}, 64")
+            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
+            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
+            if ph < self.STAGES - 1:
+                em.raw(f"s_cbranch_scc1 L_{self.LABEL}_done_%=")
+            else:
+                em.raw(f"s_cbranch_scc0 L_{self.LABEL}_loop_%=")
+        em.raw(f"L_{self.LABEL}_done_%=:")
+        if self.TIMED:
+            em.raw("s_memtime %[c1]")
+        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
+        em.raw("s_nop 7")
+        em.raw("s_nop 7")            # last MFMA results -> the compiler's v_accvgpr_read
+        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
+        return em.text() + "\n"
+
+
 # ---------------------------------------------------------------------------------------------------------------- dQ loop
-class DqLoop:
+class DqLoop(W1Loop):
     """dQ:  per 32-key half-tile g (tile = g >> 1 in the K|V ring, key block kb = g & 1), two 32-row q-blocks j per wave:
          A(g): S[g&1][j] = -lse + K_g Q_j^T, DP[g&1][j] = -delta + V_g dO_j^T          16 MFMAs (-lse / -delta enter as srcC)
          B(g): D[g&1][j] = bf16(exp2(S) * DP)                                             80 VALU
@@ -181,12 +353,13 @@ class DqLoop:
                          v[160:223] srcC of the first k-step: -lse2[q] x16 (j = 0,1), -delta[q] x16 (j = 0,1)
                          v[224:231] lane LDS offsets   v[232:235] LDS-DMA source offsets (K0 K1 V0 V1; advanced per tile)"""
 
+    NAME, LABEL, VMCNT, NACC = "dq", "w1dq", 4, 64
+    CLOBBER_V, CLOBBER_A = [(0, 159)], [(128, 151)]
     LA = 224
     VOFF = 232
     CI = 160
     FR = 128       # AGPR
     NFR = 6
-    LEAD = KNOB.get("lead", 6)       # fragment reads are issued this many MFMAs ahead of their first use
 
     def S(self, p, j):
         return p * 64 + j * 16
@@ -199,15 +372,8 @@ class DqLoop:
 
     # fragments of one half-step: 0..3 K transposed (cc, db) = (f >> 1, f & 1) of the PREVIOUS tile; 4..7 K rows ks; 8..11 V rows ks.
     # ring position advances continuously (12 per half-step, ring of 6: every half-step starts at position 0)
-    def frag_reg(self, f):
-        return (160 if KNOB.get("ringv") else self.FR) + 4 * (f % self.NFR)
-
-    def fr(self, f):
-        return (vr if KNOB.get("ringv") else ar)(self.frag_reg(f), 4)
-
     def issue_frag(self, em, f, slotA, kbA, slotC, kbC, tag=None):
         r = self.frag_reg(f)
-        ar = vr if KNOB.get("ringv") else globals()["ar"]
         tag = f if tag is None else tag
         if f < 4:
             cc, db = f >> 1, f & 1
@@ -227,40 +393,27 @@ class DqLoop:
                 c = i >> 1
                 cc, db = c >> 1, c & 1
                 d = ar(32 * j + 16 * db, 16)
-                out.append((f"{MFMA} {d}, {self.fr(c)}, {vr(self.D(pc, j, cc), 4)}, {d}", c))
+                out.append((f"{MFMA} {d}, {ar(self.frag_reg(c), 4)}, {vr(self.D(pc, j, cc), 4)}, {d}", c))
             elif i < 16:
                 ks = (i - 8) >> 1
                 d = vr(self.S(pa, j), 16)
-                c = (vr(self.CI + 16 * j, 16) if KNOB.get("cinit", 1) in (1, 2) else "0") if ks == 0 else d
-                out.append((f"{MFMA} {d}, {self.fr(4 + ks)}, {ar(64 + 16 * j + 4 * ks, 4)}, {c}", 4 + ks))
+                c = vr(self.CI + 16 * j, 16) if ks == 0 else d
+                out.append((f"{MFMA} {d}, {ar(self.frag_reg(4 + ks), 4)}, {ar(64 + 16 * j + 4 * ks, 4)}, {c}", 4 + ks))
             else:
                 ks = (i - 16) >> 1
                 d = vr(self.DP(pa, j), 16)
-                c = (vr(self.CI + 32 + 16 * j, 16) if KNOB.get("cinit", 1) in (1, 3) else "0") if ks == 0 else d
-                out.append((f"{MFMA} {d}, {self.fr(8 + ks)}, {ar(96 + 16 * j + 4 * ks, 4)}, {c}", 8 + ks))
+                c = vr(self.CI + 32 + 16 * j, 16) if ks == 0 else d
+                out.append((f"{MFMA} {d}, {ar(self.frag_reg(8 + ks), 4)}, {ar(96 + 16 * j + 4 * ks, 4)}, {c}", 8 + ks))
         return out
 
     def valu_ops(self, pb):
         """B stage on S[pb], DP[pb] -> D[pb]: 16 units of (exp, exp, mul, mul, cvt), software-pipelined by one unit"""
-        if "novalu" in ABLATE:
-            return []
-
         def unit(u):
             j, p = u >> 3, u & 7
             s0, d0 = self.S(pb, j) + 2 * p, self.DP(pb, j) + 2 * p
             w = self.D(pb, j, p >> 2) + (p & 3)
-            if KNOB.get("pkmul"):
-                return ([f"v_exp_f32 v{s0}, v{s0}", f"v_exp_f32 v{s0 + 1}, v{s0 + 1}"],
-                        [f"v_pk_mul_f32 {vr(s0, 2)}, {vr(d0, 2)}, {vr(s0, 2)}", None, f"v_cvt_pk_bf16_f32 v{w}, v{s0}, v{s0 + 1}"])
             return ([f"v_exp_f32 v{s0}, v{s0}", f"v_exp_f32 v{s0 + 1}, v{s0 + 1}"],
                     [f"v_mul_f32 v{s0}, v{d0}, v{s0}", f"v_mul_f32 v{s0 + 1}, v{d0 + 1}, v{s0 + 1}", f"v_cvt_pk_bf16_f32 v{w}, v{s0}, v{s0 + 1}"])
-        if KNOB.get("vorder", 1) == 0:
-            ops = list(unit(0)[0])
-            for u in range(16):
-                if u + 1 < 16:
-                    ops += unit(u + 1)[0]
-                ops += unit(u)[1]
-            return ops
         # no instruction directly follows one it depends on: step t = mul(t).a, exp(t+1).a, mul(t).b, exp(t+1).b, cvt(t-1)
         ops = list(unit(0)[0])
         for t in range(17):
@@ -270,63 +423,12 @@ class DqLoop:
             ops += [o for o in (m[0], x[0], m[1], x[1], c) if o is not None]
         return ops
 
-    def half_step(self, em, slotA, kbA, slotC, kbC, pa, nxt, fill_first=()):
-        """C reads D[pa] (tile slotC, kbC); A writes S/DP[pa] (tile slotA, kbA); B reads S/DP[pa ^ 1], writes D[pa ^ 1].
-        nxt = (slotC, kbC) of the following half-step, whose transposed fragments are requested in the last four gaps (their ring positions are free by then)."""
-        need = {f: 2 * f for f in range(12)}
-        post = [lambda f=f: self.issue_frag(em, f, 0, 0, nxt[0], nxt[1], tag=("n", f)) for f in range(4)]
-        # the prefetched fragments carry the tag ("n", f): rename them to plain f for this stretch
-        em.retag({("n", f): f for f in range(4)})
-        schedule(em, self.mfmas(pa, pa), lambda f: self.issue_frag(em, f, slotA, kbA, slotC, kbC), need, self.valu_ops(pa ^ 1), self.LEAD,
-                 pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill_first)
-
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT = "%0", "%1"
-        RK, RV, KSTEP, VSTEP, WBASE, NITER = "%[rk]", "%[rv]", "%[kstep]", "%[vstep]", "%[wbase]", "%[niter]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        for i in range(64):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
-        for r in list(range(64, 128)) + list(range(128, 144)):      # S/DP[1], D[0]
-            em.raw(f"v_mov_b32 v{r}, 0")
-        # the first half-step's transposed fragments: tile "-1" = ring slot 3 (zero-filled by the caller), key block 0
-        for f in range(4):
-            self.issue_frag(em, f, 0, 0, 3, 0, tag=("n", f))
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1dq_loop_%=:")
-        for ph in range(4):
-            # tile i (ring slot ph) must have landed for every wave.  Every read of tile i-2's slot has been waited for by its
-            # consumer MFMA, so after the barrier LDS-DMA may refill that slot with tile i+2 (issued inside the first gaps).
-            em.raw("s_waitcnt vmcnt(4)")
-            if "nosync" not in ABLATE:
-                em.raw("s_barrier")
-            dst = ((ph + 2) & 3) * 16384
-            fill = []
-            for k, (rs, extra) in enumerate([(RK, 0), (RK, 1024), (RV, 8192), (RV, 9216)]):
-                fill.append([f"s_add_u32 m0, {WBASE}, {dst + extra}"])
-                fill.append([f"buffer_load_dwordx4 v{self.VOFF + k}, {rs}, 0 offen lds",
-                             f"v_add_u32 v{self.VOFF + k}, {KSTEP if k < 2 else VSTEP}, v{self.VOFF + k}"])
-            sp = (ph - 1) & 3
-            self.half_step(em, ph, 0, sp, 0, 0, nxt=(sp, 1), fill_first=fill)
-            self.half_step(em, ph, 1, sp, 1, 1, nxt=(ph, 0))
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if ph < 3:
-                em.raw("s_cbranch_scc1 L_w1dq_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1dq_loop_%=")
-        em.raw("L_w1dq_done_%=:")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")            # last MFMA results -> the compiler's v_accvgpr_read
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+    def init_regs(self, em):
+        vmov(em, [*range(64, 128), *range(128, 144)], 0)      # S/DP[1], D[0]
 
 
 # --------------------------------------------------------------------------------------------------------------- dK/dV loop
-class DkvLoop:
+class DkvLoop(W1Loop):
     """dK, dV:  a wave owns two 32-key blocks kb (K, V fragments and the dK^T, dV^T accumulators stay in AGPRs for the whole
        sweep) and streams 64-row Q|dO tiles; per 32-row half-tile g (tile = g >> 1, row block qb = g & 1):
          A(g): S[g&1][kb] = -lse[q] + Q_g K_kb^T,  DP[g&1][kb] = -delta[q] + dO_g V_kb^T   16 MFMAs; q runs over the accumulator
@@ -343,12 +445,15 @@ class DkvLoop:
        LDS            ring slot s at 16384 s: Q tile | dO tile;  statistics of slot s at 65536 + 1024 s: wave w's 256-byte piece holds
                       -lse2 of rows 16w..16w+15 at +0 and -delta of the same rows at +64"""
 
+    NAME, LABEL, VMCNT, NACC = "dkv", "w1dkv", 5, 128
+    CLOBBER_V, CLOBBER_A = [(0, 223)], [(192, 223)]
+    OPERANDS, STATS, EXTRA_NEED = QDO, True, {"cs": 16, "cd": 24}
     LA = 224
     VOFF = 232
     SB = 237
+    CS, CD = 192, 208
     FR = 192
     NFR = 8
-    LEAD = KNOB.get("lead", 6)
 
     def S(self, p, kb):
         return p * 64 + kb * 16
@@ -362,19 +467,12 @@ class DkvLoop:
     def DSK(self, p, kb, cc):
         return 128 + p * 32 + 16 + kb * 8 + cc * 4
 
-    def frag_reg(self, f):
-        return self.FR + 4 * (f % self.NFR)
-
     def issue_frag(self, em, f, slotA, qbA, slotC, qbC, tag=None):
         """f 0..7: transposed fragments of the PREVIOUS half (even: dO tile, odd: Q tile; (cc, db) = (f >> 2, (f >> 1) & 1));
         8..11: Q rows ks; 12..15: dO rows ks; "cs" / "cd": the srcC tuples (-lse / -delta of the 32 rows)"""
         tag = f if tag is None else tag
         if f == "cs" or f == "cd":
-            base = 192 if f == "cs" else 208
-            for g in range(4):
-                off = slotA * 1024 + 512 * qbA + 256 * (g >> 1) + 32 * (g & 1) + (64 if f == "cd" else 0)
-                em.ds(f"ds_read_b128 {vr(base + 4 * g, 4)}, v{self.SB} offset:{off}", tag)
-            return
+            return self.issue_stats(em, f, slotA, qbA, tag)
         r = self.frag_reg(f)
         if f < 8:
             c = f >> 1
@@ -405,19 +503,16 @@ class DkvLoop:
             elif i < 24:
                 ks = (i - 16) >> 1
                 d = vr(self.S(pa, kb), 16)
-                c = vr(192, 16) if ks == 0 else d
+                c = vr(self.CS, 16) if ks == 0 else d
                 out.append((f"{MFMA} {d}, {ar(self.frag_reg(8 + ks), 4)}, {ar(128 + 16 * kb + 4 * ks, 4)}, {c}", 8 + ks))
             else:
                 ks = (i - 24) >> 1
                 d = vr(self.DP(pa, kb), 16)
-                c = vr(208, 16) if ks == 0 else d
+                c = vr(self.CD, 16) if ks == 0 else d
                 out.append((f"{MFMA} {d}, {ar(self.frag_reg(12 + ks), 4)}, {ar(160 + 16 * kb + 4 * ks, 4)}, {c}", 12 + ks))
         return out
 
     def valu_ops(self, pb):
-        if "novalu" in ABLATE:
-            return []
-
         def unit(u):
             kb, p = u >> 3, u & 7
             s0, d0 = self.S(pb, kb) + 2 * p, self.DP(pb, kb) + 2 * p
@@ -433,61 +528,12 @@ class DkvLoop:
             ops += [o for o in (m[0], x[0], c[0], m[1], x[1], c[1]) if o is not None]
         return ops
 
-    def half_step(self, em, slotA, qbA, slotC, qbC, pa, nxt, fill_first=()):
-        need = {f: 2 * f for f in range(16)}
-        need["cs"] = 16
-        need["cd"] = 24
-        post = [lambda f=f: self.issue_frag(em, f, 0, 0, nxt[0], nxt[1], tag=("n", f)) for f in range(4)]
-        em.retag({("n", f): f for f in range(4)})
-        schedule(em, self.mfmas(pa, pa), lambda f: self.issue_frag(em, f, slotA, qbA, slotC, qbC), need, self.valu_ops(pa ^ 1), self.LEAD,
-                 pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill_first)
-
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT = "%0", "%1"
-        RQ, RDO, RST, QSTEP, DSTEP, WBASE, SBASE, NITER = "%[rq]", "%[rdo]", "%[rst]", "%[qstep]", "%[dstep]", "%[wbase]", "%[sbase]", "%[niter]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        for i in range(128):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
-        for r in list(range(64, 128)) + list(range(128, 160)):      # S/DP[1], PK/DSK[0]
-            em.raw(f"v_mov_b32 v{r}, 0")
-        for f in range(4):
-            self.issue_frag(em, f, 0, 0, 3, 0, tag=("n", f))
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1dkv_loop_%=:")
-        for ph in range(4):
-            em.raw("s_waitcnt vmcnt(5)")
-            if "nosync" not in ABLATE:
-                em.raw("s_barrier")
-            dst = ((ph + 2) & 3) * 16384
-            fill = []
-            for k, (rs, extra) in enumerate([(RQ, 0), (RQ, 1024), (RDO, 8192), (RDO, 9216)]):
-                fill.append([f"s_add_u32 m0, {WBASE}, {dst + extra}"])
-                fill.append([f"buffer_load_dwordx4 v{self.VOFF + k}, {rs}, 0 offen lds",
-                             f"v_add_u32 v{self.VOFF + k}, {QSTEP if k < 2 else DSTEP}, v{self.VOFF + k}"])
-            fill.append([f"s_add_u32 m0, {SBASE}, {((ph + 2) & 3) * 1024}"])
-            fill.append([f"buffer_load_dword v{self.VOFF + 4}, {RST}, 0 offen lds", f"v_add_u32 v{self.VOFF + 4}, 256, v{self.VOFF + 4}"])
-            sp = (ph - 1) & 3
-            self.half_step(em, ph, 0, sp, 0, 0, nxt=(sp, 1), fill_first=fill)
-            self.half_step(em, ph, 1, sp, 1, 1, nxt=(ph, 0))
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if ph < 3:
-                em.raw("s_cbranch_scc1 L_w1dkv_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1dkv_loop_%=")
-        em.raw("L_w1dkv_done_%=:")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+    def init_regs(self, em):
+        vmov(em, [*range(64, 128), *range(128, 160)], 0)      # S/DP[1], PK/DSK[0]
 
 
 # --------------------------------------------------------------------------------------------------------------- forward loop
-class FwdLoop:
+class FwdLoop(W1Loop):
     """forward:  a wave owns two 32-row q-blocks j (Q fragments and O^T accumulators in AGPRs) and streams 64-key K|V tiles; per
        32-key half-tile g:
          A(g): S[g&1][j] = -M[q] + K_g Q_j^T                     8 MFMAs; -M[q] is the srcC of the first k-step (loop-invariant tuple)
@@ -509,20 +555,20 @@ class FwdLoop:
                       v[0:63] S[p][j]   v[64:95] PK[p][j][cc]   v[96:127] srcC tuples (j = 0, 1)   v[128:135] l[j][0..3]   v136 v137 -M[q]
                       v[144:151] lane LDS offsets   v[152:155] LDS-DMA source offsets (K0 K1 V0 V1)   v156 4 * (lane >> 5)   v157 -inf"""
 
+    NAME, LABEL, VMCNT, NACC = "fwd", "w1fwd", 4, 64
+    CLOBBER_V, CLOBBER_A = [(0, 127), (157, 157)], [(96, 127)] + ([(128, 131)] if KNOB["mfsum"] else [])
+    MASKED, TIMED = True, True
+    T0, NEGM, HI, NINF = 96, 136, 156, 157
     LA = 144
     VOFF = 152
     FR = 96
     NFR = 8
-    LEAD = KNOB.get("lead", 6)
 
     def S(self, p, j):
         return p * 32 + j * 16
 
     def PK(self, p, j, cc):
         return 64 + p * 16 + j * 8 + cc * 4
-
-    def frag_reg(self, f):
-        return self.FR + 4 * (f % self.NFR)
 
     def issue_frag(self, em, f, slotA, kbA, slotC, kbC, tag=None):
         """f 0..3: transposed V fragments (cc, db) = (f >> 1, f & 1) of the PREVIOUS half; 4..7: K rows ks"""
@@ -545,7 +591,7 @@ class FwdLoop:
                 cc, db = c >> 1, c & 1
                 d = ar(32 * j + 16 * db, 16)
                 out.append((f"{MFMA} {d}, {ar(self.frag_reg(c), 4)}, {vr(self.PK(pc, j, cc), 4)}, {d}", c))
-                if KNOB.get("mfsum", 1) and db == 1 and j == 1:
+                if KNOB["mfsum"] and db == 1 and j == 1:
                     # W1_KNOBS=mfsum=1: l[q] += sum_k P[k][q] as a 16x16x32 product of a SPARSE selector against the same packed P registers the PV product
                     # reads.  Read as the B operand of v_mfma_f32_16x16x32_bf16, lane L of the 32x32x16 B fragment (column q = L % 32, keys 8 (L / 32) ..+7 of the
                     # 16-key chunk) is column n' = L % 16, k'-block L / 16: blocks 0, 2 hold q = n' (keys 0-7, 8-15), blocks 1, 3 hold q = n' + 16.  With
@@ -558,22 +604,19 @@ class FwdLoop:
             else:
                 ks = (i - 8) >> 1
                 d = vr(self.S(pa, j), 16)
-                c = vr(96 + 16 * j, 16) if ks == 0 else d
+                c = vr(self.T0 + 16 * j, 16) if ks == 0 else d
                 out.append((f"{MFMA} {d}, {ar(self.frag_reg(4 + ks), 4)}, {ar(64 + 16 * j + 4 * ks, 4)}, {c}", 4 + ks))
         return out
 
     def valu_ops(self, pb):
-        if "novalu" in ABLATE:
-            return []
-
         def unit(u):
             j, p = u >> 3, u & 7
             s0 = self.S(pb, j) + 2 * p
             w = self.PK(pb, j, p >> 2) + (p & 3)
             l0, l1 = 128 + 4 * j + ((2 * p) & 3), 128 + 4 * j + ((2 * p + 1) & 3)
-            if KNOB.get("mfsum", 1):      # row sums on the matrix pipe (see mfmas): no adds at all
+            if KNOB["mfsum"]:      # row sums on the matrix pipe (see mfmas): no adds at all
                 return ([f"v_exp_f32 v{s0}, v{s0}", f"v_exp_f32 v{s0 + 1}, v{s0 + 1}"], [None, None], f"v_cvt_pk_bf16_f32 v{w}, v{s0}, v{s0 + 1}")
-            if KNOB.get("pksum"):      # the two row-sum adds as ONE packed add (same fp32 additions in the same order: bit-identical results)
+            if KNOB["pksum"]:      # the two row-sum adds as ONE packed add (same fp32 additions in the same order: bit-identical results)
                 return ([f"v_exp_f32 v{s0}, v{s0}", f"v_exp_f32 v{s0 + 1}, v{s0 + 1}"],
                         [f"v_pk_add_f32 {vr(l0, 2)}, {vr(l0, 2)}, {vr(s0, 2)}", None],
                         f"v_cvt_pk_bf16_f32 v{w}, v{s0}, v{s0 + 1}")
@@ -587,88 +630,20 @@ class FwdLoop:
             ops += [o for o in (m[0], x[0], m[1], x[1], unit(t)[2]) if o is not None]
         return ops
 
-    def mask_block(self, em, kb, krem, tmp, label):
-        """srcC tuples for a half-tile with fewer than 32 valid keys left: row r of this lane is key 32 kb + rowconst(r) + 4 hi"""
-        em.raw(f"s_cmp_ge_i32 {krem}, 64")
-        em.raw(f"s_cbranch_scc1 {label}")
-        for r in range(16):
-            rowc = (r & 3) + 8 * (r >> 2) + 32 * kb
-            em.raw(f"s_sub_i32 {tmp}, {krem}, {rowc}")
-            em.raw(f"v_cmp_lt_i32 vcc, v156, {tmp}")
-            for j in range(2):
-                em.raw(f"v_cndmask_b32 v{96 + 16 * j + r}, v157, v{136 + j}, vcc")
-        em.raw(f"{label}:")
-
-    def half_step(self, em, slotA, kbA, slotC, kbC, pa, nxt, fill_first=()):
-        ms = self.mfmas(pa, pa)
-        need = {}
-        for idx, (_, f) in enumerate(ms):           # first MFMA that reads each fragment (f: 2 f without the mfsum products)
-            if f is not None and f not in need:
-                need[f] = idx
-        post = [lambda f=f: self.issue_frag(em, f, 0, 0, nxt[0], nxt[1], tag=("n", f)) for f in range(4)]
-        em.retag({("n", f): f for f in range(4)})
-        schedule(em, ms, lambda f: self.issue_frag(em, f, slotA, kbA, slotC, kbC), need, self.valu_ops(pa ^ 1), self.LEAD,
-                 pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill_first)
-
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT, KREM, TMP = "%0", "%1", "%2", "%3"
-        RK, RV, KSTEP, VSTEP, WBASE, NITER, KREM0 = "%[rk]", "%[rv]", "%[kstep]", "%[vstep]", "%[wbase]", "%[niter]", "%[krem]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        if KNOB.get("mfsum", 1):
+    def init_early(self, em):
+        if KNOB["mfsum"]:
             for i in range(4):                                     # the selector operand A' (v158: 0x3f803f80 in lanes 0, 17, 32, 49, else 0)
                 em.raw(f"v_accvgpr_write_b32 a{128 + i}, v158")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        em.raw(f"s_mov_b32 {KREM}, {KREM0}")
-        for i in range(64):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
-        em.raw("v_mov_b32 v157, 0xff800000")                      # -inf
-        for r in range(32, 64):                                   # S[1] = -inf: the pipeline's first B stage adds nothing
-            em.raw(f"v_mov_b32 v{r}, v157")
-        for r in list(range(64, 80)) + list(range(128, 136)):    # PK[0], l
-            em.raw(f"v_mov_b32 v{r}, 0")
-        for j in range(2):                                        # srcC tuples = -M[q]
-            for r in range(16):
-                em.raw(f"v_mov_b32 v{96 + 16 * j + r}, v{136 + j}")
-        for f in range(4):
-            self.issue_frag(em, f, 0, 0, 3, 0, tag=("n", f))
-        em.raw("s_memtime %[c0]")
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1fwd_loop_%=:")
-        for ph in range(4):
-            em.raw("s_waitcnt vmcnt(4)")
-            if "nosync" not in ABLATE:
-                em.raw("s_barrier")
-            dst = ((ph + 2) & 3) * 16384
-            fill = []
-            for k, (rs, extra) in enumerate([(RK, 0), (RK, 1024), (RV, 8192), (RV, 9216)]):
-                fill.append([f"s_add_u32 m0, {WBASE}, {dst + extra}"])
-                fill.append([f"buffer_load_dwordx4 v{self.VOFF + k}, {rs}, 0 offen lds",
-                             f"v_add_u32 v{self.VOFF + k}, {KSTEP if k < 2 else VSTEP}, v{self.VOFF + k}"])
-            sp = (ph - 1) & 3
-            self.mask_block(em, 0, KREM, TMP, f"L_w1fwd_m{2 * ph}_%=")
-            self.half_step(em, ph, 0, sp, 0, 0, nxt=(sp, 1), fill_first=fill)
-            self.mask_block(em, 1, KREM, TMP, f"L_w1fwd_m{2 * ph + 1}_%=")
-            self.half_step(em, ph, 1, sp, 1, 1, nxt=(ph, 0))
-            em.raw(f"s_sub_i32 {KREM}, {KREM}, 64")
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if ph < 3:
-                em.raw("s_cbranch_scc1 L_w1fwd_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1fwd_loop_%=")
-        em.raw("L_w1fwd_done_%=:")
-        em.raw("s_memtime %[c1]")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+
+    def init_regs(self, em):
+        em.raw(f"v_mov_b32 v{self.NINF}, 0xff800000")            # -inf
+        vmov(em, range(32, 64), f"v{self.NINF}")                  # S[1] = -inf: the pipeline's first B stage adds nothing
+        vmov(em, [*range(64, 80), *range(128, 136)], 0)           # PK[0], l
+        self.init_srcc(em)
 
 
 # ------------------------------------------------------------------------------------------------------- forward, head_dim 128
-class Fwd128Loop:
+class Fwd128Loop(W1Loop):
     """FwdLoop for head_dim 128 (csrc/attention_hd128.hip, the Wan2.2 shapes): same pipeline -- half-step(g) issues C(g-1) | A(g+1) | B(g)
        on 32-key half-tiles, two q-blocks per wave, row-bound shift, fp32 row sums -- with
          A(g): S[g&1][j] = -M[q] + K_g Q_j^T       16 MFMAs (8 k-steps x 2 q-blocks)
@@ -682,21 +657,20 @@ class Fwd128Loop:
                       v[144:175] lane LDS offsets [slot pair][K rows ks 0..7 | V transposed (db, second read) 0..7]
                       v[176:183] LDS-DMA source offsets (K x4, V x4)   v184 4 * (lane >> 5)   v185 -inf"""
 
+    NAME, LABEL, VMCNT, NACC, SLOT = "fwd128", "w1f128", 8, 128, 32768
+    CLOBBER_V, CLOBBER_A = [(0, 127), (185, 185)], [(192, 255)]
+    MASKED = True
+    T0, NEGM, HI, NINF = 96, 136, 184, 185
     LA = 144
     VOFF = 176
-    HI4 = 184
-    NINF = 185
     FR = 192
-    LEAD = KNOB.get("lead", 6)
+    NFR = 16
 
     def S(self, p, j):
         return p * 32 + j * 16
 
     def PK(self, p, j, cc):
         return 64 + p * 16 + j * 8 + cc * 4
-
-    def frag_reg(self, f):
-        return self.FR + 4 * f
 
     def issue_frag(self, em, f, slotA, kbA, slotC, kbC, tag=None):
         """f 0..7: transposed V fragments (cc, db) = (f >> 2, f & 3) of the PREVIOUS half; 8..15: K rows ks = f - 8"""
@@ -722,16 +696,13 @@ class Fwd128Loop:
         for ks in range(8):
             for j in range(2):
                 d = vr(self.S(pa, j), 16)
-                c = vr(96 + 16 * j, 16) if ks == 0 else d
+                c = vr(self.T0 + 16 * j, 16) if ks == 0 else d
                 out.append((f"{MFMA} {d}, {ar(self.frag_reg(8 + ks), 4)}, {ar(128 + 32 * j + 4 * ks, 4)}, {c}", 8 + ks))
         return out
 
     def valu_ops(self, pb):
         """as FwdLoop.valu_ops plus the softmax scale: S holds q.k - M / c (q arrives UNscaled here: the backward kernels of
         attention_hd128.hip read the same q), so one v_mul by c = scale * log2(e) (an SGPR) precedes each exp"""
-        if "novalu" in ABLATE:
-            return []
-
         def unit(u):
             j, p = u >> 3, u & 7
             s0 = self.S(pb, j) + 2 * p
@@ -747,83 +718,16 @@ class Fwd128Loop:
             ops += [o for o in (x[0], m[0], x[1], x[2], m[1], x[3], unit(t)[2]) if o is not None]
         return ops
 
-    def mask_block(self, em, kb, krem, tmp, label):
-        em.raw(f"s_cmp_ge_i32 {krem}, 64")
-        em.raw(f"s_cbranch_scc1 {label}")
-        for r in range(16):
-            rowc = (r & 3) + 8 * (r >> 2) + 32 * kb
-            em.raw(f"s_sub_i32 {tmp}, {krem}, {rowc}")
-            em.raw(f"v_cmp_lt_i32 vcc, v{self.HI4}, {tmp}")
-            for j in range(2):
-                em.raw(f"v_cndmask_b32 v{96 + 16 * j + r}, v{self.NINF}, v{136 + j}, vcc")
-        em.raw(f"{label}:")
-
-    def half_step(self, em, slotA, kbA, slotC, kbC, pa, nxt, fill_first=()):
-        need = {f: 2 * f for f in range(16)}
-        post = [lambda f=f: self.issue_frag(em, f, 0, 0, nxt[0], nxt[1], tag=("n", f)) for f in range(4)]
-        em.retag({("n", f): f for f in range(4)})
-        schedule(em, self.mfmas(pa, pa), lambda f: self.issue_frag(em, f, slotA, kbA, slotC, kbC), need, self.valu_ops(pa ^ 1), self.LEAD,
-                 pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill_first)
-
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT, KREM, TMP = "%0", "%1", "%2", "%3"
-        RK, RV, KSTEP, VSTEP, WBASE, NITER, KREM0 = "%[rk]", "%[rv]", "%[kstep]", "%[vstep]", "%[wbase]", "%[niter]", "%[krem]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        em.raw(f"s_mov_b32 {KREM}, {KREM0}")
-        for i in range(128):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
+    def init_regs(self, em):
         em.raw(f"v_mov_b32 v{self.NINF}, 0xff800000")
-        for r in range(32, 64):
-            em.raw(f"v_mov_b32 v{r}, v{self.NINF}")
-        for r in list(range(64, 80)) + list(range(128, 136)):
-            em.raw(f"v_mov_b32 v{r}, 0")
-        for j in range(2):
-            for r in range(16):
-                em.raw(f"v_mov_b32 v{96 + 16 * j + r}, v{136 + j}")
-        for f in range(4):
-            self.issue_frag(em, f, 0, 0, 3, 0, tag=("n", f))
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1f128_loop_%=:")
-        for ph in range(4):
-            em.raw("s_waitcnt vmcnt(8)")
-            if "nosync" not in ABLATE:
-                em.raw("s_barrier")
-            dst = ((ph + 2) & 3) * 32768
-            fill = []
-            for k in range(8):
-                isV = k >= 4
-                fill.append([f"s_add_u32 m0, {WBASE}, {dst + (16384 if isV else 0) + (k & 3) * 1024}"])
-                fill.append([f"buffer_load_dwordx4 v{self.VOFF + k}, {RV if isV else RK}, 0 offen lds",
-                             f"v_add_u32 v{self.VOFF + k}, {VSTEP if isV else KSTEP}, v{self.VOFF + k}"])
-            sp = (ph - 1) & 3
-            self.mask_block(em, 0, KREM, TMP, f"L_w1f128_m{2 * ph}_%=")
-            self.half_step(em, ph, 0, sp, 0, 0, nxt=(sp, 1), fill_first=fill)
-            self.mask_block(em, 1, KREM, TMP, f"L_w1f128_m{2 * ph + 1}_%=")
-            self.half_step(em, ph, 1, sp, 1, 1, nxt=(ph, 0))
-            em.raw(f"s_sub_i32 {KREM}, {KREM}, 64")
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if ph < 3:
-                em.raw("s_cbranch_scc1 L_w1f128_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1f128_loop_%=")
-        em.raw("L_w1f128_done_%=:")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+        vmov(em, range(32, 64), f"v{self.NINF}")                  # S[1]
+        vmov(em, [*range(64, 80), *range(128, 136)], 0)           # PK[0], l
+        self.init_srcc(em)
 
 
 # ---------------------------------------------------------------------------------------------------- forward, head_dim 128, e4m3 operands
-MFMA8 = "v_mfma_scale_f32_32x32x64_f8f6f4"
-
-
-class Fwd128F8Loop:
-    """The head_dim-128 forward on OCP-e4m3 operands (csrc/attention_f8.hip; BASELINE configs[4] "fp8 MFMA path"): both products of a 64-key tile
+class Fwd128F8Loop(W1Loop):
+    """The head_dim-128 forward on OCP-e4m3 operands (csrc/attention_hd128.hip; BASELINE configs[4] "fp8 MFMA path"): both products of a 64-key tile
        run as v_mfma_scale_f32_32x32x64_f8f6f4 (K = 64 per instruction, 64 cycles: twice the bf16 matrix rate).  Per tile T, one straight-line block:
          C(T-2): O^T[j][db] += V8^T P8            8 MFMAs (4 d-blocks x 2 q-blocks; contraction = the tile's 64 keys)
          A(T)  : S[T&1][j][b] = -M[q] + K8 Q8^T   8 MFMAs (2 key blocks x 2 k-steps of 64 x 2 q-blocks)
@@ -843,9 +747,14 @@ class Fwd128F8Loop:
                       v[200:203] LDS-DMA source offsets   v204 v205 l[j]   v[206:213] partial sums   v[214:217] E8M0 of x [p][j]   v218 v219 2^x
                       v220 v221 v222 E8M0 of eq, ek, ev   v223 -inf   v224 16 h   v225 v226 -M[j]   v227 v228 temporaries"""
 
-    T0, LAK, LAV, VOFF, L, TP, XS, FS, EQ, EK, EV, NINF, HI16, NEGM, U, E = 160, 192, 196, 200, 204, 206, 214, 218, 220, 221, 222, 223, 224, 225, 227, 228
-    QF, FR = 128, 160
-    LEAD = KNOB.get("lead8", 6)
+    NAME, LABEL, VMCNT, NACC = "fwd128f8", "w1f8", 0, 128
+    CLOBBER_V, CLOBBER_A = [(0, 191), (206, 219), (223, 223), (227, 228)], [(160, 223)]
+    MASKED, AHEAD, PREFETCH_SLOT = True, 1, 2
+    MASK_ROW = list(range(16))             # the key order above: score register r of lane half h is key 32 b + 16 h + r
+    MASK_TAIL = ["s_nop 1"]                # the second block's mask sits right in front of the MFMA that reads the tuples it wrote
+    T0, LAK, LAV, VOFF, L, TP, XS, FS, EQ, EK, EV, NINF, HI, NEGM, U, E = 160, 192, 196, 200, 204, 206, 214, 218, 220, 221, 222, 223, 224, 225, 227, 228
+    QF, FR, FW, NFR = 128, 160, 8, 8
+    LEAD = KNOB["lead8"]
 
     def S(self, p, j, b):
         return 64 * p + 32 * j + 16 * b
@@ -853,11 +762,9 @@ class Fwd128F8Loop:
     def P8(self, p, j):
         return 128 + 16 * p + 8 * j
 
-    def frag_reg(self, f):
-        return self.FR + 8 * f
-
-    def issue_frag(self, em, f, slotK, slotV, tag=None):
-        """f 0..3: V8^T d-block f of ring slot slotV; f 4..7: K8 (b, ks) = ((f - 4) >> 1, (f - 4) & 1) of ring slot slotK.  Two 16-byte reads each."""
+    def issue_frag(self, em, f, slotK, _kbA, slotV, _kbC, tag=None):
+        """f 0..3: V8^T d-block f of ring slot slotV; f 4..7: K8 (b, ks) = ((f - 4) >> 1, (f - 4) & 1) of ring slot slotK.  Two 16-byte reads each.
+        (The stretch is a whole tile here: the half-tile arguments of the shared half_step are unused.)"""
         tag = f if tag is None else tag
         r = self.frag_reg(f)
         for u in range(2):
@@ -883,8 +790,6 @@ class Fwd128F8Loop:
         return out
 
     def valu_ops(self, pb):
-        if "novalu" in ABLATE:
-            return []
         ops = []
         for j in range(2):
             s = [self.S(pb, j, b) + r for b in range(2) for r in range(16)]          # byte order of the packed P8: 16 b + r
@@ -913,76 +818,23 @@ class Fwd128F8Loop:
                 ops.append(f"v_cvt_scalef32_pk_fp8_f32 v{d}, v{s[4 * w + 2]}, v{s[4 * w + 3]}, v{self.FS + j} op_sel:[0,0,0,1]")
         return ops
 
-    def mask_lines(self, b, krem, tmp, label):
-        """keys >= krem of key block b get -inf in the srcC tuples (score register r of lane half h = key 32 b + 16 h + r); skipped for full tiles"""
-        out = [f"s_cmp_ge_i32 {krem}, 64", f"s_cbranch_scc1 {label}"]
-        for r in range(16):
-            out += [f"s_sub_i32 {tmp}, {krem}, {32 * b + r}", f"v_cmp_lt_i32 vcc, v{self.HI16}, {tmp}"]
-            out += [f"v_cndmask_b32 v{self.T0 + 16 * j + r}, v{self.NINF}, v{self.NEGM + j}, vcc" for j in range(2)]
-        out += ["s_nop 1", f"{label}:"]
-        return out
-
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT, KREM, TMP = "%0", "%1", "%2", "%3"
-        RK, RV, KSTEP, VSTEP, WBASE, NITER, KREM0 = "%[rk]", "%[rv]", "%[kstep]", "%[vstep]", "%[wbase]", "%[niter]", "%[krem]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        em.raw(f"s_mov_b32 {KREM}, {KREM0}")
-        for i in range(128):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
+    def init_regs(self, em):
         em.raw(f"v_mov_b32 v{self.NINF}, 0xff800000")
-        for r in range(64, 128):                       # S[1]: the first B stage (tile -1) must produce p = 0
-            em.raw(f"v_mov_b32 v{r}, v{self.NINF}")
-        for r in list(range(128, 160)) + [self.L, self.L + 1]:
-            em.raw(f"v_mov_b32 v{r}, 0")
-        for r in range(self.XS, self.XS + 4):
-            em.raw(f"v_mov_b32 v{r}, 127")
-        for j in range(2):
-            for r in range(16):
-                em.raw(f"v_mov_b32 v{self.T0 + 16 * j + r}, v{self.NEGM + j}")
-        for f in range(4):
-            self.issue_frag(em, f, 0, 2, tag=("n", f))
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1f8_loop_%=:")
-        for ph in range(4):
-            em.raw("s_waitcnt vmcnt(0)")
-            if "nosync" not in ABLATE:
-                em.raw("s_barrier")
-            dst = ((ph + 1) & 3) * 16384
-            fill = []
-            for k in range(4):
-                isV = k >= 2
-                fill.append([f"s_add_u32 m0, {WBASE}, {dst + (8192 if isV else 0) + (k & 1) * 1024}"])
-                fill.append([f"buffer_load_dwordx4 v{self.VOFF + k}, {RV if isV else RK}, 0 offen lds",
-                             f"v_add_u32 v{self.VOFF + k}, {VSTEP if isV else KSTEP}, v{self.VOFF + k}"])
-            pa = ph & 1
-            for ln in self.mask_lines(0, KREM, TMP, f"L_w1f8_m{2 * ph}_%="):
-                em.raw(ln)
-            need = {0: 0, 1: 2, 2: 4, 3: 6, 4: 8, 5: 10, 6: 12, 7: 14}
-            slotV_next = (ph - 1) & 3                    # C of the NEXT iteration reads V8^T of tile T - 1
-            post = [lambda f=f: self.issue_frag(em, f, 0, slotV_next, tag=("n", f)) for f in range(4)]
-            em.retag({("n", f): f for f in range(4)})
-            schedule(em, self.mfmas(pa, pa), lambda f: self.issue_frag(em, f, ph, (ph - 2) & 3), need, self.valu_ops(pa ^ 1), self.LEAD,
-                     pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill, raw_after={11: self.mask_lines(1, KREM, TMP, f"L_w1f8_m{2 * ph + 1}_%=")})
-            em.raw(f"s_sub_i32 {KREM}, {KREM}, 64")
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if ph < 3:
-                em.raw("s_cbranch_scc1 L_w1f8_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1f8_loop_%=")
-        em.raw("L_w1f8_done_%=:")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+        vmov(em, range(64, 128), f"v{self.NINF}")                 # S[1]: the first B stage (tile -1) must produce p = 0
+        vmov(em, [*range(128, 160), self.L, self.L + 1], 0)
+        vmov(em, range(self.XS, self.XS + 4), 127)
+        self.init_srcc(em)
+
+    def phase(self, em, ph):
+        """one stretch per tile T = ph: A reads K8 of slot ph, C reads V8^T of tile T - 2, the NEXT stretch's C that of tile T - 1; key block 1's mask
+        is pinned behind MFMA 11, the last score product of key block 0"""
+        for ln in self.mask_lines(0, ph):
+            em.raw(ln)
+        self.half_step(em, ph, 0, (ph - 2) & 3, 0, ph & 1, nxt=((ph - 1) & 3, 0), fill_first=self.fill(ph), raw_after={11: self.mask_lines(1, ph)})
 
 
 # ---------------------------------------------------------------------------------------------------------- dK, dV, head_dim 128
-class Dkv128Loop:
+class Dkv128Loop(W1Loop):
     """DkvLoop for head_dim 128 (csrc/attention_hd128.hip): ONE 32-key block per wave -- dK^T, dV^T (4 d-blocks each) and the K, V
        fragments (8 k-steps each) already take 192 AGPRs -- streaming 64-row Q|dO tiles; per 32-row half-tile g:
          A(g): S[g&1] = -lse2[q] / c + Q_g K^T,  DP[g&1] = -delta[q] + dO_g V^T        16 MFMAs (8 k-steps each); q unscaled, so
@@ -997,11 +849,15 @@ class Dkv128Loop:
                       v[128:159] lane LDS offsets [slot pair][rows ks 0..7 | transposed (db, second read) 0..7]
                       v[160:167] LDS-DMA source offsets (Q x4, dO x4)   v168 statistics source offset   v169 statistics read base"""
 
+    NAME, LABEL, VMCNT, NACC, SLOT = "dkv128", "w1dkv128", 9, 128, 32768
+    CLOBBER_V, CLOBBER_A = [(0, 127)], [(192, 255)]
+    OPERANDS, STATS, EXTRA_NEED = QDO, True, {"cs": 16, "cd": 24}
     LA = 128
     VOFF = 160
     SB = 169
+    CS, CD = 96, 112
     FR = 192
-    LEAD = KNOB.get("lead", 6)
+    NFR = 16
 
     def S(self, p):
         return p * 32
@@ -1015,19 +871,12 @@ class Dkv128Loop:
     def DSK(self, p, cc):
         return 64 + p * 16 + 8 + cc * 4
 
-    def frag_reg(self, f):
-        return self.FR + 4 * (f % 16)
-
     def issue_frag(self, em, f, slotA, qbA, slotC, qbC, tag=None):
         """f 0..15: transposed fragments of the PREVIOUS half (even: dO tile, odd: Q tile; (cc, db) = (f >> 3, (f >> 1) & 3));
         16..23: Q rows ks; 24..31: dO rows ks; "cs" / "cd": the srcC tuples"""
         tag = f if tag is None else tag
         if f == "cs" or f == "cd":
-            base = 96 if f == "cs" else 112
-            for g in range(4):
-                off = slotA * 1024 + 512 * qbA + 256 * (g >> 1) + 32 * (g & 1) + (64 if f == "cd" else 0)
-                em.ds(f"ds_read_b128 {vr(base + 4 * g, 4)}, v{self.SB} offset:{off}", tag)
-            return
+            return self.issue_stats(em, f, slotA, qbA, tag)
         r = self.frag_reg(f)
         if f < 16:
             c = f >> 1
@@ -1054,18 +903,15 @@ class Dkv128Loop:
             out.append((f"{MFMA} {d}, {ar(self.frag_reg(f), 4)}, {b}, {d}", f))
         for ks in range(8):
             d = vr(self.S(pa), 16)
-            c = vr(96, 16) if ks == 0 else d
+            c = vr(self.CS, 16) if ks == 0 else d
             out.append((f"{MFMA} {d}, {ar(self.frag_reg(16 + ks), 4)}, {ar(128 + 4 * ks, 4)}, {c}", 16 + ks))
         for ks in range(8):
             d = vr(self.DP(pa), 16)
-            c = vr(112, 16) if ks == 0 else d
+            c = vr(self.CD, 16) if ks == 0 else d
             out.append((f"{MFMA} {d}, {ar(self.frag_reg(24 + ks), 4)}, {ar(160 + 4 * ks, 4)}, {c}", 24 + ks))
         return out
 
     def valu_ops(self, pb):
-        if "novalu" in ABLATE:
-            return []
-
         def unit(p):
             s0, d0 = self.S(pb) + 2 * p, self.DP(pb) + 2 * p
             wp, wd = self.PK(pb, p >> 2) + (p & 3), self.DSK(pb, p >> 2) + (p & 3)
@@ -1080,62 +926,12 @@ class Dkv128Loop:
             ops += [o for o in (x[0], m[0], x[1], c[0], x[2], m[1], x[3], c[1]) if o is not None]
         return ops
 
-    def half_step(self, em, slotA, qbA, slotC, qbC, pa, nxt, fill_first=()):
-        need = {f: f for f in range(32)}
-        need["cs"] = 16
-        need["cd"] = 24
-        post = [lambda f=f: self.issue_frag(em, f, 0, 0, nxt[0], nxt[1], tag=("n", f)) for f in range(4)]
-        em.retag({("n", f): f for f in range(4)})
-        schedule(em, self.mfmas(pa, pa), lambda f: self.issue_frag(em, f, slotA, qbA, slotC, qbC), need, self.valu_ops(pa ^ 1), self.LEAD,
-                 pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill_first)
-
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT = "%0", "%1"
-        RQ, RDO, RST, QSTEP, DSTEP, WBASE, SBASE, NITER = "%[rq]", "%[rdo]", "%[rst]", "%[qstep]", "%[dstep]", "%[wbase]", "%[sbase]", "%[niter]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        for i in range(128):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
-        for r in list(range(32, 64)) + list(range(64, 80)):      # S / DP[1], PK / DSK[0]
-            em.raw(f"v_mov_b32 v{r}, 0")
-        for f in range(4):
-            self.issue_frag(em, f, 0, 0, 3, 0, tag=("n", f))
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1dkv128_loop_%=:")
-        for ph in range(4):
-            em.raw("s_waitcnt vmcnt(9)")
-            if "nosync" not in ABLATE:
-                em.raw("s_barrier")
-            dst = ((ph + 2) & 3) * 32768
-            fill = []
-            for k in range(8):
-                isdo = k >= 4
-                fill.append([f"s_add_u32 m0, {WBASE}, {dst + (16384 if isdo else 0) + (k & 3) * 1024}"])
-                fill.append([f"buffer_load_dwordx4 v{self.VOFF + k}, {RDO if isdo else RQ}, 0 offen lds",
-                             f"v_add_u32 v{self.VOFF + k}, {DSTEP if isdo else QSTEP}, v{self.VOFF + k}"])
-            fill.append([f"s_add_u32 m0, {SBASE}, {((ph + 2) & 3) * 1024}"])
-            fill.append([f"buffer_load_dword v{self.VOFF + 8}, {RST}, 0 offen lds", f"v_add_u32 v{self.VOFF + 8}, 256, v{self.VOFF + 8}"])
-            sp = (ph - 1) & 3
-            self.half_step(em, ph, 0, sp, 0, 0, nxt=(sp, 1), fill_first=fill)
-            self.half_step(em, ph, 1, sp, 1, 1, nxt=(ph, 0))
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if ph < 3:
-                em.raw("s_cbranch_scc1 L_w1dkv128_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1dkv128_loop_%=")
-        em.raw("L_w1dkv128_done_%=:")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+    def init_regs(self, em):
+        vmov(em, [*range(32, 64), *range(64, 80)], 0)      # S / DP[1], PK / DSK[0]
 
 
 # ------------------------------------------------------------------------------------- dQ, head_dim 128, two q-blocks per wave
-class Dq128x2Loop:
+class Dq128x2Loop(W1Loop):
     """DqLoop for head_dim 128 with TWO 32-row q-blocks j per wave, streaming 64-key K|V tiles (LDS image as Fwd128Loop), so that every streamed K / V
        fragment feeds two MFMAs (the matrix pipe's energy floor is 0.74 J per TFLOP and every 1 KiB fragment read per MFMA adds 0.24:
        tools/mfma_energy_probe.hip, DESIGN section 4.2 -- a single q-block per wave pays one read per MFMA).  dQ^T (128) + the Q and dO fragments of both
@@ -1149,13 +945,14 @@ class Dq128x2Loop:
                       v[0:127] S / DP [p][j] (s dp)   v[128:159] D[p][j][cc]   v[160:191] fragment ring (8 x 4)
                       v[192:223] lane LDS offsets [slot pair][16]   v[224:231] LDS-DMA source offsets (K x4, V x4)   v232 v233 -lse2[q_j]   v234 v235 -delta[q_j]"""
 
+    NAME, LABEL, VMCNT, NACC, SLOT = "dq128x2", "w1dq128x2", 8, 128, 32768
+    CLOBBER_V, CLOBBER_A = [(0, 191)], []
     LA = 192
     VOFF = 224
     NL = 232
     ND = 234
     FR = 160
     NFR = 8
-    LEAD = KNOB.get("lead", 6)
 
     def S(self, p, j):
         return 64 * p + 32 * j
@@ -1165,9 +962,6 @@ class Dq128x2Loop:
 
     def D(self, p, j, cc):
         return 128 + 16 * p + 8 * j + 4 * cc
-
-    def frag_reg(self, f):
-        return self.FR + 4 * (f % self.NFR)
 
     def issue_frag(self, em, f, slotA, kbA, slotC, kbC, tag=None):
         """f 0..7: transposed K fragments (cc, db) = (f >> 2, f & 3) of the PREVIOUS half; 8..15: K rows ks; 16..23: V rows ks"""
@@ -1202,9 +996,6 @@ class Dq128x2Loop:
         return out
 
     def valu_ops(self, pb):
-        if "novalu" in ABLATE:
-            return []
-
         def unit(u):
             j, p = u >> 3, u & 7
             s0, d0 = self.S(pb, j) + 2 * p, self.DP(pb, j) + 2 * p
@@ -1224,58 +1015,12 @@ class Dq128x2Loop:
             ops += [o for o in (a[0], x[0], a[1], x[1], m[0], x[2], m[1], x[3], c) if o is not None]
         return ops
 
-    def half_step(self, em, slotA, kbA, slotC, kbC, pa, nxt, fill_first=()):
-        need = {f: 2 * f for f in range(24)}
-        post = [lambda f=f: self.issue_frag(em, f, 0, 0, nxt[0], nxt[1], tag=("n", f)) for f in range(4)]
-        em.retag({("n", f): f for f in range(4)})
-        schedule(em, self.mfmas(pa, pa), lambda f: self.issue_frag(em, f, slotA, kbA, slotC, kbC), need, self.valu_ops(pa ^ 1), self.LEAD,
-                 pre_issued=(0, 1, 2, 3), post_issue=post, fill_first=fill_first)
-
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT = "%0", "%1"
-        RK, RV, KSTEP, VSTEP, WBASE, NITER = "%[rk]", "%[rv]", "%[kstep]", "%[vstep]", "%[wbase]", "%[niter]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        for i in range(128):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
-        for r in list(range(64, 128)) + list(range(128, 144)):      # S / DP[1], D[0]
-            em.raw(f"v_mov_b32 v{r}, 0")
-        for f in range(4):
-            self.issue_frag(em, f, 0, 0, 3, 0, tag=("n", f))
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1dq128x2_loop_%=:")
-        for ph in range(4):
-            em.raw("s_waitcnt vmcnt(8)")
-            if "nosync" not in ABLATE:
-                em.raw("s_barrier")
-            dst = ((ph + 2) & 3) * 32768
-            fill = []
-            for k in range(8):
-                isv = k >= 4
-                fill.append([f"s_add_u32 m0, {WBASE}, {dst + (16384 if isv else 0) + (k & 3) * 1024}"])
-                fill.append([f"buffer_load_dwordx4 v{self.VOFF + k}, {RV if isv else RK}, 0 offen lds",
-                             f"v_add_u32 v{self.VOFF + k}, {VSTEP if isv else KSTEP}, v{self.VOFF + k}"])
-            sp = (ph - 1) & 3
-            self.half_step(em, ph, 0, sp, 0, 0, nxt=(sp, 1), fill_first=fill)
-            self.half_step(em, ph, 1, sp, 1, 1, nxt=(ph, 0))
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if ph < 3:
-                em.raw("s_cbranch_scc1 L_w1dq128x2_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1dq128x2_loop_%=")
-        em.raw("L_w1dq128x2_done_%=:")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+    def init_regs(self, em):
+        vmov(em, [*range(64, 128), *range(128, 144)], 0)      # S / DP[1], D[0]
 
 
 # --------------------------------------------------------------------------------------------------------------------- GEMM loop
-class GemmLoop:
+class GemmLoop(W1Loop):
     """C^T tile = W A^T for a 256 (M) x 128 (N) output tile, operands both K-contiguous (x [M, K], W [N, K]: y = x W^T), BK = 64 per
        stage, 4 waves as 2 (M) x 2 (N): a wave owns 128 x 64 of the tile = 2 (n) x 4 (m) accumulator blocks, D[n][m] (column m on the
        lanes, so a lane ends up with runs of 4 consecutive n = 8-byte pieces of a C row).
@@ -1284,6 +1029,10 @@ class GemmLoop:
        register map   a[0:127] acc[ni][mi]   a[128:175] fragment ring: 2 sets x (W n0 n1, A m0..m3)
                       v[0:11] LDS-DMA source offsets (8 A pieces, 4 W pieces; + 128 bytes per stage)
                       v[12:35] lane read offsets [stage][A ks0..3, W ks0..3] (wave's panel offset and the stage base folded in)"""
+
+    NAME, LABEL, STAGES, VMCNT, NACC = "gemm", "w1gemm", 3, 12, 128
+    CLOBBER_V, CLOBBER_A = [], [(128, 175)]
+    NOSYNC, PREFETCH_SLOT = False, None
 
     def frag(self, setno, i):          # i: 0,1 = W n-block; 2..5 = A m-block
         return 128 + 24 * setno + 4 * i
@@ -1295,61 +1044,31 @@ class GemmLoop:
             base = 12 + 8 * stage + (4 if isW else 0) + ks
             em.ds(f"ds_read_b128 {ar(self.frag(setno, i), 4)}, v{base} offset:{4096 * blk}", tag)
 
-    def generate(self):
-        em = Emitter()
-        SAVE_M0, CNT = "%0", "%1"
-        RA, RW, WBA, WBW, NITER = "%[ra]", "%[rw]", "%[wba]", "%[wbw]", "%[niter]"
-        em.raw(f"s_mov_b32 {SAVE_M0}, m0")
-        em.raw(f"s_mov_b32 {CNT}, {NITER}")
-        for i in range(128):
-            em.raw(f"v_accvgpr_write_b32 a{i}, 0")
-        for _ in range(KNOB.get("pad4", 0)):      # placement experiment: shift the loop body by 4 bytes per unit (MI355X_MICROARCH.md "code-placement sensitivity")
-            em.raw("s_nop 0")
-        em.raw("L_w1gemm_loop_%=:")
-        for st in range(3):
-            # stage `st` landed for every wave (this wave's 12 pieces of the NEXT stage may still fly); everyone is past stage st-1
-            em.raw("s_waitcnt vmcnt(12)")
-            em.raw("s_barrier")
-            nxt = (st + 2) % 3
-            dma = []
-            for k in range(12):
-                isW = k >= 8
-                dst = nxt * 49152 + (32768 if isW else 0) + (k - 8 if isW else k) * 1024
-                dma.append([f"s_add_u32 m0, {WBW if isW else WBA}, {dst}"])
-                dma.append([f"buffer_load_dwordx4 v{k}, {RW if isW else RA}, 0 offen lds", f"v_add_u32 v{k}, 128, v{k}"])
-            self.issue_set(em, st, 0, 0, ("s", 0))
-            slot = 0
-            for ks in range(4):
-                setno = ks & 1
-                if ks + 1 < 4:
-                    pass
-                em.wait_tag(("s", ks))
-                mf = []
-                for ni in range(2):
-                    for mi in range(4):
-                        d = ar((ni * 4 + mi) * 16, 16)
-                        mf.append(f"{MFMA} {d}, {ar(self.frag(setno, ni), 4)}, {ar(self.frag(setno, 2 + mi), 4)}, {d}")
-                for i, text in enumerate(mf):
-                    em.raw(text)
-                    if i == 1 and ks + 1 < 4:      # the next k-step's fragments go to the other register set (its readers are done)
-                        self.issue_set(em, st, ks + 1, setno ^ 1, ("s", ks + 1))
-                    if slot < len(dma):
-                        for t in dma[slot]:
-                            em.raw(t)
-                        slot += 1
-            assert slot == len(dma)
-            em.raw(f"s_sub_u32 {CNT}, {CNT}, 1")
-            em.raw(f"s_cmp_eq_u32 {CNT}, 0")
-            if st < 2:
-                em.raw("s_cbranch_scc1 L_w1gemm_done_%=")
-            else:
-                em.raw("s_cbranch_scc0 L_w1gemm_loop_%=")
-        em.raw("L_w1gemm_done_%=:")
-        em.raw("s_waitcnt vmcnt(0) lgkmcnt(0)")
-        em.raw("s_nop 7")
-        em.raw("s_nop 7")
-        em.raw(f"s_mov_b32 m0, {SAVE_M0}")
-        return em.text() + "\n"
+    def phase(self, em, st):
+        """stage `st` landed for every wave (this wave's 12 pieces of the NEXT stage may still fly); everyone is past stage st-1, whose panels the
+        LDS-DMA issued between this stage's MFMAs refills"""
+        nxt = ((st + 2) % 3) * 49152
+        dma = (dma_fill(0, [("%[ra]", 128, nxt + 1024 * k) for k in range(8)], wbase="%[wba]") +
+               dma_fill(8, [("%[rw]", 128, nxt + 32768 + 1024 * k) for k in range(4)], wbase="%[wbw]"))
+        self.issue_set(em, st, 0, 0, ("s", 0))
+        slot = 0
+        for ks in range(4):
+            setno = ks & 1
+            em.wait_tag(("s", ks))
+            mf = []
+            for ni in range(2):
+                for mi in range(4):
+                    d = ar((ni * 4 + mi) * 16, 16)
+                    mf.append(f"{MFMA} {d}, {ar(self.frag(setno, ni), 4)}, {ar(self.frag(setno, 2 + mi), 4)}, {d}")
+            for i, text in enumerate(mf):
+                em.raw(text)
+                if i == 1 and ks + 1 < 4:      # the next k-step's fragments go to the other register set (its readers are done)
+                    self.issue_set(em, st, ks + 1, setno ^ 1, ("s", ks + 1))
+                if slot < len(dma):
+                    for t in dma[slot]:
+                        em.raw(t)
+                    slot += 1
+        assert slot == len(dma)
 
 
 def clobbers(ranges, aranges=()):
@@ -1362,24 +1081,13 @@ def clobbers(ranges, aranges=()):
     return ",\n".join("    " + ln for ln in lines) + "\n"
 
 
-TARGETS = {"w1_dq_loop.inc": lambda: DqLoop().generate(),
-           "w1_dq_clobbers.inc": lambda: clobbers([(0, 159)], [(128, 151)]),
-           "w1_dkv_loop.inc": lambda: DkvLoop().generate(),
-           "w1_dkv_clobbers.inc": lambda: clobbers([(0, 223)], [(192, 223)]),
-           "w1_fwd128_loop.inc": lambda: Fwd128Loop().generate(),
-           "w1_fwd128_clobbers.inc": lambda: clobbers([(0, 127), (185, 185)], [(192, 255)]),
-           "w1_fwd128f8_loop.inc": lambda: Fwd128F8Loop().generate(),
-           "w1_fwd128f8_clobbers.inc": lambda: clobbers([(0, 191), (206, 219), (223, 223), (227, 228)], [(160, 223)]),
-           "w1_dkv128_loop.inc": lambda: Dkv128Loop().generate(),
-           "w1_dkv128_clobbers.inc": lambda: clobbers([(0, 127)], [(192, 255)]),
-           "w1_dq128x2_loop.inc": lambda: Dq128x2Loop().generate(),
-           "w1_dq128x2_clobbers.inc": lambda: clobbers([(0, 191)], []),
-           "w1_gemm_loop.inc": lambda: GemmLoop().generate(),
-           "w1_gemm_clobbers.inc": lambda: clobbers([], [(128, 175)]),
-           "w1_fwd_loop.inc": lambda: FwdLoop().generate(),
-           "w1_fwd_clobbers.inc": lambda: clobbers([(0, 127), (157, 157)], [(96, 127)] + ([(128, 131)] if KNOB.get("mfsum", 1) else [])),
-           # what the C++ around the forward loop must know about the knobs the loop was generated with (attention_w1.hip: selector operand, epilogue)
-           "w1_fwd_knobs.inc": lambda: f"#define W1_FWD_MFSUM {1 if KNOB.get('mfsum', 1) else 0}\n"}
+LOOPS = (DqLoop, DkvLoop, FwdLoop, Fwd128Loop, Fwd128F8Loop, Dkv128Loop, Dq128x2Loop, GemmLoop)
+TARGETS = {}
+for _cls in LOOPS:
+    TARGETS[f"w1_{_cls.NAME}_loop.inc"] = lambda cls=_cls: cls().generate()
+    TARGETS[f"w1_{_cls.NAME}_clobbers.inc"] = lambda cls=_cls: clobbers(cls.CLOBBER_V, cls.CLOBBER_A)
+# what the C++ around the forward loop must know about the knobs the loop was generated with (attention_w1.hip: selector operand, epilogue)
+TARGETS["w1_fwd_knobs.inc"] = lambda: f"#define W1_FWD_MFSUM {1 if KNOB['mfsum'] else 0}\n"
 
 
 def main():

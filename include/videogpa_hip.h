@@ -181,7 +181,9 @@ int32_t vgpa_attn_bwd_dkv_w1(const void* q, const void* k, const void* v, const 
  * train/CogVideoX-5B/03_train.py:102-106).  bf16 row-major operands with explicit row strides (elements).
  *   down  : T[M,R]  = X[M,K] A[R,K]^T                     K % 64 == 0, R <= 256
  *   up_add: Y[M,N]  = (accumulate ? Y : 0) + s * T[M,rp] Bw[N,rp]^T   rp in {16,32,48,64,96,128,192}, N % 8 == 0
- *   grad  : G[P,Q]  = s * U[M,P]^T V[M,Q]                 G fp32, overwritten; P % 8 == 0, Q % 8 == 0 */
+ *   grad  : G[P,Q]  = s * U[M,P]^T V[M,Q]                 G fp32, overwritten; P % 8 == 0, Q % 8 == 0
+ * Every row stride is a multiple of 8 and at least the row's length (ldx >= K, ldt >= R resp. rp, ldy >= N, ldb >= rp, ldu >= P, ldv >= Q, ldg >= Q): rows that
+ * overlap, or run backwards, are VGPA_ERR_INVALID.  Operands that are read are 16-byte aligned, T of `down` 8-byte (it is stored in 8-byte pieces), Y 16-byte. */
 int32_t vgpa_lora_down(const void* X, int64_t ldx, const void* A, void* T, int64_t ldt, int64_t M, int64_t K, int64_t R,
                        vgpa_stream_t stream);
 int32_t vgpa_lora_up_add(void* Y, int64_t ldy, const void* T, int64_t ldt, const void* Bw, int64_t ldb, float s, int64_t M,

@@ -10,6 +10,7 @@ import torch.nn.functional as F
 pytestmark = pytest.mark.gpu
 
 import attn_tol
+import lora_tol
 import row_tol
 from attn_ref64 import attn_ref64
 from attn_tol import lse2_tol
@@ -287,6 +288,7 @@ def test_lora_kernels_raw(ops, M, K, r, n):
     t = ops.lora_down(dev(x), dev(a_cat))
     t_ref = x.double() @ a_cat.double().t()
     assert (t.double().cpu() - t_ref).abs().max().item() < 0.02 * t_ref.abs().max().item() + 1e-3
+    assert not lora_tol.judge("down", t.cpu(), t_ref, lora_tol.down_tol(t_ref, x.double().abs() @ a_cat.double().abs().t(), K))     # per element: tests/lora_tol.py
     # up_add into a column slice of a wider buffer
     N = 96
     y = torch.randn(M, n * N, generator=g).to(torch.bfloat16)
@@ -299,15 +301,19 @@ def test_lora_kernels_raw(ops, M, K, r, n):
         ref = y[:, j * N:(j + 1) * N].double() + 2.0 * (t[:, j * rp:(j + 1) * rp].double().cpu() @ bw.double().t())
         err = (yd[:, j * N:(j + 1) * N].double().cpu() - ref).abs().max().item()
         assert err < 0.02 * ref.abs().max().item() + 1e-3, err
+        ref_j, dot, S = lora_tol.up_ref64(y[:, j * N:(j + 1) * N], t[:, j * rp:(j + 1) * rp].cpu(), bw, 2.0)
+        assert not lora_tol.judge(f"up_add {j}", yd[:, j * N:(j + 1) * N].cpu(), ref_j, lora_tol.up_tol(ref_j, dot, S, 2.0, rp, True))
     # grad: fp32 U^T V over tokens
     u = torch.randn(M, n * rp, generator=g).to(torch.bfloat16)
     gr = ops.lora_grad(dev(u), dev(x), 0.5)
     ref = 0.5 * (u.double().t() @ x.double())
     assert gr.dtype == torch.float32 and tuple(gr.shape) == (n * rp, K)
     assert (gr.double().cpu() - ref).abs().max().item() < 2e-3 * ref.abs().max().item() + 1e-4
+    assert not lora_tol.judge("grad", gr.cpu(), ref, lora_tol.grad_tol(ref, lora_tol.grad_ref64(u, x, 0.5)[1], 0.5, M))
     gr2 = ops.lora_grad(dev(x)[:, :64], dev(u), 1.0)          # strided U (column slice)
     ref2 = x[:, :64].double().t() @ u.double()
     assert (gr2.double().cpu() - ref2).abs().max().item() < 2e-3 * ref2.abs().max().item() + 1e-4
+    assert not lora_tol.judge("grad, U a column slice", gr2.cpu(), ref2, lora_tol.grad_tol(ref2, lora_tol.grad_ref64(x[:, :64], u, 1.0)[1], 1.0, M))
 
 
 def test_lora_grad_is_bit_reproducible_at_the_headline_shape(ops):
@@ -322,6 +328,8 @@ def test_lora_grad_is_bit_reproducible_at_the_headline_shape(ops):
     assert all(torch.equal(a[0], x) for x in a[1:]) and all(torch.equal(b[0], x) for x in b[1:])
     ref = 2.0 * (dy[:, :256].double().t() @ t[:, 64:128].double())
     assert (a[0][:256].double() - ref).abs().max().item() < 1e-3 * ref.abs().max().item()
+    for name, got, (ref, S), sc in (("dB", a[0], lora_tol.grad_ref64(dy, t[:, 64:128], 2.0), 2.0), ("dA", b[0], lora_tol.grad_ref64(t, dy, 1.0), 1.0)):
+        assert not lora_tol.judge(name, got, ref, lora_tol.grad_tol(ref, S, sc, M))          # every element, fp64 on the device
 
 
 def test_linear_lora_function_vs_torch(ops):
@@ -355,6 +363,19 @@ def test_linear_lora_function_vs_torch(ops):
         assert (Ad[i].grad.double().cpu() - Ar[i].grad).abs().max().item() < 0.03 * Ar[i].grad.abs().max().item()
         assert (Bd[i].grad.double().cpu() - Br[i].grad).abs().max().item() < 0.03 * Br[i].grad.abs().max().item()
     assert Ad[1].grad is None and Bd[1].grad is None
+    # dA, dB per element against fp64 of the device's OWN bf16 intermediates (T = lora_down(x, bf16(A)), dT = lora_down(dy_i, bf16(float(bf16(B)) s)^T)): the adapter-gradient
+    # kernel alone, without the vendor GEMM's rounding or the 3 % of the maximum above
+    rp, M = ops._pad_rank(r), Bt * S
+    x2, dy2 = dev(x).reshape(M, K), dev(dy).reshape(M, 3 * Dn)
+    for i in (0, 2):
+        a_pad, sbt = torch.zeros(rp, K, dtype=torch.bfloat16, device="cuda"), torch.zeros(rp, Dn, dtype=torch.bfloat16, device="cuda")
+        a_pad[:r] = Ad[i].detach().to(torch.bfloat16)
+        sbt[:r] = (Bd[i].detach().to(torch.bfloat16).float() * 2.0).to(torch.bfloat16).t()
+        T, dT = ops.lora_down(x2, a_pad)[:, :r], ops.lora_down(dy2[:, i * Dn:(i + 1) * Dn], sbt)[:, :r]
+        ref, Sm = lora_tol.grad_ref64(dy2[:, i * Dn:(i + 1) * Dn], T, 2.0)
+        assert not lora_tol.judge(f"dB[{i}]", Bd[i].grad, ref, lora_tol.grad_tol(ref, Sm, 2.0, M))
+        ref, Sm = lora_tol.grad_ref64(dT, x2, 1.0)
+        assert not lora_tol.judge(f"dA[{i}]", Ad[i].grad, ref, lora_tol.grad_tol(ref, Sm, 1.0, M))
 
 
 # ------------------------------------------------------------------------------------------ edge cases / error codes

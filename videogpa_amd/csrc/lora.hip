@@ -382,12 +382,15 @@ __global__ __launch_bounds__(256) void lora_ext_refresh_kernel(const float* __re
 }
 
 static inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+static inline bool a8(const void* p) { return ((uintptr_t)p & 7) == 0; }
 
 extern "C" {
 
-// T[M,R] = X[M,K] A[R,K]^T  (bf16; X row stride ldx, T row stride ldt; K % 64 == 0; R <= 256; ldx, ldt, K multiples of 8)
+// T[M,R] = X[M,K] A[R,K]^T  (bf16; X row stride ldx >= K, T row stride ldt >= R; K % 64 == 0; R <= 256; ldx, ldt multiples of 8; X, A 16-byte and T 8-byte aligned:
+// T leaves as 8-byte pieces, and a stride below the row length -- a negative one included -- would put the DMA descriptor's end, (rows - 1) ldx + K, before its base)
 int32_t vgpa_lora_down(const void* X, int64_t ldx, const void* A, void* T, int64_t ldt, int64_t M, int64_t K, int64_t R, hipStream_t stream) {
-    if (!X || !A || !T || M <= 0 || K <= 0 || K % 64 != 0 || R <= 0 || R > 256 || ldx % 8 || ldt % 8 || ldt < R || !a16(X) || !a16(A)) return VGPA_ERR_INVALID;
+    if (!X || !A || !T || M <= 0 || K <= 0 || K % 64 != 0 || R <= 0 || R > 256 || ldx % 8 || ldt % 8 || ldx < K || ldt < R || !a16(X) || !a16(A) || !a8(T))
+        return VGPA_ERR_INVALID;
     if (M > ((int64_t)1 << 31) * 32) return VGPA_ERR_INVALID;
     const int ncb = (int)((R + 31) / 32);
     const dim3 grid((unsigned)((M + 63) / 64));
@@ -430,11 +433,13 @@ int32_t vgpa_lora_down(const void* X, int64_t ldx, const void* A, void* T, int64
     return VGPA_OK;
 }
 
-// Y[M,N] = (accumulate ? Y : 0) + s * T[M,rp] Bw[N,rp]^T   (bf16; rp in {16,32,48,64,96,128,192}; N % 8 == 0; 16-byte aligned rows of Y)
+// Y[M,N] = (accumulate ? Y : 0) + s * T[M,rp] Bw[N,rp]^T   (bf16; rp in {16,32,48,64,96,128,192}; N % 8 == 0; 16-byte aligned rows of Y, T, Bw; ldy >= N -- overlapping rows
+// of Y would be read-modify-written by two workgroups -- and ldt, ldb >= rp: every lane reads rp columns of its row)
 int32_t vgpa_lora_up_add(void* Y, int64_t ldy, const void* T, int64_t ldt, const void* Bw, int64_t ldb, float s, int64_t M, int64_t N,
                          int64_t rp, int32_t accumulate, hipStream_t stream) {
     if (!Y || !T || !Bw || M <= 0 || N <= 0 || N % 8 != 0 || ldy % 8 || ldt % 8 || ldb % 8 || !a16(T) || !a16(Bw) || !a16(Y))
         return VGPA_ERR_INVALID;
+    if (ldy < N || ldt < rp || ldb < rp) return VGPA_ERR_INVALID;
     const dim3 grid((unsigned)((M + 63) / 64), (unsigned)((N + UP_COLS - 1) / UP_COLS));
 #define UP(KS) VGPA_LAUNCH((lora_up_add_kernel<KS>), grid, dim3(256), 0, stream, (bf16_t*)Y, ldy, (const bf16_t*)T, ldt, (const bf16_t*)Bw, ldb, s, M, (int)N, (int)accumulate)
     switch (rp) {
@@ -463,7 +468,7 @@ static void lora_grad_plan(int64_t M, int64_t P, int64_t Q, int* n_pt, int* n_qt
     *splits = (M + r - 1) / r;
 }
 
-// G[P,Q] (fp32, row stride ldg) = s * U[M,P]^T V[M,Q]   (bf16 operands, P, Q multiples of 8), bit-reproducible: every row range writes
+// G[P,Q] (fp32, row stride ldg >= Q) = s * U[M,P]^T V[M,Q]   (bf16 operands, P, Q multiples of 8, ldu >= P, ldv >= Q), bit-reproducible: every row range writes
 // its partial [P, Q] into the caller's workspace (>= vgpa_lora_grad_workspace_bytes) and a merge kernel adds the partials in a fixed
 // order.  G is overwritten (no zeroing needed).
 size_t vgpa_lora_grad_workspace_bytes(int64_t M, int64_t P, int64_t Q) {
@@ -477,6 +482,7 @@ int32_t vgpa_lora_grad_ws(const void* U, int64_t ldu, const void* V, int64_t ldv
                           int64_t Q, void* workspace, size_t ws_bytes, hipStream_t stream) {
     if (!U || !V || !G || !workspace || M <= 0 || P <= 0 || Q <= 0 || P % 8 || Q % 8 || ldu % 8 || ldv % 8 || !a16(U) || !a16(V) || !a16(workspace))
         return VGPA_ERR_INVALID;
+    if (ldu < P || ldv < Q || ldg < Q || ((uintptr_t)G & 3)) return VGPA_ERR_INVALID;      // ldg < Q: the merge kernel's rows of G would overlap
     int n_pt, n_qt;
     int64_t rows, splits;
     lora_grad_plan(M, P, Q, &n_pt, &n_qt, &rows, &splits);

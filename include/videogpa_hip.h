@@ -475,6 +475,33 @@ int32_t vgpa_dualdpt_aux_tail_f32(const float* x, const float* xtab, const float
                                   const float* ln_w, const float* ln_b, float eps, const float* w2, const float* b2, float* preds, float* conf,
                                   int64_t N, int64_t h, int64_t w, int64_t C, int32_t output_dim, vgpa_stream_t stream);
 
+/* ---- CogVideoX VAE encoder on one frame (diffusers' autoencoder_kl_cogvideox.py; videogpa_amd/vae.py, csrc/vae.hip): fp32, NHWC, forward only ----
+ * The 3x3 convolution of vgpa_conv3x3_f32 with its zero padding given per side: pad_lo rows / columns in front of index 0, pad_hi behind the last
+ * (each 0 | 1), Ho = (H + pad_lo + pad_hi - 3) / stride + 1.  CogVideoXDownsample3D is stride 2 with pad_lo = 0, pad_hi = 1.  out = conv(x) + bias? + res?.
+ * The K sum (9 Cin products) runs in chains of 64 products that start from zero and are added up in order: the rounding error of one long fp32
+ * chain grows with the square root of its length, and the encoder's outputs are held to 4 x the error of an fp32 CPU convolution.  So
+ * pad_lo = pad_hi = 1 agrees with vgpa_conv3x3_f32 to rounding, not bit for bit; like it, every output sums in the same order whatever N, H, W. */
+int32_t vgpa_conv3x3_pad_f32(const float* x, const float* w_packed, const float* bias, const float* res, float* out, int64_t N, int64_t H, int64_t W,
+                             int64_t Cin, int64_t Cout, int64_t stride, int32_t pad_lo, int32_t pad_hi, vgpa_stream_t stream);
+/* Layout change in front of conv_in: x [N,3,H,W] NCHW contiguous (in_dtype 0 fp32 | 1 bf16) -> out fp32 [N,H,W,16], channels 3..15 = 0, so that the
+ * stem runs on vgpa_conv3x3_f32 with a [3][3][16][Cout] weight whose rows 3..15 are zero.  out is 16-byte aligned. */
+int32_t vgpa_vae_input_f32(const void* x, int32_t in_dtype, float* out, int64_t N, int64_t H, int64_t W, vgpa_stream_t stream);
+/* GroupNorm statistics of x [N,HW,C] with G groups of C / G neighbouring channels: stats fp32 [N,G,2] = (mean, 1 / sqrt(biased variance + eps)).
+ * C a multiple of 4 and of G, at most 1024.  Two stages, both deterministic: per workgroup and channel (mean, M2) by Welford's update, merged over
+ * the workgroups and the group's channels with Chan's pairwise formula in a fixed order, all in fp64; no atomics and no sum of squares.  A
+ * sample's statistics do not depend on N. */
+size_t vgpa_groupnorm_stats_workspace_bytes(int64_t N, int64_t HW, int64_t C, int64_t G);
+int32_t vgpa_groupnorm_stats_f32(const float* x, float* stats, int64_t N, int64_t HW, int64_t C, int64_t G, float eps, void* workspace,
+                                 size_t ws_bytes, vgpa_stream_t stream);
+/* out = silu((x - mean) * rstd * gamma + beta) with the statistics above; gamma, beta [C]; x, out, gamma and beta 16-byte aligned.  Never in place. */
+int32_t vgpa_groupnorm_silu_f32(const float* x, const float* stats, const float* gamma, const float* beta, float* out, int64_t N, int64_t HW,
+                                int64_t C, int64_t G, vgpa_stream_t stream);
+/* DiagonalGaussianDistribution of moments fp32 [N,hw,2L] (mean | logvar on the channel axis): logvar is clamped to [-30, 20], std = exp(logvar / 2),
+ * sample = (mean + std * noise) * scale.  Outputs are [N,L,hw] (= [N,L,1,h,w]) in out_dtype 0 fp32 | 1 bf16, rounded once from fp32; each of sample,
+ * mean, logvar, std_out may be NULL (not all).  noise [N,L,hw] in out_dtype, or NULL for none (sample = mean * scale). */
+int32_t vgpa_vae_sample(const float* moments, const void* noise, float scale, void* sample, void* mean, void* logvar, void* std_out,
+                        int32_t out_dtype, int64_t N, int64_t hw, int64_t L, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,5 +1,9 @@
 // The exact-fp32 MFMA convolution core shared by csrc/vggt_heads.hip and csrc/dualdpt.hip: conv_kernel<.., MODE> and its launcher.
-//   CV_CONV      3x3 (stride 1 | 2, pad 1) or 1x1 convolution with the fused ReLU / bias / residual adds
+//   CV_CONV      3x3 (stride 1 | 2; pad 1, or one-sided: ConvArgs.pad) or 1x1 convolution with the fused ReLU / bias / residual adds
+//   CV_CONV_CHUNKED  the same convolution with its K sum cut into runs of CV_CHUNK_ITERS * 16 products: every run starts from zero and is added to a
+//                second accumulator when it ends.  One chain of n fp32 additions carries a rounding error that grows like sqrt(n) times the size of the
+//                partial sums; n / T short chains plus one chain over their n / T results grow like sqrt(T + n / T) instead -- at the VAE encoder's
+//                9 * 512 products a sixth of the single chain's error, for one vector add per accumulator register every CV_CHUNK_ITERS iterations
 //   CV_TAIL      the end of vggt's DPTHead: bilinear loader (+ embedding), epilogue bias + ReLU, 1x1 conv 32 -> od, activate_head
 //   CV_AUX_TAIL  the end of DA3's auxiliary branch (dualdpt.py:250-258): the loader reads the map as it is (+ embedding, zero padding), the epilogue
 //                is bias, LayerNorm over the 32 hidden channels of the pixel, ReLU, 1x1 conv 32 -> od, linear preds and conf = 1 + exp
@@ -15,6 +19,8 @@
 #define CV_CONV 0
 #define CV_TAIL 1
 #define CV_AUX_TAIL 2
+#define CV_CONV_CHUNKED 3
+#define CV_CHUNK_ITERS 4
 #define CV_THREADS 256
 #define CV_BM 128
 #define CV_KC 16
@@ -30,6 +36,7 @@ struct ConvArgs {
     const float* res2;   // [N,Ho,Wo,Cout] | NULL
     float* out;          // [N,Ho,Wo,Cout]
     int N, H, W, Ho, Wo, Cin, Cout, ksize, stride, flags;
+    int pad;             // zero padding in front of row / column 0 (ksize / 2 for the centred window); past the last one the bounds test pads as far as the window reaches
     int64_t M;
     // CV_TAIL and CV_AUX_TAIL only
     const float* xtab;   // [Wo, Cin/2] | NULL
@@ -90,7 +97,7 @@ __device__ __forceinline__ float4 sample4(const float* __restrict__ base, int h,
 
 template <int WM, int WN, int TM, int TN, int MODE>
 __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
-    constexpr bool TAIL = MODE != CV_CONV;                                  // either tail: 32 hidden channels, the epilogue goes through LDS
+    constexpr bool TAIL = MODE == CV_TAIL || MODE == CV_AUX_TAIL;                               // either tail: 32 hidden channels, the epilogue goes through LDS
     constexpr int BN = WN * TN * 32;
     constexpr int BS = (BN % 64 == 0) ? BN + 32 : BN + 64;
     constexpr int NB = (CV_KC * BN / 4 + CV_THREADS - 1) / CV_THREADS;      // float4 of the weight tile per thread
@@ -118,7 +125,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
         pn = (int)(p / ((int64_t)a.Wo * a.Ho));
     }
     const float* xn = a.x + (size_t)pn * a.H * a.W * a.Cin;
-    const int pad = a.ksize >> 1;
+    const int pad = a.pad;
     const int cchunks = a.Cin / CV_KC, iters = a.ksize * a.ksize * cchunks;
 
     float4 ra[2], rb[NB];
@@ -188,6 +195,16 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
+    [[maybe_unused]] f32x16_t tot[TM][TN];                                  // CV_CONV_CHUNKED: the sum of the finished runs
+    if constexpr (MODE == CV_CONV_CHUNKED) {
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int j = 0; j < TN; ++j)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tot[i][j][r] = 0.f;
+    }
+
     fetch(0);
     stash();
     __syncthreads();
@@ -207,6 +224,20 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
         }
+        if constexpr (MODE == CV_CONV_CHUNKED) {
+            const bool last = it + 1 == iters;
+            if ((it & (CV_CHUNK_ITERS - 1)) == CV_CHUNK_ITERS - 1 || last) {
+#pragma unroll
+                for (int i = 0; i < TM; ++i)
+#pragma unroll
+                    for (int j = 0; j < TN; ++j)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            tot[i][j][r] += acc[i][j][r];
+                            acc[i][j][r] = last ? tot[i][j][r] : 0.f;          // the epilogue reads acc
+                        }
+            }
+        }
         __syncthreads();
         if (it + 1 < iters) {
             stash();
@@ -215,7 +246,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
     }
 
     // accumulator element r of lane l: channel column l & 31, pixel row (r & 3) + 8 * (r >> 2) + 4 * (l >> 5)
-    if constexpr (MODE == CV_CONV) {
+    if constexpr (!TAIL) {
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int co = n0 + (wn * TN + j) * 32 + l31;
@@ -306,7 +337,7 @@ static int32_t tail_args(ConvArgs& a, const float* x, const float* xtab, const f
     if (h > (1 << 20) || w > (1 << 20) || H > (1 << 20) || W > (1 << 20) || C > (1 << 20)) return VGPA_ERR_INVALID;
     if (!aligned16(x) || !aligned16(w1_packed) || !aligned16(xtab) || !aligned16(ytab)) return VGPA_ERR_INVALID;
     a.x = x; a.w = w1_packed; a.bias = b1; a.xtab = xtab; a.ytab = ytab; a.w2 = w2; a.b2 = b2; a.preds = preds; a.conf = conf;
-    a.N = (int)N; a.H = (int)h; a.W = (int)w; a.Ho = (int)H; a.Wo = (int)W; a.Cin = (int)C; a.Cout = 32; a.ksize = 3; a.stride = 1;
+    a.N = (int)N; a.H = (int)h; a.W = (int)w; a.Ho = (int)H; a.Wo = (int)W; a.Cin = (int)C; a.Cout = 32; a.ksize = 3; a.stride = 1; a.pad = 1;
     a.od = od;
     a.M = N * H * W;
     return VGPA_OK;
@@ -316,14 +347,14 @@ template <int MODE>
 static int32_t conv_launch(const ConvArgs& a, hipStream_t stream) {
     const int64_t mb = (a.M + CV_BM - 1) / CV_BM;
     if (mb <= 0 || mb > 0x7fffffffLL) return VGPA_ERR_INVALID;
-    if constexpr (MODE != CV_CONV) {
+    if constexpr (MODE == CV_TAIL || MODE == CV_AUX_TAIL) {
         VGPA_LAUNCH((conv_kernel<4, 1, 1, 1, MODE>), dim3((unsigned)mb, 1), dim3(CV_THREADS), 0, stream, a);
     } else if (a.Cout >= 128) {
-        VGPA_LAUNCH((conv_kernel<2, 2, 2, 2, CV_CONV>), dim3((unsigned)mb, (unsigned)((a.Cout + 127) / 128)), dim3(CV_THREADS), 0, stream, a);
+        VGPA_LAUNCH((conv_kernel<2, 2, 2, 2, MODE>), dim3((unsigned)mb, (unsigned)((a.Cout + 127) / 128)), dim3(CV_THREADS), 0, stream, a);
     } else if (a.Cout > 32) {
-        VGPA_LAUNCH((conv_kernel<2, 2, 2, 1, CV_CONV>), dim3((unsigned)mb, (unsigned)((a.Cout + 63) / 64)), dim3(CV_THREADS), 0, stream, a);
+        VGPA_LAUNCH((conv_kernel<2, 2, 2, 1, MODE>), dim3((unsigned)mb, (unsigned)((a.Cout + 63) / 64)), dim3(CV_THREADS), 0, stream, a);
     } else {
-        VGPA_LAUNCH((conv_kernel<4, 1, 1, 1, CV_CONV>), dim3((unsigned)mb, 1), dim3(CV_THREADS), 0, stream, a);
+        VGPA_LAUNCH((conv_kernel<4, 1, 1, 1, MODE>), dim3((unsigned)mb, 1), dim3(CV_THREADS), 0, stream, a);
     }
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;

@@ -1,8 +1,10 @@
 // VGGT prediction heads (vggt/heads/dpt_head.py, camera_head.py), the part that is not torch plumbing.  Everything fp32 in, fp32 out,
 // channels-last (NHWC), forward only:
-//   conv_kernel<.., CV_CONV>        3x3 (stride 1 | 2, pad 1) or 1x1 convolution as an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32:
+//   conv_kernel<.., CV_CONV>        3x3 (stride 1 | 2, pad 1, or 0 | 1 in front and 0 | 1 behind) or 1x1 convolution as an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32:
 //                                   a k-ordered fmaf chain, only the summation order differs from torch's conv2d), with the fused pieces a
 //                                   ResidualConvUnit / FeatureFusionBlock needs: out = conv(relu?(x)) + bias? + relu?(res)? + res2?
+//   conv_kernel<.., CV_CONV_CHUNKED> the convolution of the CogVideoX VAE encoder (vgpa_conv3x3_pad_f32): padding per side, and the K sum in short runs
+//                                   (conv_mfma.h), because its outputs are held to a bound that one chain of 9 * 512 fp32 additions does not meet
 //   conv_kernel<.., CV_TAIL>        the end of DPTHead._forward_impl (dpt_head.py:229-247) in one launch on the same core: the loader samples the
 //                                   [N,h,w,C] map bilinearly (align_corners=True) at the (H,W) grid and adds the 0.1-scaled UV positional
 //                                   embedding from two separable tables; the epilogue is bias + ReLU, the 1x1 conv 32 -> output_dim, activate_head.
@@ -86,8 +88,9 @@ __global__ __launch_bounds__(AT_THREADS) void attn_small_kernel(const float* __r
     }
 }
 
+template <int MODE>
 static int32_t conv_entry(const float* x, const float* w, const float* bias, const float* res, const float* res2, float* out, int64_t N, int64_t H,
-                          int64_t W, int64_t Cin, int64_t Cout, int ksize, int64_t stride, int32_t flags, hipStream_t stream) {
+                          int64_t W, int64_t Cin, int64_t Cout, int ksize, int64_t stride, int pad_lo, int pad_hi, int32_t flags, hipStream_t stream) {
     if (!x || !w || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
     if ((stride != 1 && stride != 2) || (flags & ~(CV_RELU_IN | CV_RELU_RES)) || H > (1 << 30) || W > (1 << 30) || Cin > (1 << 20) || Cout > (1 << 20))
         return VGPA_ERR_INVALID;
@@ -95,22 +98,30 @@ static int32_t conv_entry(const float* x, const float* w, const float* bias, con
     ConvArgs a = {};
     a.x = x; a.w = w; a.bias = bias; a.res = res; a.res2 = res2; a.out = out;
     a.N = (int)N; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout; a.ksize = ksize; a.stride = (int)stride; a.flags = flags;
-    a.Ho = ksize == 3 ? (int)((H - 1) / stride + 1) : (int)H;
-    a.Wo = ksize == 3 ? (int)((W - 1) / stride + 1) : (int)W;
+    a.pad = pad_lo;
+    if (H + pad_lo + pad_hi < ksize || W + pad_lo + pad_hi < ksize) return VGPA_ERR_INVALID;
+    a.Ho = (int)((H + pad_lo + pad_hi - ksize) / stride + 1);          // the centred 3x3 (pad 1 | 1): (H - 1) / stride + 1; the 1x1: H
+    a.Wo = (int)((W + pad_lo + pad_hi - ksize) / stride + 1);
     a.M = N * a.Ho * a.Wo;
-    return conv_launch<CV_CONV>(a, stream);
+    return conv_launch<MODE>(a, stream);
 }
 
 extern "C" {
 
 int32_t vgpa_conv3x3_f32(const float* x, const float* w_packed, const float* bias, const float* res, const float* res2, float* out, int64_t N,
                          int64_t H, int64_t W, int64_t Cin, int64_t Cout, int64_t stride, int32_t flags, hipStream_t stream) {
-    return conv_entry(x, w_packed, bias, res, res2, out, N, H, W, Cin, Cout, 3, stride, flags, stream);
+    return conv_entry<CV_CONV>(x, w_packed, bias, res, res2, out, N, H, W, Cin, Cout, 3, stride, 1, 1, flags, stream);
 }
 
 int32_t vgpa_conv1x1_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t M, int64_t Cin, int64_t Cout,
                          hipStream_t stream) {
-    return conv_entry(x, w_packed, bias, nullptr, nullptr, out, 1, 1, M, Cin, Cout, 1, 1, 0, stream);
+    return conv_entry<CV_CONV>(x, w_packed, bias, nullptr, nullptr, out, 1, 1, M, Cin, Cout, 1, 1, 0, 0, 0, stream);
+}
+
+int32_t vgpa_conv3x3_pad_f32(const float* x, const float* w_packed, const float* bias, const float* res, float* out, int64_t N, int64_t H, int64_t W,
+                             int64_t Cin, int64_t Cout, int64_t stride, int32_t pad_lo, int32_t pad_hi, hipStream_t stream) {
+    if (pad_lo < 0 || pad_lo > 1 || pad_hi < 0 || pad_hi > 1) return VGPA_ERR_INVALID;
+    return conv_entry<CV_CONV_CHUNKED>(x, w_packed, bias, res, nullptr, out, N, H, W, Cin, Cout, 3, stride, pad_lo, pad_hi, 0, stream);
 }
 
 int32_t vgpa_dpt_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* w2,

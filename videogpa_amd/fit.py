@@ -99,7 +99,7 @@ def validate(trainer, dataset, val_idx, cfg, rank=0, world=1, collate=collate_pa
     return {"val/loss": a[0] / n, "val/reward_margin": a[1] / n, "val/reward_accuracy": a[2] / n}
 
 
-def fit(config: Dict[str, Any], transformer=None, dataset: Optional[DPODataset] = None, log=print, image_encoder=None, model: str = "cogvideox"):
+def fit(config: Dict[str, Any], transformer=None, dataset: Optional[DPODataset] = None, log=print, image_encoder=None, model: str = "cogvideox", vae=None):
     """model = "cogvideox" (CogVideoXDPOTrainer over the paired [B,2,F,C,H,W] layout) or "wan" (WanDPOTrainer over the reference's own batch keys
     x_win / x_lose [B,C,F,H,W], prompt_emb, image_latent: train/Wan2.2-TI2V-5B/03_train.py:309-387)."""
     if model not in ("cogvideox", "wan"):
@@ -128,7 +128,7 @@ def fit(config: Dict[str, Any], transformer=None, dataset: Optional[DPODataset] 
             raise ValueError("fit(model='wan') needs the denoiser (videogpa_amd.wan_model.WanModel or a module with its call convention)")
         trainer = WanDPOTrainer(cfg, transformer).cuda()
     else:
-        trainer = CogVideoXDPOTrainer(cfg, transformer=transformer, image_encoder=image_encoder).cuda()
+        trainer = CogVideoXDPOTrainer(cfg, transformer=transformer, image_encoder=image_encoder, vae=vae).cuda()
     trainer.train()
     engine = DPOEngine(trainer)
     pos = {"epoch": 0, "batch": 0}

@@ -1651,6 +1651,96 @@ def lpips_layer_f32(f0, f1, w, relu=False, total=None, accumulate=False, out=Non
     return out
 
 
+# ---- CogVideoX VAE encoder around the convolutions (csrc/vae.hip): fp32, channels-last, forward only ---------------------------------------
+def _dtype_code(dtype, name):
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise RuntimeError(f"{name}: float32 or bfloat16, got {dtype}")
+    return 1 if dtype == torch.bfloat16 else 0
+
+
+def conv3x3_pad_f32(x, w_packed, bias=None, res=None, stride=1, pad_lo=1, pad_hi=1):
+    """x [N,H,W,Cin] -> conv3x3(x, stride) + bias? + res? with `pad_lo` zero rows / columns in front and `pad_hi` behind (each 0 or 1):
+    [N,Ho,Wo,Cout], Ho = (H + pad_lo + pad_hi - 3) // stride + 1.  CogVideoXDownsample3D is stride 2, pad_lo 0, pad_hi 1.  The convolution of the
+    VAE encoder: the sum over the 9 Cin products runs in chains of 64 that are added up afterwards (csrc/conv_mfma.h, CV_CONV_CHUNKED), so its rounding
+    error is a fraction of conv3x3_f32's single chain at the same speed class; the two agree to that rounding, not bit for bit."""
+    _heads_in(x, w_packed, bias, res)
+    N, H, W, Cin = x.shape
+    Cout = w_packed.shape[-1]
+    if tuple(w_packed.shape) != (3, 3, Cin, Cout) or Cin % 16 or Cout % 16:
+        raise RuntimeError(f"conv3x3_pad_f32: weight {tuple(w_packed.shape)} does not fit input channels {Cin} (multiples of 16)")
+    if stride not in (1, 2) or pad_lo not in (0, 1) or pad_hi not in (0, 1) or min(H, W) + pad_lo + pad_hi < 3:
+        raise RuntimeError(f"conv3x3_pad_f32: stride {stride}, padding ({pad_lo}, {pad_hi}) on a {H} x {W} map is not supported")
+    Ho, Wo = (H + pad_lo + pad_hi - 3) // stride + 1, (W + pad_lo + pad_hi - 3) // stride + 1
+    out = torch.empty(N, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
+    if res is not None and res.shape != out.shape:
+        raise RuntimeError("conv3x3_pad_f32: residual shape differs from the output's")
+    _timed("conv3x3_pad_f32", 2.0 * out.numel() * 9 * Cin,
+           lambda: _lib.call("vgpa_conv3x3_pad_f32", x, w_packed, bias, res, out, N, H, W, Cin, Cout, stride, pad_lo, pad_hi, _stream()))
+    return out
+
+
+def vae_input_f32(x):
+    """x [N,3,H,W] (fp32 or bf16) -> fp32 [N,H,W,16], channels 3..15 zero: the input of the 16-channel form of the 3-channel stem"""
+    _req(x)
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError(f"vae_input_f32: expected [N,3,H,W], got {tuple(x.shape)}")
+    N, _, H, W = x.shape
+    out = torch.empty(N, H, W, 16, device=x.device, dtype=torch.float32)
+    _timed("vae_input_f32", float(x.numel() * x.element_size() + 4 * out.numel()),
+           lambda: _lib.call("vgpa_vae_input_f32", x, _dtype_code(x.dtype, "vae_input_f32"), out, N, H, W, _stream()), "byte")
+    return out
+
+
+def groupnorm_stats_f32(x, groups, eps):
+    """x [N,...,C] channels-last -> fp32 [N,groups,2] = (mean, rstd) of every (sample, group of C / groups neighbouring channels)"""
+    _heads_in(x)
+    N, C = x.shape[0], x.shape[-1]
+    HW = x.numel() // (N * C)
+    if C % 4 or C % groups or C > 1024:
+        raise RuntimeError(f"groupnorm_stats_f32: {C} channels in {groups} groups is not supported (C a multiple of 4 and of the groups, <= 1024)")
+    stats = torch.empty(N, groups, 2, device=x.device, dtype=torch.float32)
+    ws_bytes = _lib.query("vgpa_groupnorm_stats_workspace_bytes", N, HW, C, groups)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
+    _timed("groupnorm_stats_f32", 4.0 * x.numel(),
+           lambda: _lib.call("vgpa_groupnorm_stats_f32", x, stats, N, HW, C, groups, float(eps), ws, ws_bytes, _stream()), "byte")
+    return stats
+
+
+def groupnorm_silu_f32(x, gamma, beta, groups, eps, stats=None):
+    """silu(F.group_norm(x, groups, gamma, beta, eps)) of x [N,...,C] channels-last, same shape; `stats` from groupnorm_stats_f32, computed when None"""
+    _heads_in(x, gamma, beta, stats)
+    N, C = x.shape[0], x.shape[-1]
+    if gamma.numel() != C or beta.numel() != C:
+        raise RuntimeError(f"groupnorm_silu_f32: gamma / beta do not hold {C} values")
+    if stats is None:
+        stats = groupnorm_stats_f32(x, groups, eps)
+    elif tuple(stats.shape) != (N, groups, 2):
+        raise RuntimeError(f"groupnorm_silu_f32: `stats` must be [{N},{groups},2]")
+    out = torch.empty_like(x)
+    _timed("groupnorm_silu_f32", 8.0 * x.numel(),
+           lambda: _lib.call("vgpa_groupnorm_silu_f32", x, stats, gamma, beta, out, N, x.numel() // (N * C), C, groups, _stream()), "byte")
+    return out
+
+
+def vae_sample(moments, noise=None, scale=1.0, dtype=torch.float32, want=("sample",)):
+    """moments fp32 [N,h,w,2L] -> dict of the requested [N,L,1,h,w] tensors in `dtype`: "mean", "logvar" (clamped to [-30, 20]), "std" = exp(logvar / 2),
+    "sample" = (mean + std * noise) * scale with noise [N,L,1,h,w] in `dtype` (None: no noise)"""
+    _heads_in(moments)
+    N, h, w, L2 = moments.shape
+    L = L2 // 2
+    if L2 % 2 or not want or any(k not in ("sample", "mean", "logvar", "std") for k in want):
+        raise RuntimeError(f"vae_sample: moments {tuple(moments.shape)}, outputs {want!r}")
+    if noise is not None:
+        _req(noise, dtype)
+        if tuple(noise.shape) != (N, L, 1, h, w):
+            raise RuntimeError(f"vae_sample: noise {tuple(noise.shape)} is not [{N},{L},1,{h},{w}]")
+    out = {k: torch.empty(N, L, 1, h, w, device=moments.device, dtype=dtype) for k in want}
+    _timed("vae_sample", 4.0 * moments.numel(),
+           lambda: _lib.call("vgpa_vae_sample", moments, noise, float(scale), out.get("sample"), out.get("mean"), out.get("logvar"), out.get("std"),
+                             _dtype_code(dtype, "vae_sample"), N, h * w, L, _stream()), "byte")
+    return out
+
+
 # ---- Depth Anything 3's backbone between its blocks, and its camera decoding (csrc/da3.hip): fp32, forward only ---------------------------
 DA3_REF_VIEW_STRATEGIES = {"first": 0, "middle": 1, "saddle_balanced": 2, "saddle_sim_range": 3}
 

@@ -42,6 +42,7 @@ DEFAULT_CONFIG: Dict[str, Any] = {
     "log_every_n_steps": 10,
     "fp8_ffn": False,                         # opt-in: the frozen feed-forward on OCP-e4m3 operands (CogVideoXTransformer3DModel.enable_fp8); the reference runs it in bf16
     "tuned_gemms": True,                      # pick the hipBLASLt solutions of videogpa_amd/tuned/ (ops.use_tuned_gemms); False = the library's default heuristic
+    "enable_slicing": True, "enable_tiling": True,      # of the I2V trainer's `vae` (train/CogVideoX-I2V-5B/03_train.py:78-79,96-97); nothing without one
     "seed": 0,                                # (t, eps) stream = seed + rank: every rank draws its own
 }
 
@@ -69,14 +70,25 @@ def variant_config(variant: str, **overrides) -> Dict[str, Any]:
 
 class CogVideoXDPOTrainer(nn.Module):
     def __init__(self, config: Dict[str, Any], transformer: Optional[nn.Module] = None, scheduler=None, separate_ref: bool = False,
-                 image_encoder=None):
-        """image_encoder: I2V only -- callable `[B,3,1,H,W] image in the dataset's value range -> [B,C_lat,1,h,w]` standing
-        for `vae.encode(...).latent_dist.sample() * vae.config.scaling_factor` (train/CogVideoX-I2V-5B/03_train.py:124-125);
-        the VAE itself is a third-party network outside this path."""
+                 image_encoder=None, vae=None):
+        """I2V only.  vae: an `AutoencoderKLCogVideoX` (videogpa_amd.vae, or any object with its `encode` / `config` / `dtype`); the conditioning image
+        is then encoded inside the step as the reference does, `vae.encode(x.to(vae.dtype)).latent_dist.sample() * vae.config.scaling_factor`
+        (train/CogVideoX-I2V-5B/03_train.py:124-125), and the config keys `enable_slicing` / `enable_tiling` switch the VAE's modes (:94-97).
+        image_encoder: a callable `[B,3,1,H,W] image in the dataset's value range -> [B,C_lat,1,h,w]` standing for that expression; it wins
+        over `vae` when both are given."""
         super().__init__()
         cfg = dict(DEFAULT_CONFIG)
         cfg.update(config)
         self.config = cfg
+        self.vae = vae
+        if vae is not None:
+            vae.requires_grad_(False)          # frozen, as the reference builds it (:93)
+            if cfg.get("enable_slicing"):
+                vae.enable_slicing()
+            if cfg.get("enable_tiling"):
+                vae.enable_tiling()
+            if image_encoder is None:
+                image_encoder = lambda x: vae.encode(x.to(vae.dtype)).latent_dist.sample() * vae.config.scaling_factor      # noqa: E731
         self.image_encoder = image_encoder
         local_model = isinstance(cfg.get("model_path"), str) and os.path.isdir(cfg["model_path"])
         if transformer is None:
@@ -274,7 +286,7 @@ class CogVideoXDPOTrainer(nn.Module):
     def _i2v_condition(self, batch, x_pair):
         """Conditioning channels of the I2V model (train/CogVideoX-I2V-5B/03_train.py:119-130): batch['image_emb'] [B,3,h,w]
         (what DPODataset emits from 02_encode's 'image_embeds') is resized to the pixel size of the latents (nearest, the
-        F.interpolate default, :123), encoded by the caller-supplied `image_encoder` (:124-125), zero-padded to F frames
+        F.interpolate default, :123), encoded by the `vae` or the caller-supplied `image_encoder` (:124-125), zero-padded to F frames
         (:127-128); without an image the condition is zeros (:130).  A pre-encoded batch['image_latent'] is also accepted."""
         cfg = self._base_config()
         B, _, Fr, C, H, W = x_pair.shape
@@ -288,8 +300,8 @@ class CogVideoXDPOTrainer(nn.Module):
         il = batch.get("image_latent")
         if il is None and batch.get("image_emb") is not None:
             if self.image_encoder is None:
-                raise RuntimeError("batch['image_emb'] needs CogVideoXDPOTrainer(image_encoder=...): the callable standing for "
-                                   "vae.encode(x).latent_dist.sample() * scaling_factor (train/CogVideoX-I2V-5B/03_train.py:124-125)")
+                raise RuntimeError("batch['image_emb'] needs CogVideoXDPOTrainer(vae=...) or (image_encoder=...): the VAE, or the callable standing "
+                                   "for vae.encode(x).latent_dist.sample() * scaling_factor (train/CogVideoX-I2V-5B/03_train.py:124-125)")
             with torch.no_grad():
                 img = torch.nn.functional.interpolate(batch["image_emb"].to(x_pair.device), size=(H * 8, W * 8))
                 il = self.image_encoder(img.unsqueeze(2))                       # [B,C,1,h,w]

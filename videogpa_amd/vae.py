@@ -1,0 +1,364 @@
+"""CogVideoX's VAE, encoder side, on the device: the drop-in for `diffusers.AutoencoderKLCogVideoX` where the reference's I2V trainer uses it --
+`vae.encode(image[:, :, None]).latent_dist.sample() * vae.config.scaling_factor` inside every training step
+(train/CogVideoX-I2V-5B/03_train.py:94-97,121-128).
+
+    from videogpa_amd.vae import AutoencoderKLCogVideoX
+    vae = AutoencoderKLCogVideoX.from_pretrained(model_path, subfolder="vae", torch_dtype=torch.bfloat16).cuda()
+    vae.enable_slicing(); vae.enable_tiling()
+    z = vae.encode(x).latent_dist.sample() * vae.config.scaling_factor      # x [B,3,1,H,W] -> [B,16,1,H/8,W/8]
+
+ONE frame only: a causal 3-D convolution sees its only frame repeated in time, so each folds into a 2-D convolution whose weight is the sum of the
+temporal taps (in fp32, from the checkpoint's values), and the temporal pooling of the downsamplers is the identity.  `encode` of more frames
+(02_encode.py's offline video encode) and the decoder raise NotImplementedError.  Inference only, fp32 arithmetic, channels-last inside: the
+convolutions run on the exact-fp32 MFMA kernel of the VGGT heads (`ops.conv3x3_pad_f32`: its form with the padding given per side, for the
+downsampler, and the K sum in short runs, for the accuracy bound of tests/test_gpu_vae.py; `ops.conv1x1_f32` for the shortcuts), GroupNorm + SiLU, the 3-channel stem's layout change and the Gaussian epilogue on csrc/vae.hip.  See DESIGN.md section 5f.
+
+PARITY UNPINNED (diffusers is neither installed nor vendored): the network, its parameter names and the tiled-encode scheme are restated from
+diffusers' autoencoder_kl_cogvideox.py.  The loader is strict, so the first real checkpoint shows at once if a name here is wrong."""
+import json
+import os
+
+import torch
+import torch.nn as nn
+
+from . import ops
+from ._nn import _forward_only, _PackedCache
+from .transformer import _Config
+
+DEFAULT_CONFIG = dict(
+    in_channels=3, out_channels=3,
+    down_block_types=("CogVideoXDownBlock3D",) * 4, up_block_types=("CogVideoXUpBlock3D",) * 4,
+    block_out_channels=(128, 256, 256, 512), latent_channels=16, layers_per_block=3, act_fn="silu", norm_eps=1e-6, norm_num_groups=32,
+    temporal_compression_ratio=4, sample_height=480, sample_width=720, scaling_factor=0.7, shift_factor=None, latents_mean=None, latents_std=None,
+    force_upcast=True, use_quant_conv=False, use_post_quant_conv=False, invert_scale_latents=False)
+
+
+class _CausalConv3d(nn.Module):
+    """CogVideoXCausalConv3d: the parameters live in `.conv` (a Conv3d); spatial zero padding k // 2, the first frame repeated k - 1 times in front"""
+
+    def __init__(self, cin, cout, k=3):
+        super().__init__()
+        self.conv = nn.Conv3d(cin, cout, k)
+
+
+class _ResnetBlock3D(nn.Module):
+    def __init__(self, cin, cout, groups, eps):
+        super().__init__()
+        self.norm1 = nn.GroupNorm(groups, cin, eps=eps)
+        self.norm2 = nn.GroupNorm(groups, cout, eps=eps)
+        self.conv1 = _CausalConv3d(cin, cout)
+        self.conv2 = _CausalConv3d(cout, cout)
+        if cin != cout:
+            self.conv_shortcut = nn.Conv3d(cin, cout, 1)
+
+
+class _Downsample3D(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.conv = nn.Conv2d(c, c, 3, stride=2, padding=0)
+
+
+class _DownBlock3D(nn.Module):
+    def __init__(self, cin, cout, layers, groups, eps, downsample):
+        super().__init__()
+        self.resnets = nn.ModuleList([_ResnetBlock3D(cin if j == 0 else cout, cout, groups, eps) for j in range(layers)])
+        if downsample:
+            self.downsamplers = nn.ModuleList([_Downsample3D(cout)])
+
+
+class _MidBlock3D(nn.Module):
+    def __init__(self, c, groups, eps):
+        super().__init__()
+        self.resnets = nn.ModuleList([_ResnetBlock3D(c, c, groups, eps) for _ in range(2)])
+
+
+class _Encoder3D(nn.Module):
+    def __init__(self, cfg):
+        super().__init__()
+        chans, groups, eps = tuple(cfg.block_out_channels), cfg.norm_num_groups, cfg.norm_eps
+        self.conv_in = _CausalConv3d(cfg.in_channels, chans[0])
+        self.down_blocks = nn.ModuleList([
+            _DownBlock3D(chans[max(i - 1, 0)], c, cfg.layers_per_block, groups, eps, downsample=i < len(chans) - 1) for i, c in enumerate(chans)])
+        self.mid_block = _MidBlock3D(chans[-1], groups, eps)
+        self.norm_out = nn.GroupNorm(groups, chans[-1], eps=eps)
+        self.conv_out = _CausalConv3d(chans[-1], 2 * cfg.latent_channels)
+
+
+def _fold(conv):
+    """a causal Conv3d on one frame -> the packed 2-D weight [3,3,Cin,Cout]: the frame fills all kt temporal taps, so they add (fp32)"""
+    return ops.pack_conv_weight(conv.weight.detach().float().sum(dim=2))
+
+
+def _vec(p):
+    return p.detach().float().contiguous()
+
+
+def _pack_resnet(r):
+    """fp32 kernel-layout copies of a resnet's parameters: GroupNorm (gamma, beta), folded convolutions (weight, bias), the 1x1x1 shortcut as [Cin,Cout]"""
+    sc = None
+    if hasattr(r, "conv_shortcut"):
+        w = r.conv_shortcut.weight.detach().float()
+        sc = (w.reshape(w.shape[0], w.shape[1]).t().contiguous(), _vec(r.conv_shortcut.bias))
+    return dict(n1=(_vec(r.norm1.weight), _vec(r.norm1.bias)), n2=(_vec(r.norm2.weight), _vec(r.norm2.bias)),
+                c1=(_fold(r.conv1.conv), _vec(r.conv1.conv.bias)), c2=(_fold(r.conv2.conv), _vec(r.conv2.conv.bias)), sc=sc)
+
+
+def _resnet_forward(p, h, groups, eps):
+    """CogVideoXResnetBlock3D of the encoder (no time embedding, no spatial norm) on h [N,H,W,C]: norm1, SiLU, conv1, norm2, SiLU, conv2, plus the
+    input (through the shortcut convolution when the width changes), the add fused into conv2's epilogue"""
+    t = ops.conv3x3_pad_f32(ops.groupnorm_silu_f32(h, *p["n1"], groups, eps), *p["c1"])
+    t = ops.groupnorm_silu_f32(t, *p["n2"], groups, eps)
+    return ops.conv3x3_pad_f32(t, *p["c2"], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
+
+
+class DiagonalGaussianDistribution:
+    """diffusers' class of the same name over the encoder's moments (kept as fp32 [N,h,w,2L] channels-last): `mean`, `logvar` (clamped to [-30, 20]),
+    `std` = exp(logvar / 2), `mode()` and `sample(generator)` are [N,L,1,h,w] in the VAE's dtype, each rounded once from the fp32 value"""
+
+    def __init__(self, moments, dtype):
+        self._moments, self._dtype, self._cache = moments, dtype, {}
+
+    def _get(self, name):
+        if name not in self._cache:
+            self._cache.update(ops.vae_sample(self._moments, dtype=self._dtype, want=("mean", "logvar", "std")))
+        return self._cache[name]
+
+    mean = property(lambda self: self._get("mean"))
+    logvar = property(lambda self: self._get("logvar"))
+    std = property(lambda self: self._get("std"))
+
+    def mode(self):
+        return self.mean
+
+    def sample(self, generator=None):
+        """mean + std * randn, the noise drawn by torch.randn on the device in the VAE's dtype (a device generator reproduces it); formed in fp32 and
+        rounded once (upstream's result to the rounding of its bf16 intermediates)"""
+        N, h, w, L2 = self._moments.shape
+        noise = torch.randn((N, L2 // 2, 1, h, w), generator=generator, device=self._moments.device, dtype=self._dtype)
+        return ops.vae_sample(self._moments, noise=noise, dtype=self._dtype)["sample"]
+
+
+class AutoencoderKLOutput:
+    def __init__(self, latent_dist):
+        self.latent_dist = latent_dist
+
+
+class AutoencoderKLCogVideoX(nn.Module):
+    config_name = "config.json"
+    weights_name = "diffusion_pytorch_model.safetensors"
+
+    def __init__(self, **kw):
+        super().__init__()
+        cfg = _Config(DEFAULT_CONFIG)
+        cfg.update(kw)                                   # unknown keys are kept on .config (checkpoint configs carry _class_name, _diffusers_version, ...)
+        for k in ("block_out_channels", "down_block_types", "up_block_types"):
+            cfg[k] = tuple(cfg[k])
+        if cfg.use_quant_conv:
+            raise NotImplementedError("use_quant_conv=True is not implemented (no CogVideoX checkpoint sets it)")
+        if cfg.act_fn not in ("silu", "swish"):
+            raise NotImplementedError(f"act_fn={cfg.act_fn!r}: only SiLU runs on the device")
+        if cfg.in_channels != 3:
+            raise NotImplementedError(f"in_channels={cfg.in_channels}: the stem kernel takes 3-channel images")
+        bad = [c for c in cfg.block_out_channels if c % 32 or c > 1024] + ([] if (2 * cfg.latent_channels) % 16 == 0 else [2 * cfg.latent_channels])
+        if bad or any(c % cfg.norm_num_groups for c in cfg.block_out_channels):
+            raise NotImplementedError(f"block_out_channels {cfg.block_out_channels} / latent_channels {cfg.latent_channels} / norm_num_groups "
+                                      f"{cfg.norm_num_groups}: widths must be multiples of 32 (<= 1024) and of the groups, 2 * latent_channels of 16")
+        self.config = cfg
+        self.encoder = _Encoder3D(cfg)
+        self.use_slicing = self.use_tiling = False
+        self.tile_sample_min_height = cfg.sample_height // 2
+        self.tile_sample_min_width = cfg.sample_width // 2
+        down = 2 ** (len(cfg.block_out_channels) - 1)
+        self.tile_latent_min_height = int(self.tile_sample_min_height / down)
+        self.tile_latent_min_width = int(self.tile_sample_min_width / down)
+        self.tile_overlap_factor_height = 1 / 6
+        self.tile_overlap_factor_width = 1 / 5
+        self._packed = _PackedCache()
+
+    # ------------------------------------------------------------------ diffusers' switches
+    def enable_slicing(self):
+        """one sample per pass through the encoder (peak memory of one); no numerical effect: GroupNorm is per sample and every kernel's summation order
+        is independent of the batch"""
+        self.use_slicing = True
+
+    def disable_slicing(self):
+        self.use_slicing = False
+
+    def enable_tiling(self, tile_sample_min_height=None, tile_sample_min_width=None, tile_overlap_factor_height=None, tile_overlap_factor_width=None):
+        self.use_tiling = True
+        self.tile_sample_min_height = tile_sample_min_height or self.tile_sample_min_height
+        self.tile_sample_min_width = tile_sample_min_width or self.tile_sample_min_width
+        down = 2 ** (len(self.config.block_out_channels) - 1)
+        self.tile_latent_min_height = int(self.tile_sample_min_height / down)
+        self.tile_latent_min_width = int(self.tile_sample_min_width / down)
+        self.tile_overlap_factor_height = tile_overlap_factor_height or self.tile_overlap_factor_height
+        self.tile_overlap_factor_width = tile_overlap_factor_width or self.tile_overlap_factor_width
+
+    def disable_tiling(self):
+        self.use_tiling = False
+
+    @property
+    def dtype(self):
+        return next(self.parameters()).dtype
+
+    # ------------------------------------------------------------------ loading
+    @classmethod
+    def from_pretrained(cls, path, subfolder=None, torch_dtype=None, **kw):
+        """diffusers' on-disk layout from a LOCAL directory: <path>/<subfolder>/config.json + diffusion_pytorch_model.safetensors, or its shards
+        `diffusion_pytorch_model-0000i-of-0000n.safetensors` listed by `diffusion_pytorch_model.safetensors.index.json`.  `decoder.*` tensors are
+        skipped; a missing or unexpected `encoder.*` tensor, or one of another shape, is an error naming it.  torch_dtype=None keeps float32."""
+        from safetensors.torch import load_file
+        root = os.path.join(path, subfolder) if subfolder else path
+        if not os.path.isdir(root):
+            raise FileNotFoundError(f"AutoencoderKLCogVideoX.from_pretrained: {root!r} is not a local directory (there is no hub access on this path)")
+        with open(os.path.join(root, cls.config_name)) as f:
+            cfg = json.load(f)
+        index = os.path.join(root, cls.weights_name + ".index.json")
+        if os.path.isfile(index):
+            with open(index) as f:
+                files = sorted(set(json.load(f)["weight_map"].values()))
+        elif os.path.isfile(os.path.join(root, cls.weights_name)):
+            files = [cls.weights_name]
+        else:
+            raise FileNotFoundError(f"neither {cls.weights_name} nor its .index.json under {root}")
+        sd = {}
+        for fn in files:
+            sd.update(load_file(os.path.join(root, fn)))
+        model = cls(**{**cfg, **kw})
+        model.load_state_dict(sd)
+        if torch_dtype is not None:
+            model = model.to(torch_dtype)
+        model.eval()
+        return model
+
+    def load_state_dict(self, state_dict, strict=True, assign=False):
+        """strict on the encoder: `decoder.*` (not implemented here) is dropped, every other difference raises with the tensor's name"""
+        sd = {k: v for k, v in state_dict.items() if not k.startswith("decoder.")}
+        own = self.state_dict()
+        missing, unexpected = sorted(k for k in own if k not in sd), sorted(k for k in sd if k not in own)
+        wrong = sorted(f"{k}: checkpoint {tuple(sd[k].shape)}, model {tuple(own[k].shape)}" for k in sd if k in own and sd[k].shape != own[k].shape)
+        if strict and (missing or unexpected or wrong):
+            raise RuntimeError("AutoencoderKLCogVideoX.load_state_dict: " + "; ".join(
+                f"{what}: {', '.join(keys)}" for what, keys in (("missing", missing), ("unexpected", unexpected), ("shape mismatch", wrong)) if keys))
+        return super().load_state_dict(sd, strict=strict, assign=assign)
+
+    # ------------------------------------------------------------------ kernel-layout copies
+    def _resnets(self):
+        enc = self.encoder
+        return [r for b in enc.down_blocks for r in b.resnets] + list(enc.mid_block.resnets)
+
+    def packed(self):
+        """fp32 kernel-layout copies of every parameter (temporal taps folded, the stem padded to 16 input channels with zero rows), rebuilt when a
+        parameter changes or moves"""
+        enc = self.encoder
+
+        def make():
+            w_in = _fold(enc.conv_in.conv)
+            w_in = torch.cat([w_in, w_in.new_zeros(3, 3, 16 - w_in.shape[2], w_in.shape[3])], dim=2).contiguous()
+            out = {"conv_in": (w_in, _vec(enc.conv_in.conv.bias)), "conv_out": (_fold(enc.conv_out.conv), _vec(enc.conv_out.conv.bias)),
+                   "norm_out": (_vec(enc.norm_out.weight), _vec(enc.norm_out.bias)), "resnets": {}, "down": {}}
+            for r in self._resnets():
+                out["resnets"][id(r)] = _pack_resnet(r)
+            for b in enc.down_blocks:
+                if hasattr(b, "downsamplers"):
+                    c = b.downsamplers[0].conv
+                    out["down"][id(b)] = (ops.pack_conv_weight(c.weight), _vec(c.bias))
+            return out
+        return self._packed.get("all", list(self.parameters()), make)
+
+    # ------------------------------------------------------------------ forward
+    def _moments(self, x):
+        """x [N,3,H,W] in the module's dtype -> the encoder's output [N,H/8,W/8,2L] fp32 channels-last"""
+        P, G, eps = self.packed(), self.config.norm_num_groups, self.config.norm_eps
+        enc = self.encoder
+        h = ops.conv3x3_pad_f32(ops.vae_input_f32(x.contiguous()), *P["conv_in"])
+
+        def resnet(r, h):
+            return _resnet_forward(P["resnets"][id(r)], h, G, eps)
+
+        for b in enc.down_blocks:
+            for r in b.resnets:
+                h = resnet(r, h)
+            if hasattr(b, "downsamplers"):
+                if min(h.shape[1], h.shape[2]) < 2:
+                    raise RuntimeError(f"the image is too small: a {h.shape[1]} x {h.shape[2]} map reached a downsampler")
+                h = ops.conv3x3_pad_f32(h, *P["down"][id(b)], stride=2, pad_lo=0, pad_hi=1)      # temporal pooling: the identity on one frame
+        for r in enc.mid_block.resnets:
+            h = resnet(r, h)
+        return ops.conv3x3_pad_f32(ops.groupnorm_silu_f32(h, *P["norm_out"], G, eps), *P["conv_out"])
+
+    def tile_plan(self, height, width):
+        """The tile grid of diffusers' tiled_encode for a height x width image: (rows, cols) of (start, size) in pixels, the blend extents and the kept
+        tile size in latent pixels"""
+        fh, fw = self.tile_overlap_factor_height, self.tile_overlap_factor_width
+        stride_h, stride_w = int(self.tile_sample_min_height * (1 - fh)), int(self.tile_sample_min_width * (1 - fw))
+        blend_h, blend_w = int(self.tile_latent_min_height * fh), int(self.tile_latent_min_width * fw)
+        rows = [(i, min(self.tile_sample_min_height, height - i)) for i in range(0, height, stride_h)]
+        cols = [(j, min(self.tile_sample_min_width, width - j)) for j in range(0, width, stride_w)]
+        return dict(rows=rows, cols=cols, blend=(blend_h, blend_w), keep=(self.tile_latent_min_height - blend_h, self.tile_latent_min_width - blend_w))
+
+    def _tiled_moments(self, x):
+        plan = self.tile_plan(x.shape[2], x.shape[3])
+        rows, cols, (blend_h, blend_w), (keep_h, keep_w) = plan["rows"], plan["cols"], plan["blend"], plan["keep"]
+        N = x.shape[0]
+        by_shape = {}                                                   # tiles of one size share a pass through the encoder as a batch
+        for a, (i, th) in enumerate(rows):
+            for b, (j, tw) in enumerate(cols):
+                by_shape.setdefault((th, tw), []).append((a, b, i, j))
+        tiles = {}
+        for (th, tw), members in by_shape.items():
+            m = self._moments(torch.cat([x[:, :, i:i + th, j:j + tw] for _, _, i, j in members], dim=0))
+            for k, (a, b, _, _) in enumerate(members):
+                tiles[a, b] = m[k * N:(k + 1) * N]
+
+        def blend(prev, cur, extent, dim):                              # in place on `cur`, reading the neighbour's last rows / columns
+            extent = min(prev.shape[dim], cur.shape[dim], extent)
+            if extent > 0:
+                shape = [1, 1, 1, 1]
+                shape[dim] = extent
+                t = (torch.arange(extent, device=cur.device, dtype=torch.float32) / extent).reshape(shape)
+                head = cur.narrow(dim, 0, extent)
+                head.copy_(prev.narrow(dim, prev.shape[dim] - extent, extent) * (1 - t) + head * t)
+
+        out_rows = []
+        for a in range(len(rows)):
+            kept = []
+            for b in range(len(cols)):
+                if a > 0:
+                    blend(tiles[a - 1, b], tiles[a, b], blend_h, 1)
+                if b > 0:
+                    blend(tiles[a, b - 1], tiles[a, b], blend_w, 2)
+                kept.append(tiles[a, b][:, :keep_h, :keep_w])
+            out_rows.append(torch.cat(kept, dim=2))
+        return torch.cat(out_rows, dim=1).contiguous()
+
+    def _encode(self, x):
+        H, W = x.shape[2], x.shape[3]
+        if self.use_tiling and (W > self.tile_sample_min_width or H > self.tile_sample_min_height):
+            return self._tiled_moments(x)
+        return self._moments(x)
+
+    def encode(self, x, return_dict=True):
+        """x [B,3,1,H,W] -> AutoencoderKLOutput whose `.latent_dist` is the DiagonalGaussianDistribution of the [B,L,1,H/8,W/8] latent.  The input
+        is rounded to the module's dtype first (the reference's `.to(self.vae.dtype)`)."""
+        if x.dim() != 5 or x.shape[1] != 3:
+            raise RuntimeError(f"encode: expected [B,3,F,H,W], got {tuple(x.shape)}")
+        if x.shape[2] != 1:
+            raise NotImplementedError(f"encode of {x.shape[2]} frames: only the one-frame encode (the I2V conditioning image) runs on the device; "
+                                      "the video encode of 02_encode.py is offline data preparation and out of scope")
+        if not x.is_cuda:
+            raise RuntimeError("videogpa_amd ops need GPU tensors (no CPU fallback)")
+        _forward_only(self, x)
+        x = x.to(self.dtype)[:, :, 0]
+        if self.use_slicing and x.shape[0] > 1:
+            moments = torch.cat([self._encode(x[i:i + 1]) for i in range(x.shape[0])], dim=0)
+        else:
+            moments = self._encode(x)
+        dist = DiagonalGaussianDistribution(moments, self.dtype)
+        return AutoencoderKLOutput(dist) if return_dict else (dist,)
+
+    def decode(self, *a, **kw):
+        raise NotImplementedError("the CogVideoX VAE decoder is not implemented: this module is the encoder side only")
+
+    def forward(self, *a, **kw):
+        raise NotImplementedError("AutoencoderKLCogVideoX.forward (encode + decode) is not implemented: call .encode()")

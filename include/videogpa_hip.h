@@ -483,6 +483,23 @@ int32_t vgpa_dualdpt_aux_tail_f32(const float* x, const float* xtab, const float
  * pad_lo = pad_hi = 1 agrees with vgpa_conv3x3_f32 to rounding, not bit for bit; like it, every output sums in the same order whatever N, H, W. */
 int32_t vgpa_conv3x3_pad_f32(const float* x, const float* w_packed, const float* bias, const float* res, float* out, int64_t N, int64_t H, int64_t W,
                              int64_t Cin, int64_t Cout, int64_t stride, int32_t pad_lo, int32_t pad_hi, vgpa_stream_t stream);
+/* CogVideoXCausalConv3d over the frames of a chunk: x [N,T,H,W,Cin] -> out [N,T,H,W,Cout] = conv3x3x3(x) + bias? + res?, stride 1, spatial zero
+ * padding 1, w_packed [3][3][3][Cin][Cout] (kt, ky, kx).  Temporal tap kt of output frame t reads frame t + kt - 2.  The two frames in front of
+ * frame 0 are prev [N,2,H,W,Cin] (diffusers' conv_cache: the last two input frames of the chunk before); with prev NULL frame 0 stands in for
+ * both (the first-frame replication).  Cin, Cout multiples of 16; x, prev and w_packed 16-byte aligned; never in place.  The K sum (27 Cin products,
+ * tap-major) runs in the chains of 64 of vgpa_conv3x3_pad_f32.  CONTRACT: every output element sums the same products in the same order whatever
+ * N and T are and whether its earlier frames come from prev or from x, so one call over T frames equals any split into two calls bit for bit when
+ * the second gets the first's last two input frames as prev.  T = 1 without prev agrees with vgpa_conv3x3_pad_f32 on the tap-summed weight to
+ * rounding only. */
+int32_t vgpa_conv3x3x3_causal_f32(const float* x, const float* prev, const float* w_packed, const float* bias, const float* res, float* out, int64_t N,
+                                  int64_t T, int64_t H, int64_t W, int64_t Cin, int64_t Cout, vgpa_stream_t stream);
+/* CogVideoXDownsample3D in one launch: x [N,T,H,W,C] -> out [N,T',Ho,Wo,Cout], the stride-2 convolution of vgpa_conv3x3_pad_f32 with pad_lo = 0,
+ * pad_hi = 1 (Ho = (H - 2) / 2 + 1; H, W >= 2) of the temporally pooled frames, which the loader forms and never writes.  compress_time 0: T' = T,
+ * frame by frame.  compress_time 1: T' = (T + 1) / 2; output frame t' reads frames (2t', 2t' + 1) of an even T; of an odd T frame 0 alone for
+ * t' = 0 and frames (2t' - 1, 2t') after it; a pooled value is (a + b) * 0.5 in fp32.  Bit for bit the result of pooling so on the host and
+ * calling vgpa_conv3x3_pad_f32 on [N * T',H,W,C]. */
+int32_t vgpa_vae_downsample_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t N, int64_t T, int64_t H, int64_t W,
+                                int64_t C, int64_t Cout, int32_t compress_time, vgpa_stream_t stream);
 /* Layout change in front of conv_in: x [N,3,H,W] NCHW contiguous (in_dtype 0 fp32 | 1 bf16) -> out fp32 [N,H,W,16], channels 3..15 = 0, so that the
  * stem runs on vgpa_conv3x3_f32 with a [3][3][16][Cout] weight whose rows 3..15 are zero.  out is 16-byte aligned. */
 int32_t vgpa_vae_input_f32(const void* x, int32_t in_dtype, float* out, int64_t N, int64_t H, int64_t W, vgpa_stream_t stream);

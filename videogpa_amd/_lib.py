@@ -104,6 +104,8 @@ SIGNATURES = {
     "vgpa_da3_pose_decode": (I32, [P, I64, F32, F32, P, P, P]),
     "vgpa_dualdpt_aux_tail_f32": (I32, [P, P, P, P, P, P, P, F32, P, P, P, P, I64, I64, I64, I64, I32, P]),
     "vgpa_conv3x3_pad_f32": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, P]),
+    "vgpa_conv3x3x3_causal_f32": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, P]),
+    "vgpa_vae_downsample_f32": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),
     "vgpa_vae_input_f32": (I32, [P, I32, P, I64, I64, I64, P]),
     "vgpa_groupnorm_stats_workspace_bytes": (SZ, [I64, I64, I64, I64]),
     "vgpa_groupnorm_stats_f32": (I32, [P, P, I64, I64, I64, I64, F32, P, SZ, P]),

@@ -4,6 +4,13 @@
 //                second accumulator when it ends.  One chain of n fp32 additions carries a rounding error that grows like sqrt(n) times the size of the
 //                partial sums; n / T short chains plus one chain over their n / T results grow like sqrt(T + n / T) instead -- at the VAE encoder's
 //                9 * 512 products a sixth of the single chain's error, for one vector add per accumulator register every CV_CHUNK_ITERS iterations
+//   CV_CONV3D    the causal 3x3x3 convolution of the CogVideoX VAE encoder over frames (vgpa_conv3x3x3_causal_f32): x [N,T,H,W,Cin], flat
+//                M = N * T * H * W, the pixel decoded once to (n, t, y, x), K = 27 * Cin walked tap-major (kt, ky, kx) with the K sum in the runs of
+//                CV_CONV_CHUNKED.  Temporal tap kt of output frame t reads frame t + kt - 2; a frame in front of frame 0 comes from
+//                ConvArgs.prev [N,2,H,W,Cin] (the last two frames of the chunk before) or, without one, is frame 0 again.  Only the loader's
+//                source address depends on N, T and prev: an output sums the same products in the same order wherever its frames lie
+//   CV_POOL_DOWN CogVideoXDownsample3D with its temporal pooling (vgpa_vae_downsample_f32): CV_CONV_CHUNKED on [N * T',H,W,C] whose loader reads
+//                frame t' as (a + b) * 0.5 of two frames of x [N,Tin,H,W,C] (or one frame as it is), so the pooled tensor is never written
 //   CV_TAIL      the end of vggt's DPTHead: bilinear loader (+ embedding), epilogue bias + ReLU, 1x1 conv 32 -> od, activate_head
 //   CV_AUX_TAIL  the end of DA3's auxiliary branch (dualdpt.py:250-258): the loader reads the map as it is (+ embedding, zero padding), the epilogue
 //                is bias, LayerNorm over the 32 hidden channels of the pixel, ReLU, 1x1 conv 32 -> od, linear preds and conf = 1 + exp
@@ -20,6 +27,8 @@
 #define CV_TAIL 1
 #define CV_AUX_TAIL 2
 #define CV_CONV_CHUNKED 3
+#define CV_CONV3D 4
+#define CV_POOL_DOWN 5
 #define CV_CHUNK_ITERS 4
 #define CV_THREADS 256
 #define CV_BM 128
@@ -51,6 +60,10 @@ struct ConvArgs {
     const float* ln_w;   // [32]
     const float* ln_b;   // [32]
     float eps;
+    // CV_CONV3D and CV_POOL_DOWN only
+    const float* prev;   // CV_CONV3D: [N,2,H,W,Cin] | NULL
+    int T;               // frames of the output
+    int Tin;             // CV_POOL_DOWN: frames of x (T = (Tin + 1) / 2)
 };
 
 __device__ __forceinline__ float4 f4_fma(float s, float4 a, float4 acc) {
@@ -98,6 +111,7 @@ __device__ __forceinline__ float4 sample4(const float* __restrict__ base, int h,
 template <int WM, int WN, int TM, int TN, int MODE>
 __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
     constexpr bool TAIL = MODE == CV_TAIL || MODE == CV_AUX_TAIL;                               // either tail: 32 hidden channels, the epilogue goes through LDS
+    constexpr bool CHUNKED = MODE == CV_CONV_CHUNKED || MODE == CV_CONV3D || MODE == CV_POOL_DOWN;  // the K sum in runs of CV_CHUNK_ITERS iterations
     constexpr int BN = WN * TN * 32;
     constexpr int BS = (BN % 64 == 0) ? BN + 32 : BN + 64;
     constexpr int NB = (CV_KC * BN / 4 + CV_THREADS - 1) / CV_THREADS;      // float4 of the weight tile per thread
@@ -124,9 +138,23 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
         py = (int)((p / a.Wo) % a.Ho);
         pn = (int)(p / ((int64_t)a.Wo * a.Ho));
     }
+    [[maybe_unused]] int pt = 0;                                            // CV_CONV3D: the output frame; pn above is then (n, t) in one
+    [[maybe_unused]] const float* xb = nullptr;                             // CV_POOL_DOWN: the second frame of the pooled pair (== xn: one frame as it is)
+    if constexpr (MODE == CV_CONV3D) {
+        pt = pn % a.T;
+        pn /= a.T;
+    }
     const float* xn = a.x + (size_t)pn * a.H * a.W * a.Cin;
+    if constexpr (MODE == CV_CONV3D) xn = a.x + (size_t)pn * a.T * a.H * a.W * a.Cin;         // frame 0 of the sample
+    if constexpr (MODE == CV_POOL_DOWN) {
+        const int tp = pn % a.T, n = pn / a.T;
+        const int f1 = (a.Tin & 1) ? 2 * tp : 2 * tp + 1, f0 = f1 > 0 ? f1 - 1 : 0;               // odd count: frame 0 alone, then (2t' - 1, 2t')
+        const size_t fs = (size_t)a.H * a.W * a.Cin;
+        xn = a.x + ((size_t)n * a.Tin + f0) * fs;
+        xb = a.x + ((size_t)n * a.Tin + f1) * fs;
+    }
     const int pad = a.pad;
-    const int cchunks = a.Cin / CV_KC, iters = a.ksize * a.ksize * cchunks;
+    const int cchunks = a.Cin / CV_KC, iters = (MODE == CV_CONV3D ? 27 : a.ksize * a.ksize) * cchunks;
 
     float4 ra[2], rb[NB];
     auto fetch = [&](int it) {
@@ -153,6 +181,32 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
 #pragma unroll
             for (int i = 0; i < 2; ++i)
                 ra[i] = in ? sample4(xn, a.H, a.W, a.Cin, a.sy, a.sx, iy, ix, c0 + 4 * (jq + 2 * i), a.xtab, a.ytab) : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if constexpr (MODE == CV_CONV3D) {
+            const int kt = tap / 9, r9 = tap - 9 * kt;
+            const int iy = py + r9 / 3 - 1, ix = px + r9 % 3 - 1, ft = pt + kt - 2;
+            const bool in = pvalid && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+            const size_t fs = (size_t)a.H * a.W * a.Cin;
+            // the frame: of x; in front of frame 0, of prev (sample pn, frame ft + 2) or frame 0 of x again
+            const float* fb = ft >= 0 ? xn + (size_t)ft * fs : a.prev ? a.prev + ((size_t)pn * 2 + (ft + 2)) * fs : xn;
+            const float* src = fb + ((size_t)iy * a.W + ix) * a.Cin + c0;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) ra[i] = in ? *reinterpret_cast<const float4*>(src + 4 * (jq + 2 * i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if constexpr (MODE == CV_POOL_DOWN) {
+            const int iy = py * a.stride + dy, ix = px * a.stride + dx;
+            const bool in = pvalid && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
+            const size_t off = ((size_t)iy * a.W + ix) * a.Cin + c0;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (in) {
+                    v = *reinterpret_cast<const float4*>(xn + off + 4 * (jq + 2 * i));
+                    if (xb != xn) {
+                        const float4 u = *reinterpret_cast<const float4*>(xb + off + 4 * (jq + 2 * i));
+                        v = make_float4((v.x + u.x) * 0.5f, (v.y + u.y) * 0.5f, (v.z + u.z) * 0.5f, (v.w + u.w) * 0.5f);
+                    }
+                }
+                ra[i] = v;
+            }
         } else {
             const int iy = py * a.stride + dy, ix = px * a.stride + dx;
             const bool in = pvalid && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
@@ -195,8 +249,8 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-    [[maybe_unused]] f32x16_t tot[TM][TN];                                  // CV_CONV_CHUNKED: the sum of the finished runs
-    if constexpr (MODE == CV_CONV_CHUNKED) {
+    [[maybe_unused]] f32x16_t tot[TM][TN];                                  // CHUNKED: the sum of the finished runs
+    if constexpr (CHUNKED) {
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -224,7 +278,7 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
 #pragma unroll
                 for (int j = 0; j < TN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[i], fb[j], acc[i][j], 0, 0, 0);
         }
-        if constexpr (MODE == CV_CONV_CHUNKED) {
+        if constexpr (CHUNKED) {
             const bool last = it + 1 == iters;
             if ((it & (CV_CHUNK_ITERS - 1)) == CV_CHUNK_ITERS - 1 || last) {
 #pragma unroll

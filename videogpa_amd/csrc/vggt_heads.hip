@@ -5,6 +5,8 @@
 //                                   ResidualConvUnit / FeatureFusionBlock needs: out = conv(relu?(x)) + bias? + relu?(res)? + res2?
 //   conv_kernel<.., CV_CONV_CHUNKED> the convolution of the CogVideoX VAE encoder (vgpa_conv3x3_pad_f32): padding per side, and the K sum in short runs
 //                                   (conv_mfma.h), because its outputs are held to a bound that one chain of 9 * 512 fp32 additions does not meet
+//   conv_kernel<.., CV_CONV3D>      the encoder's causal 3x3x3 convolution over the frames of a chunk (vgpa_conv3x3x3_causal_f32) and
+//   conv_kernel<.., CV_POOL_DOWN>   its downsampler with the temporal pooling in the loader (vgpa_vae_downsample_f32): the chunked core again
 //   conv_kernel<.., CV_TAIL>        the end of DPTHead._forward_impl (dpt_head.py:229-247) in one launch on the same core: the loader samples the
 //                                   [N,h,w,C] map bilinearly (align_corners=True) at the (H,W) grid and adds the 0.1-scaled UV positional
 //                                   embedding from two separable tables; the epilogue is bias + ReLU, the 1x1 conv 32 -> output_dim, activate_head.
@@ -122,6 +124,37 @@ int32_t vgpa_conv3x3_pad_f32(const float* x, const float* w_packed, const float*
                              int64_t Cin, int64_t Cout, int64_t stride, int32_t pad_lo, int32_t pad_hi, hipStream_t stream) {
     if (pad_lo < 0 || pad_lo > 1 || pad_hi < 0 || pad_hi > 1) return VGPA_ERR_INVALID;
     return conv_entry<CV_CONV_CHUNKED>(x, w_packed, bias, res, nullptr, out, N, H, W, Cin, Cout, 3, stride, pad_lo, pad_hi, 0, stream);
+}
+
+// The causal 3x3x3 convolution over the frames of a chunk (videogpa_amd/vae.py): only the loader knows about time, see CV_CONV3D in conv_mfma.h
+int32_t vgpa_conv3x3x3_causal_f32(const float* x, const float* prev, const float* w_packed, const float* bias, const float* res, float* out, int64_t N,
+                                  int64_t T, int64_t H, int64_t W, int64_t Cin, int64_t Cout, hipStream_t stream) {
+    if (!x || !w_packed || !out || N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
+    if (N > (1 << 20) || T > (1 << 20) || H > (1 << 20) || W > (1 << 20) || Cin > (1 << 20) || Cout > (1 << 20) || N * T > (1 << 30)) return VGPA_ERR_INVALID;
+    if (!aligned16(x) || !aligned16(prev) || !aligned16(w_packed) || out == x || out == prev) return VGPA_ERR_INVALID;
+    ConvArgs a = {};
+    a.x = x; a.prev = prev; a.w = w_packed; a.bias = bias; a.res = res; a.out = out;
+    a.N = (int)N; a.T = (int)T; a.H = a.Ho = (int)H; a.W = a.Wo = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout; a.ksize = 3; a.stride = 1; a.pad = 1;
+    a.M = N * T * H * W;
+    return conv_launch<CV_CONV3D>(a, stream);
+}
+
+// CogVideoXDownsample3D in one launch: the one-sided stride-2 convolution above over N * T' frames, whose loader pools the frame pairs (CV_POOL_DOWN)
+int32_t vgpa_vae_downsample_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t N, int64_t T, int64_t H, int64_t W,
+                                int64_t C, int64_t Cout, int32_t compress_time, hipStream_t stream) {
+    if (!x || !w_packed || !out || N <= 0 || T <= 0 || H < 2 || W < 2 || C <= 0 || Cout <= 0 || (C & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
+    if (N > (1 << 20) || T > (1 << 20) || H > (1 << 20) || W > (1 << 20) || C > (1 << 20) || Cout > (1 << 20) || N * T > (1 << 30)) return VGPA_ERR_INVALID;
+    if ((compress_time != 0 && compress_time != 1) || !aligned16(x) || !aligned16(w_packed) || out == x) return VGPA_ERR_INVALID;
+    if (!compress_time || T == 1)                                          // nothing to pool: the frames are samples of the 2-D convolution
+        return conv_entry<CV_CONV_CHUNKED>(x, w_packed, bias, nullptr, nullptr, out, N * T, H, W, C, Cout, 3, 2, 0, 1, 0, stream);
+    ConvArgs a = {};
+    a.x = x; a.w = w_packed; a.bias = bias; a.out = out;
+    a.Tin = (int)T; a.T = (int)((T + 1) / 2);
+    a.N = (int)(N * a.T); a.H = (int)H; a.W = (int)W; a.Cin = (int)C; a.Cout = (int)Cout; a.ksize = 3; a.stride = 2; a.pad = 0;
+    a.Ho = (int)((H + 1 - 3) / 2 + 1);                                     // one zero row / column behind the last, none in front
+    a.Wo = (int)((W + 1 - 3) / 2 + 1);
+    a.M = (int64_t)a.N * a.Ho * a.Wo;
+    return conv_launch<CV_POOL_DOWN>(a, stream);
 }
 
 int32_t vgpa_dpt_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* w2,

@@ -1679,6 +1679,54 @@ def conv3x3_pad_f32(x, w_packed, bias=None, res=None, stride=1, pad_lo=1, pad_hi
     return out
 
 
+def pack_conv3d_weight(w):
+    """Conv3d weight [Cout, Cin, kt, kh, kw] -> [kt][kh][kw][Cin][Cout] fp32 contiguous, the layout conv3d_causal_f32 reads"""
+    return w.detach().float().permute(2, 3, 4, 1, 0).contiguous()
+
+
+def conv3d_causal_f32(x, w_packed, bias=None, res=None, prev=None):
+    """CogVideoXCausalConv3d over the frames of a chunk: x [N,T,H,W,Cin] -> conv3x3x3(x) + bias? + res? as [N,T,H,W,Cout], stride 1, spatial zero
+    padding 1; w_packed [3,3,3,Cin,Cout].  Temporal tap kt of output frame t reads frame t + kt - 2: in front of frame 0 that is `prev`
+    [N,2,H,W,Cin] (the last two input frames of the chunk before, diffusers' conv_cache) or, with prev None, frame 0 again.  Every output sums in
+    the same order whatever N, T and prev are (runs of 64 products, csrc/conv_mfma.h CV_CONV3D), so a call over T frames equals its split into
+    two calls bit for bit when the second gets x[:, -2:] of the first as `prev`."""
+    _heads_in(x, w_packed, bias, res, prev)
+    if x.dim() != 5:
+        raise RuntimeError(f"conv3d_causal_f32: expected [N,T,H,W,Cin], got {tuple(x.shape)}")
+    N, T, H, W, Cin = x.shape
+    Cout = w_packed.shape[-1]
+    if tuple(w_packed.shape) != (3, 3, 3, Cin, Cout) or Cin % 16 or Cout % 16:
+        raise RuntimeError(f"conv3d_causal_f32: weight {tuple(w_packed.shape)} does not fit input channels {Cin} (multiples of 16)")
+    if prev is not None and tuple(prev.shape) != (N, 2, H, W, Cin):
+        raise RuntimeError(f"conv3d_causal_f32: prev {tuple(prev.shape)} is not [{N},2,{H},{W},{Cin}]")
+    out = torch.empty(N, T, H, W, Cout, device=x.device, dtype=torch.float32)
+    if res is not None and res.shape != out.shape:
+        raise RuntimeError("conv3d_causal_f32: residual shape differs from the output's")
+    _timed("conv3d_causal_f32", 2.0 * out.numel() * 27 * Cin,
+           lambda: _lib.call("vgpa_conv3x3x3_causal_f32", x, prev, w_packed, bias, res, out, N, T, H, W, Cin, Cout, _stream()))
+    return out
+
+
+def vae_downsample_f32(x, w_packed, bias=None, compress_time=True):
+    """CogVideoXDownsample3D in one launch: x [N,T,H,W,C] -> [N,T',Ho,Wo,Cout], conv3x3_pad_f32(stride 2, pad_lo 0, pad_hi 1) of every temporally
+    pooled frame, which the loader forms as (a + b) * 0.5 and never writes.  T' = T without compress_time, else (T + 1) // 2: an even T pools
+    frames (2t', 2t' + 1); an odd T keeps frame 0 and pools (2t' - 1, 2t').  Bit for bit pooling first and conv3x3_pad_f32 after it."""
+    _heads_in(x, w_packed, bias)
+    if x.dim() != 5:
+        raise RuntimeError(f"vae_downsample_f32: expected [N,T,H,W,C], got {tuple(x.shape)}")
+    N, T, H, W, C = x.shape
+    Cout = w_packed.shape[-1]
+    if tuple(w_packed.shape) != (3, 3, C, Cout) or C % 16 or Cout % 16:
+        raise RuntimeError(f"vae_downsample_f32: weight {tuple(w_packed.shape)} does not fit input channels {C} (multiples of 16)")
+    if min(H, W) < 2:
+        raise RuntimeError(f"vae_downsample_f32: a {H} x {W} map is too small")
+    To = (T + 1) // 2 if compress_time else T
+    out = torch.empty(N, To, (H - 2) // 2 + 1, (W - 2) // 2 + 1, Cout, device=x.device, dtype=torch.float32)
+    _timed("vae_downsample_f32", 2.0 * out.numel() * 9 * C,
+           lambda: _lib.call("vgpa_vae_downsample_f32", x, w_packed, bias, out, N, T, H, W, C, Cout, 1 if compress_time else 0, _stream()))
+    return out
+
+
 def vae_input_f32(x):
     """x [N,3,H,W] (fp32 or bf16) -> fp32 [N,H,W,16], channels 3..15 zero: the input of the 16-channel form of the 3-channel stem"""
     _req(x)
@@ -1723,21 +1771,24 @@ def groupnorm_silu_f32(x, gamma, beta, groups, eps, stats=None):
 
 
 def vae_sample(moments, noise=None, scale=1.0, dtype=torch.float32, want=("sample",)):
-    """moments fp32 [N,h,w,2L] -> dict of the requested [N,L,1,h,w] tensors in `dtype`: "mean", "logvar" (clamped to [-30, 20]), "std" = exp(logvar / 2),
-    "sample" = (mean + std * noise) * scale with noise [N,L,1,h,w] in `dtype` (None: no noise)"""
+    """moments fp32 [N,h,w,2L] (one frame) or [N,T,h,w,2L] -> dict of the requested [N,L,T,h,w] tensors in `dtype` (T = 1 for the 4-D form): "mean",
+    "logvar" (clamped to [-30, 20]), "std" = exp(logvar / 2), "sample" = (mean + std * noise) * scale with noise [N,L,T,h,w] in `dtype` (None: no noise)"""
     _heads_in(moments)
-    N, h, w, L2 = moments.shape
+    if moments.dim() not in (4, 5):
+        raise RuntimeError(f"vae_sample: moments {tuple(moments.shape)} are neither [N,h,w,2L] nor [N,T,h,w,2L]")
+    shape = tuple(moments.shape)
+    N, T, h, w, L2 = shape if len(shape) == 5 else (shape[0], 1) + shape[1:]
     L = L2 // 2
     if L2 % 2 or not want or any(k not in ("sample", "mean", "logvar", "std") for k in want):
         raise RuntimeError(f"vae_sample: moments {tuple(moments.shape)}, outputs {want!r}")
     if noise is not None:
         _req(noise, dtype)
-        if tuple(noise.shape) != (N, L, 1, h, w):
-            raise RuntimeError(f"vae_sample: noise {tuple(noise.shape)} is not [{N},{L},1,{h},{w}]")
-    out = {k: torch.empty(N, L, 1, h, w, device=moments.device, dtype=dtype) for k in want}
+        if tuple(noise.shape) != (N, L, T, h, w):
+            raise RuntimeError(f"vae_sample: noise {tuple(noise.shape)} is not [{N},{L},{T},{h},{w}]")
+    out = {k: torch.empty(N, L, T, h, w, device=moments.device, dtype=dtype) for k in want}
     _timed("vae_sample", 4.0 * moments.numel(),
            lambda: _lib.call("vgpa_vae_sample", moments, noise, float(scale), out.get("sample"), out.get("mean"), out.get("logvar"), out.get("std"),
-                             _dtype_code(dtype, "vae_sample"), N, h * w, L, _stream()), "byte")
+                             _dtype_code(dtype, "vae_sample"), N, T * h * w, L, _stream()), "byte")
     return out
 
 

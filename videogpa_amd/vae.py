@@ -7,14 +7,25 @@
     vae.enable_slicing(); vae.enable_tiling()
     z = vae.encode(x).latent_dist.sample() * vae.config.scaling_factor      # x [B,3,1,H,W] -> [B,16,1,H/8,W/8]
 
-ONE frame only: a causal 3-D convolution sees its only frame repeated in time, so each folds into a 2-D convolution whose weight is the sum of the
-temporal taps (in fp32, from the checkpoint's values), and the temporal pooling of the downsamplers is the identity.  `encode` of more frames
-(02_encode.py's offline video encode) and the decoder raise NotImplementedError.  Inference only, fp32 arithmetic, channels-last inside: the
+and where the reference's offline data preparation uses it -- `vae.encode(video_tensor).latent_dist.sample()` on 49-frame clips with slicing and
+tiling on (train/CogVideoX-{5B,I2V-5B,1.5-5B}/02_encode.py):
+
+    z = vae.encode(v.to(vae.dtype)).latent_dist.sample()                    # v [B,3,F,H,W], F = 4k + 1 -> [B,16,(F-1)/4+1,H/8,W/8]
+
+ONE frame: a causal 3-D convolution sees its only frame repeated in time, so each folds into a 2-D convolution whose weight is the sum of the
+temporal taps (in fp32, from the checkpoint's values), and the temporal pooling of the downsamplers is the identity.
+A CLIP of F = 4k + 1 frames (49, 81, 13, ...): diffusers' `_encode`, restated.  The frames go through the whole encoder in batches
+(`frame_batches`: num_sample_frames_batch_size = 8 frames each, the first one longer by F % 8), every causal convolution
+(`ops.conv3d_causal_f32`, the 3x3x3 mode of the same MFMA core) reading the last two frames of its input in the batch before from the conv
+cache (frame 0 twice in the first batch), GroupNorm over the batch's (T,H,W) per sample -- so the result DEPENDS on the batching, as upstream's
+does -- and down blocks 0 and 1 halving time inside the downsampler's loader (`ops.vae_downsample_f32`).  With tiling every tile runs the frame
+batches with a cache of its own and the blends are per frame.  Any other F > 1 (02_encode.py's "clip shorter than 49 frames, take what there is")
+and the decoder raise NotImplementedError.  Inference only, fp32 arithmetic, channels-last inside: the
 convolutions run on the exact-fp32 MFMA kernel of the VGGT heads (`ops.conv3x3_pad_f32`: its form with the padding given per side, for the
 downsampler, and the K sum in short runs, for the accuracy bound of tests/test_gpu_vae.py; `ops.conv1x1_f32` for the shortcuts), GroupNorm + SiLU, the 3-channel stem's layout change and the Gaussian epilogue on csrc/vae.hip.  See DESIGN.md section 5f.
 
-PARITY UNPINNED (diffusers is neither installed nor vendored): the network, its parameter names and the tiled-encode scheme are restated from
-diffusers' autoencoder_kl_cogvideox.py.  The loader is strict, so the first real checkpoint shows at once if a name here is wrong."""
+PARITY UNPINNED (diffusers is neither installed nor vendored): the network, its parameter names, the tiled-encode scheme, the frame batching and
+the conv-cache scheme are restated from diffusers' autoencoder_kl_cogvideox.py.  The loader is strict, so the first real checkpoint shows at once if a name here is wrong."""
 import json
 import os
 
@@ -111,9 +122,39 @@ def _resnet_forward(p, h, groups, eps):
     return ops.conv3x3_pad_f32(t, *p["c2"], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
 
 
+def _pack3d(conv):
+    """a causal Conv3d as it is -> the packed 3-D weight [3,3,3,Cin,Cout] of ops.conv3d_causal_f32"""
+    return ops.pack_conv3d_weight(conv.weight)
+
+
+class _ConvCache:
+    """diffusers' conv_cache of one pass over a chunk of frames: per causal convolution the last two frames of its INPUT (behind the frames in
+    front of them: a one-frame chunk keeps the newer of the two it was given), as a contiguous copy of their own, not a view that would keep the
+    whole activation alive.  `prev` is the cache the chunk before left (None: the first chunk, frame 0 is replicated)."""
+
+    def __init__(self, prev=None):
+        self.prev, self.new = prev.new if prev is not None else {}, {}
+
+    def conv(self, name, x, w, b, res=None):
+        prev = self.prev.get(name)
+        if x.shape[1] >= 2:
+            self.new[name] = x[:, -2:].clone(memory_format=torch.contiguous_format)
+        else:
+            self.new[name] = torch.cat([prev[:, 1:] if prev is not None else x, x], dim=1)
+        return ops.conv3d_causal_f32(x, w, b, res=res, prev=prev)
+
+
+def _resnet_forward_video(p, w3, name, h, groups, eps, cache):
+    """_resnet_forward on a chunk h [N,T,H,W,C]: GroupNorm over the chunk's (T,H,W), the causal convolutions with their cache"""
+    t = cache.conv(name + ".conv1", ops.groupnorm_silu_f32(h, *p["n1"], groups, eps), w3[0], p["c1"][1])
+    t = ops.groupnorm_silu_f32(t, *p["n2"], groups, eps)
+    return cache.conv(name + ".conv2", t, w3[1], p["c2"][1], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
+
+
 class DiagonalGaussianDistribution:
-    """diffusers' class of the same name over the encoder's moments (kept as fp32 [N,h,w,2L] channels-last): `mean`, `logvar` (clamped to [-30, 20]),
-    `std` = exp(logvar / 2), `mode()` and `sample(generator)` are [N,L,1,h,w] in the VAE's dtype, each rounded once from the fp32 value"""
+    """diffusers' class of the same name over the encoder's moments (kept as fp32 [N,h,w,2L] channels-last, [N,T,h,w,2L] of a clip): `mean`, `logvar`
+    (clamped to [-30, 20]), `std` = exp(logvar / 2), `mode()` and `sample(generator)` are [N,L,T,h,w] (T = 1 of one frame) in the VAE's dtype, each
+    rounded once from the fp32 value"""
 
     def __init__(self, moments, dtype):
         self._moments, self._dtype, self._cache = moments, dtype, {}
@@ -133,8 +174,9 @@ class DiagonalGaussianDistribution:
     def sample(self, generator=None):
         """mean + std * randn, the noise drawn by torch.randn on the device in the VAE's dtype (a device generator reproduces it); formed in fp32 and
         rounded once (upstream's result to the rounding of its bf16 intermediates)"""
-        N, h, w, L2 = self._moments.shape
-        noise = torch.randn((N, L2 // 2, 1, h, w), generator=generator, device=self._moments.device, dtype=self._dtype)
+        N, (h, w, L2) = self._moments.shape[0], self._moments.shape[-3:]
+        T = self._moments.shape[1] if self._moments.dim() == 5 else 1
+        noise = torch.randn((N, L2 // 2, T, h, w), generator=generator, device=self._moments.device, dtype=self._dtype)
         return ops.vae_sample(self._moments, noise=noise, dtype=self._dtype)["sample"]
 
 
@@ -166,6 +208,7 @@ class AutoencoderKLCogVideoX(nn.Module):
         self.config = cfg
         self.encoder = _Encoder3D(cfg)
         self.use_slicing = self.use_tiling = False
+        self.num_sample_frames_batch_size = 8                # frames per pass through the encoder (diffusers' _encode); the first pass takes the remainder too
         self.tile_sample_min_height = cfg.sample_height // 2
         self.tile_sample_min_width = cfg.sample_width // 2
         down = 2 ** (len(cfg.block_out_channels) - 1)
@@ -266,6 +309,25 @@ class AutoencoderKLCogVideoX(nn.Module):
             return out
         return self._packed.get("all", list(self.parameters()), make)
 
+    def packed_video(self):
+        """the causal convolutions with their temporal taps kept, [3,3,3,Cin,Cout] fp32 (the stem padded to 16 input channels), for clips; everything
+        else comes from packed().  A cache entry of its own: a module that only ever sees one frame never builds it."""
+        enc = self.encoder
+
+        def make():
+            w_in = _pack3d(enc.conv_in.conv)
+            w_in = torch.cat([w_in, w_in.new_zeros(3, 3, 3, 16 - w_in.shape[3], w_in.shape[4])], dim=3).contiguous()
+            return {"conv_in": w_in, "conv_out": _pack3d(enc.conv_out.conv),
+                    "resnets": {id(r): (_pack3d(r.conv1.conv), _pack3d(r.conv2.conv)) for r in self._resnets()}}
+        return self._packed.get("video", list(self.parameters()), make)
+
+    def frame_batches(self, num_frames):
+        """diffusers' _encode: the (start, end) frame ranges a clip is encoded in, num_sample_frames_batch_size frames each, the first one longer by the
+        remainder (49 -> (0,9), (9,17), ..., (41,49); up to 15 frames are one batch).  Pure host arithmetic."""
+        size = self.num_sample_frames_batch_size
+        rem = num_frames % size
+        return [(size * i + (0 if i == 0 else rem), min(size * (i + 1) + rem, num_frames)) for i in range(max(num_frames // size, 1))]
+
     # ------------------------------------------------------------------ forward
     def _moments(self, x):
         """x [N,3,H,W] in the module's dtype -> the encoder's output [N,H/8,W/8,2L] fp32 channels-last"""
@@ -287,6 +349,40 @@ class AutoencoderKLCogVideoX(nn.Module):
             h = resnet(r, h)
         return ops.conv3x3_pad_f32(ops.groupnorm_silu_f32(h, *P["norm_out"], G, eps), *P["conv_out"])
 
+    def _chunk_moments(self, x, cache):
+        """one pass of diffusers' encoder over a chunk of frames: x [N,3,T,H,W] in the module's dtype -> [N,T',H/8,W/8,2L] fp32 channels-last, T' the
+        frames left by the temporal pooling of down blocks 0 and 1.  `cache` is this pass's _ConvCache (it reads the chunk before's, it keeps its own)."""
+        P, V, G, eps = self.packed(), self.packed_video(), self.config.norm_num_groups, self.config.norm_eps
+        enc = self.encoder
+        N, _, T, H, W = x.shape
+        n_time = {4: 2, 8: 3}.get(self.config.temporal_compression_ratio, 0)
+        frames = ops.vae_input_f32(x.transpose(1, 2).contiguous().view(N * T, 3, H, W)).view(N, T, H, W, 16)       # the 3-channel tensor: a host-side permute
+        h = cache.conv("conv_in", frames, V["conv_in"], P["conv_in"][1])
+
+        def resnet(name, r, h):
+            return _resnet_forward_video(P["resnets"][id(r)], V["resnets"][id(r)], name, h, G, eps, cache)
+
+        for i, b in enumerate(enc.down_blocks):
+            for j, r in enumerate(b.resnets):
+                h = resnet(f"down_blocks.{i}.resnets.{j}", r, h)
+            if hasattr(b, "downsamplers"):
+                if min(h.shape[2], h.shape[3]) < 2:
+                    raise RuntimeError(f"the clip is too small: a {h.shape[2]} x {h.shape[3]} map reached a downsampler")
+                h = ops.vae_downsample_f32(h, *P["down"][id(b)], compress_time=i < n_time)
+        for j, r in enumerate(enc.mid_block.resnets):
+            h = resnet(f"mid_block.resnets.{j}", r, h)
+        return cache.conv("conv_out", ops.groupnorm_silu_f32(h, *P["norm_out"], G, eps), V["conv_out"], P["conv_out"][1])
+
+    def _video_moments(self, x):
+        """x [N,3,F,H,W] -> [N,(F-1)/4+1,H/8,W/8,2L]: diffusers' _encode, the frame batches one after the other through the whole encoder, each with the
+        conv cache the one before left.  GroupNorm statistics are per sample and per batch of frames, as upstream, so the result depends on the batching."""
+        cache, out = None, []
+        for start, end in self.frame_batches(x.shape[2]):
+            cache = _ConvCache(cache)
+            out.append(self._chunk_moments(x[:, :, start:end], cache))
+            cache.prev = {}                                              # the chunk before's frames are no longer needed
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
     def tile_plan(self, height, width):
         """The tile grid of diffusers' tiled_encode for a height x width image: (rows, cols) of (start, size) in pixels, the blend extents and the kept
         tile size in latent pixels"""
@@ -298,23 +394,26 @@ class AutoencoderKLCogVideoX(nn.Module):
         return dict(rows=rows, cols=cols, blend=(blend_h, blend_w), keep=(self.tile_latent_min_height - blend_h, self.tile_latent_min_width - blend_w))
 
     def _tiled_moments(self, x):
-        plan = self.tile_plan(x.shape[2], x.shape[3])
+        """x [N,3,H,W] (one frame) or [N,3,F,H,W] (a clip: every tile runs the frame batches with a conv cache of its own, the blends are per frame)"""
+        video = x.dim() == 5
+        plan = self.tile_plan(x.shape[-2], x.shape[-1])
         rows, cols, (blend_h, blend_w), (keep_h, keep_w) = plan["rows"], plan["cols"], plan["blend"], plan["keep"]
-        N = x.shape[0]
+        N, ydim = x.shape[0], 2 if video else 1                         # the moments are [N,h,w,2L] or [N,T',h,w,2L]
         by_shape = {}                                                   # tiles of one size share a pass through the encoder as a batch
         for a, (i, th) in enumerate(rows):
             for b, (j, tw) in enumerate(cols):
                 by_shape.setdefault((th, tw), []).append((a, b, i, j))
         tiles = {}
         for (th, tw), members in by_shape.items():
-            m = self._moments(torch.cat([x[:, :, i:i + th, j:j + tw] for _, _, i, j in members], dim=0))
+            batch = torch.cat([x[..., i:i + th, j:j + tw] for _, _, i, j in members], dim=0)
+            m = self._video_moments(batch) if video else self._moments(batch)
             for k, (a, b, _, _) in enumerate(members):
                 tiles[a, b] = m[k * N:(k + 1) * N]
 
         def blend(prev, cur, extent, dim):                              # in place on `cur`, reading the neighbour's last rows / columns
             extent = min(prev.shape[dim], cur.shape[dim], extent)
             if extent > 0:
-                shape = [1, 1, 1, 1]
+                shape = [1] * cur.dim()
                 shape[dim] = extent
                 t = (torch.arange(extent, device=cur.device, dtype=torch.float32) / extent).reshape(shape)
                 head = cur.narrow(dim, 0, extent)
@@ -325,31 +424,36 @@ class AutoencoderKLCogVideoX(nn.Module):
             kept = []
             for b in range(len(cols)):
                 if a > 0:
-                    blend(tiles[a - 1, b], tiles[a, b], blend_h, 1)
+                    blend(tiles[a - 1, b], tiles[a, b], blend_h, ydim)
                 if b > 0:
-                    blend(tiles[a, b - 1], tiles[a, b], blend_w, 2)
-                kept.append(tiles[a, b][:, :keep_h, :keep_w])
-            out_rows.append(torch.cat(kept, dim=2))
-        return torch.cat(out_rows, dim=1).contiguous()
+                    blend(tiles[a, b - 1], tiles[a, b], blend_w, ydim + 1)
+                kept.append(tiles[a, b][(slice(None),) * ydim + (slice(0, keep_h), slice(0, keep_w))])
+            out_rows.append(torch.cat(kept, dim=ydim + 1))
+        return torch.cat(out_rows, dim=ydim).contiguous()
 
     def _encode(self, x):
-        H, W = x.shape[2], x.shape[3]
+        """x [N,3,H,W] (one frame: the folded 2-D path) or [N,3,F,H,W] (a clip) -> the moments, channels-last"""
+        H, W = x.shape[-2], x.shape[-1]
         if self.use_tiling and (W > self.tile_sample_min_width or H > self.tile_sample_min_height):
             return self._tiled_moments(x)
-        return self._moments(x)
+        return self._video_moments(x) if x.dim() == 5 else self._moments(x)
 
     def encode(self, x, return_dict=True):
-        """x [B,3,1,H,W] -> AutoencoderKLOutput whose `.latent_dist` is the DiagonalGaussianDistribution of the [B,L,1,H/8,W/8] latent.  The input
-        is rounded to the module's dtype first (the reference's `.to(self.vae.dtype)`)."""
+        """x [B,3,F,H,W], F = 1 or F = 4k + 1 (the model's clip lengths: 49, 81, 13, ...) -> AutoencoderKLOutput whose `.latent_dist` is the
+        DiagonalGaussianDistribution of the [B,L,(F-1)/4+1,H/8,W/8] latent.  The input is rounded to the module's dtype first (the reference's
+        `.to(self.vae.dtype)`).  One frame runs the folded 2-D path; a clip runs diffusers' frame batches (frame_batches) with the conv cache."""
         if x.dim() != 5 or x.shape[1] != 3:
             raise RuntimeError(f"encode: expected [B,3,F,H,W], got {tuple(x.shape)}")
-        if x.shape[2] != 1:
-            raise NotImplementedError(f"encode of {x.shape[2]} frames: only the one-frame encode (the I2V conditioning image) runs on the device; "
-                                      "the video encode of 02_encode.py is offline data preparation and out of scope")
+        F = x.shape[2]
+        if F != 1 and F % 4 != 1:
+            raise NotImplementedError(f"encode of {F} frames: one frame (the I2V conditioning image) or 4k + 1 frames (the model's clip lengths, "
+                                      "02_encode.py's 49) run on the device; a clip of another length is refused, not padded or cut")
         if not x.is_cuda:
             raise RuntimeError("videogpa_amd ops need GPU tensors (no CPU fallback)")
         _forward_only(self, x)
-        x = x.to(self.dtype)[:, :, 0]
+        x = x.to(self.dtype)
+        if F == 1:
+            x = x[:, :, 0]
         if self.use_slicing and x.shape[0] > 1:
             moments = torch.cat([self._encode(x[i:i + 1]) for i in range(x.shape[0])], dim=0)
         else:

@@ -519,6 +519,27 @@ int32_t vgpa_groupnorm_silu_f32(const float* x, const float* stats, const float*
 int32_t vgpa_vae_sample(const float* moments, const void* noise, float scale, void* sample, void* mean, void* logvar, void* std_out,
                         int32_t out_dtype, int64_t N, int64_t hw, int64_t L, vgpa_stream_t stream);
 
+/* ---- CogVideoX VAE decoder (videogpa_amd/vae.py with_decoder=True): the entry points above plus three ----
+ * CogVideoXUpsample3D in one launch: x [N,T,H,W,C] -> out [N,T',2H,2W,Cout], the 3x3 padding-1 convolution of vgpa_conv3x3_pad_f32 (w_packed
+ * [3][3][C][Cout], the K sum in its chains of 64) over the nearest-neighbour x2 map, which the loader forms by index arithmetic and never writes: tap
+ * (y, x) of output frame t' reads source pixel (y >> 1, x >> 1) of source frame f(t'), zero outside [0,2H) x [0,2W).  compress_time 0, or T = 1:
+ * T' = T, f(t') = t'.  compress_time 1 and an even T: T' = 2T, f(t') = t' >> 1.  compress_time 1 and an odd T > 1: T' = 2T - 1, f(0) = 0 and
+ * f(t') = 1 + ((t' - 1) >> 1) (frame 0 is not doubled in time).  Bit for bit the result of up-sampling so on the host and calling
+ * vgpa_conv3x3_pad_f32 on [N * T',2H,2W,C].  C, Cout multiples of 16; x and w_packed 16-byte aligned; never in place. */
+int32_t vgpa_vae_upsample_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t N, int64_t T, int64_t H, int64_t W,
+                              int64_t C, int64_t Cout, int32_t compress_time, vgpa_stream_t stream);
+/* CogVideoXSpatialNorm3D followed by SiLU: out = silu(((x - mean) * rstd * gamma + beta) * Y + B) over x [N,T,H,W,C] with the statistics of
+ * vgpa_groupnorm_stats_f32 (HW = T * H * W) and yb [N,t,h,w,2C] = (Y | B), conv_y | conv_b of the latent at the latent's resolution.  Pixel
+ * (tt, y, x) reads yb at (tz(tt), y * h / H, x * w / W): the nearest-neighbour resize of the modulation maps, never formed.  tz(tt) =
+ * floor(tt * t / T), except for an odd T > 1, where tz(0) = 0 and tz(tt) = 1 + floor((tt - 1) * (t - 1) / (T - 1)) (frame 0 of the latent goes
+ * to frame 0 alone; needs t >= 2).  H a multiple of h, W of w, t <= T; everything 16-byte aligned; never in place. */
+int32_t vgpa_spatial_norm_silu_f32(const float* x, const float* stats, const float* gamma, const float* beta, const float* yb, float* out, int64_t N,
+                                   int64_t T, int64_t H, int64_t W, int64_t C, int64_t G, int64_t t, int64_t h, int64_t w, vgpa_stream_t stream);
+/* Behind conv_out, run with its 3 output channels padded to 16: x fp32 [N,THW,16] -> out_dtype 0 fp32 | 1 bf16: out [N,3,THW], channels 0..2, rounded
+ * once (the inverse of vgpa_vae_input_f32); out_dtype 2: out uint8 [N,THW,3] = round(clamp(x / 2 + 0.5, 0, 1) * 255), ties to even (the pipeline's
+ * postprocess_video).  x is 16-byte aligned. */
+int32_t vgpa_vae_output(const float* x, void* out, int32_t out_dtype, int64_t N, int64_t THW, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,6 +111,9 @@ SIGNATURES = {
     "vgpa_groupnorm_stats_f32": (I32, [P, P, I64, I64, I64, I64, F32, P, SZ, P]),
     "vgpa_groupnorm_silu_f32": (I32, [P, P, P, P, P, I64, I64, I64, I64, P]),
     "vgpa_vae_sample": (I32, [P, P, F32, P, P, P, P, I32, I64, I64, I64, P]),
+    "vgpa_vae_upsample_f32": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),
+    "vgpa_spatial_norm_silu_f32": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, P]),
+    "vgpa_vae_output": (I32, [P, P, I32, I64, I64, P]),
 }
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library

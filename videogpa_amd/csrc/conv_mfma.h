@@ -11,6 +11,9 @@
 //                source address depends on N, T and prev: an output sums the same products in the same order wherever its frames lie
 //   CV_POOL_DOWN CogVideoXDownsample3D with its temporal pooling (vgpa_vae_downsample_f32): CV_CONV_CHUNKED on [N * T',H,W,C] whose loader reads
 //                frame t' as (a + b) * 0.5 of two frames of x [N,Tin,H,W,C] (or one frame as it is), so the pooled tensor is never written
+//   CV_UP2X      CogVideoXUpsample3D (vgpa_vae_upsample_f32): CV_CONV_CHUNKED, 3x3 with padding 1, over the nearest-neighbour x2 map of x
+//                [N,Tin,H,W,C] that is never written: tap (y, x) of output frame t reads source pixel (y >> 1, x >> 1) of source frame f(t), zero
+//                outside [0,2H) x [0,2W); f(t) = t (T = Tin), t >> 1 (T = 2 Tin) or 0, 1 + ((t - 1) >> 1) (T = 2 Tin - 1: frame 0 is not doubled)
 //   CV_TAIL      the end of vggt's DPTHead: bilinear loader (+ embedding), epilogue bias + ReLU, 1x1 conv 32 -> od, activate_head
 //   CV_AUX_TAIL  the end of DA3's auxiliary branch (dualdpt.py:250-258): the loader reads the map as it is (+ embedding, zero padding), the epilogue
 //                is bias, LayerNorm over the 32 hidden channels of the pixel, ReLU, 1x1 conv 32 -> od, linear preds and conf = 1 + exp
@@ -29,6 +32,7 @@
 #define CV_CONV_CHUNKED 3
 #define CV_CONV3D 4
 #define CV_POOL_DOWN 5
+#define CV_UP2X 6
 #define CV_CHUNK_ITERS 4
 #define CV_THREADS 256
 #define CV_BM 128
@@ -60,10 +64,10 @@ struct ConvArgs {
     const float* ln_w;   // [32]
     const float* ln_b;   // [32]
     float eps;
-    // CV_CONV3D and CV_POOL_DOWN only
+    // CV_CONV3D, CV_POOL_DOWN and CV_UP2X only
     const float* prev;   // CV_CONV3D: [N,2,H,W,Cin] | NULL
     int T;               // frames of the output
-    int Tin;             // CV_POOL_DOWN: frames of x (T = (Tin + 1) / 2)
+    int Tin;             // CV_POOL_DOWN: frames of x (T = (Tin + 1) / 2); CV_UP2X: frames of x (T = Tin, 2 Tin or 2 Tin - 1)
 };
 
 __device__ __forceinline__ float4 f4_fma(float s, float4 a, float4 acc) {
@@ -111,7 +115,7 @@ __device__ __forceinline__ float4 sample4(const float* __restrict__ base, int h,
 template <int WM, int WN, int TM, int TN, int MODE>
 __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
     constexpr bool TAIL = MODE == CV_TAIL || MODE == CV_AUX_TAIL;                               // either tail: 32 hidden channels, the epilogue goes through LDS
-    constexpr bool CHUNKED = MODE == CV_CONV_CHUNKED || MODE == CV_CONV3D || MODE == CV_POOL_DOWN;  // the K sum in runs of CV_CHUNK_ITERS iterations
+    constexpr bool CHUNKED = MODE == CV_CONV_CHUNKED || MODE == CV_CONV3D || MODE == CV_POOL_DOWN || MODE == CV_UP2X;  // the K sum in runs of CV_CHUNK_ITERS iterations
     constexpr int BN = WN * TN * 32;
     constexpr int BS = (BN % 64 == 0) ? BN + 32 : BN + 64;
     constexpr int NB = (CV_KC * BN / 4 + CV_THREADS - 1) / CV_THREADS;      // float4 of the weight tile per thread
@@ -153,6 +157,11 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
         xn = a.x + ((size_t)n * a.Tin + f0) * fs;
         xb = a.x + ((size_t)n * a.Tin + f1) * fs;
     }
+    if constexpr (MODE == CV_UP2X) {                                        // a.H, a.W: the source map; a.Ho = 2 a.H, a.Wo = 2 a.W
+        const int t = pn % a.T, n = pn / a.T;
+        const int f = a.T == a.Tin ? t : a.T == 2 * a.Tin ? t >> 1 : t == 0 ? 0 : 1 + ((t - 1) >> 1);
+        xn = a.x + ((size_t)n * a.Tin + f) * ((size_t)a.H * a.W * a.Cin);
+    }
     const int pad = a.pad;
     const int cchunks = a.Cin / CV_KC, iters = (MODE == CV_CONV3D ? 27 : a.ksize * a.ksize) * cchunks;
 
@@ -189,6 +198,12 @@ __global__ __launch_bounds__(CV_THREADS) void conv_kernel(const ConvArgs a) {
             // the frame: of x; in front of frame 0, of prev (sample pn, frame ft + 2) or frame 0 of x again
             const float* fb = ft >= 0 ? xn + (size_t)ft * fs : a.prev ? a.prev + ((size_t)pn * 2 + (ft + 2)) * fs : xn;
             const float* src = fb + ((size_t)iy * a.W + ix) * a.Cin + c0;
+#pragma unroll
+            for (int i = 0; i < 2; ++i) ra[i] = in ? *reinterpret_cast<const float4*>(src + 4 * (jq + 2 * i)) : make_float4(0.f, 0.f, 0.f, 0.f);
+        } else if constexpr (MODE == CV_UP2X) {
+            const int iy = py + dy, ix = px + dx;                               // on the up-sampled map
+            const bool in = pvalid && iy >= 0 && iy < a.Ho && ix >= 0 && ix < a.Wo;
+            const float* src = xn + ((size_t)(iy >> 1) * a.W + (ix >> 1)) * a.Cin + c0;
 #pragma unroll
             for (int i = 0; i < 2; ++i) ra[i] = in ? *reinterpret_cast<const float4*>(src + 4 * (jq + 2 * i)) : make_float4(0.f, 0.f, 0.f, 0.f);
         } else if constexpr (MODE == CV_POOL_DOWN) {

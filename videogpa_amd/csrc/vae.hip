@@ -11,12 +11,16 @@
 //   gn_silu_kernel       y = silu((x - mean) * rstd * gamma + beta), one pass of float4 accesses, grid-stride
 //   vae_sample_kernel    DiagonalGaussianDistribution: moments [N,h,w,2L] -> mean, logvar.clamp(-30, 20), std = exp(logvar / 2), sample = (mean + std * noise)
 //                        * scale as [N,L,1,h,w] in the output dtype; every output is optional
+// and of the decoder (the same convolutions plus conv_kernel's CV_UP2X up-sampler):
+//   spatial_norm_silu_kernel  CogVideoXSpatialNorm3D + SiLU: silu(GroupNorm(f) * Y + B), (Y | B) gathered from the latent-resolution map of conv_y | conv_b
+//   vae_output_kernel    behind conv_out (3 channels padded to 16): [N,T,H,W,16] fp32 -> [N,3,T,H,W] fp32 | bf16, or the uint8 frames [N,T,H,W,3]
 // The statistics and the apply pass are HBM-bound by design: algorithmic bytes N HW C 4 for the statistics, 2 N HW C 4 for the apply.
 #include "common.h"
 
 #define VAE_THREADS 256
 #define GN_ITERS 64                      // pixels a thread walks in stage 1: a workgroup owns (256 / (C / 4)) * GN_ITERS consecutive pixels of one sample
-#define GN_LOADS 4                       // of them loaded ahead of their updates (the Welford chain is serial; its loads need not be)
+#define VAE_OUT_U8 2                     // vgpa_vae_output's third out_dtype: the uint8 frames
+#define GN_LOADS 4                     // of them loaded ahead of their updates (the Welford chain is serial; its loads need not be)
 
 template <int DT>
 __global__ __launch_bounds__(VAE_THREADS) void vae_input_kernel(const void* __restrict__ x, float* __restrict__ out, int64_t HW, int64_t total4) {
@@ -165,6 +169,62 @@ __global__ __launch_bounds__(VAE_THREADS) void gn_silu_kernel(const float* __res
     }
 }
 
+// CogVideoXSpatialNorm3D + SiLU of the decoder: the GroupNorm value times Y plus B, where (Y | B) [N,t,h,w,2C] is conv_y | conv_b of the latent at
+// the latent's own resolution and the nearest-neighbour resize is the gather below (a 1x1 convolution commutes with it exactly).  H = ry h, W = rx w;
+// in time floor(dst * t / T), except that an odd T > 1 maps frame 0 to frame 0 and frames 1.. onto latent frames 1.. on their own
+__global__ __launch_bounds__(VAE_THREADS) void spatial_norm_silu_kernel(const float* __restrict__ x, const float* __restrict__ stats,
+                                                                         const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                                         const float* __restrict__ yb, float* __restrict__ out, int T, int H, int W, int C,
+                                                                         int G, int cpg, int t, int h, int w, int ry, int rx, int64_t total4) {
+    const int ncol = C >> 2;
+    const bool split = T > 1 && (T & 1);
+    for (int64_t i = (int64_t)blockIdx.x * VAE_THREADS + threadIdx.x; i < total4; i += (int64_t)gridDim.x * VAE_THREADS) {
+        const int c = (int)(i % ncol) * 4;
+        int64_t p = i / ncol;
+        const int px = (int)(p % W);
+        p /= W;
+        const int py = (int)(p % H);
+        p /= H;
+        const int pt = (int)(p % T);
+        const int64_t n = p / T;
+        const int tz = split ? (pt == 0 ? 0 : 1 + ((pt - 1) * (t - 1)) / (T - 1)) : (int)(((int64_t)pt * t) / T);
+        const float* m = yb + ((((size_t)n * t + tz) * h + py / ry) * w + px / rx) * (size_t)(2 * C) + c;
+        const float4 Y = *reinterpret_cast<const float4*>(m), B = *reinterpret_cast<const float4*>(m + C);
+        const float* st = stats + (size_t)n * G * 2;
+        const float4 v = reinterpret_cast<const float4*>(x)[i];
+        const float4 gm = *reinterpret_cast<const float4*>(gamma + c), bt = *reinterpret_cast<const float4*>(beta + c);
+        const int g0 = c / cpg, g1 = (c + 1) / cpg, g2 = (c + 2) / cpg, g3 = (c + 3) / cpg;
+        float4 y;
+        y.x = ((v.x - st[2 * g0]) * st[2 * g0 + 1] * gm.x + bt.x) * Y.x + B.x;
+        y.y = ((v.y - st[2 * g1]) * st[2 * g1 + 1] * gm.y + bt.y) * Y.y + B.y;
+        y.z = ((v.z - st[2 * g2]) * st[2 * g2 + 1] * gm.z + bt.z) * Y.z + B.z;
+        y.w = ((v.w - st[2 * g3]) * st[2 * g3 + 1] * gm.w + bt.w) * Y.w + B.w;
+        reinterpret_cast<float4*>(out)[i] = make_float4(y.x / (1.0f + expf(-y.x)), y.y / (1.0f + expf(-y.y)), y.z / (1.0f + expf(-y.z)),
+                                                        y.w / (1.0f + expf(-y.w)));
+    }
+}
+
+// behind conv_out, whose 3 channels are padded to 16: thread = one pixel of x [N,THW,16].  DT fp32 | bf16: out [N,3,THW] (the inverse of
+// vae_input_kernel); U8: out [N,THW,3] bytes = round(clamp(x / 2 + 0.5, 0, 1) * 255), ties to even as numpy's round
+template <int DT, bool U8>
+__global__ __launch_bounds__(VAE_THREADS) void vae_output_kernel(const float* __restrict__ x, void* __restrict__ out, int64_t THW, int64_t total) {
+    for (int64_t i = (int64_t)blockIdx.x * VAE_THREADS + threadIdx.x; i < total; i += (int64_t)gridDim.x * VAE_THREADS) {
+        const float4 v = reinterpret_cast<const float4*>(x)[4 * i];
+        if constexpr (U8) {
+            uint8_t* d = reinterpret_cast<uint8_t*>(out) + (size_t)i * 3;
+            d[0] = (uint8_t)rintf(fminf(fmaxf(v.x * 0.5f + 0.5f, 0.f), 1.f) * 255.f);
+            d[1] = (uint8_t)rintf(fminf(fmaxf(v.y * 0.5f + 0.5f, 0.f), 1.f) * 255.f);
+            d[2] = (uint8_t)rintf(fminf(fmaxf(v.z * 0.5f + 0.5f, 0.f), 1.f) * 255.f);
+        } else {
+            const int64_t n = i / THW, r = i - n * THW;
+            const size_t dst = (size_t)n * 3 * THW + r;
+            store1<DT>(out, dst, v.x);
+            store1<DT>(out, dst + THW, v.y);
+            store1<DT>(out, dst + 2 * THW, v.z);
+        }
+    }
+}
+
 // thread = one element of the [N,L,1,h,w] outputs
 template <int DT>
 __global__ __launch_bounds__(VAE_THREADS) void vae_sample_kernel(const float* __restrict__ moments, const void* __restrict__ noise, float scale,
@@ -229,6 +289,31 @@ int32_t vgpa_groupnorm_silu_f32(const float* x, const float* stats, const float*
     if (!vae_aligned16(x) || !vae_aligned16(out) || !vae_aligned16(gamma) || !vae_aligned16(beta)) return VGPA_ERR_INVALID;
     const int64_t total4 = N * HW * (C / 4);
     VGPA_LAUNCH(gn_silu_kernel, dim3(vae_blocks(total4)), dim3(VAE_THREADS), 0, stream, x, stats, gamma, beta, out, HW, (int)C, (int)G, (int)(C / G), total4);
+    VGPA_CHECK_LAUNCH();
+    return VGPA_OK;
+}
+
+int32_t vgpa_spatial_norm_silu_f32(const float* x, const float* stats, const float* gamma, const float* beta, const float* yb, float* out, int64_t N,
+                                   int64_t T, int64_t H, int64_t W, int64_t C, int64_t G, int64_t t, int64_t h, int64_t w, hipStream_t stream) {
+    if (!x || !stats || !gamma || !beta || !yb || !out || out == x || T <= 0 || H <= 0 || W <= 0 || t <= 0 || h <= 0 || w <= 0) return VGPA_ERR_INVALID;
+    if (T > (1 << 15) || t > (1 << 15) || H > (1 << 20) || W > (1 << 20) || !gn_shape_ok(N, T * H * W, C, G)) return VGPA_ERR_INVALID;
+    if (H % h || W % w || t > T || (T > 1 && (T & 1) && t < 2)) return VGPA_ERR_INVALID;      // integral spatial ratios; the odd-frame split needs a frame behind frame 0
+    if (!vae_aligned16(x) || !vae_aligned16(out) || !vae_aligned16(gamma) || !vae_aligned16(beta) || !vae_aligned16(yb)) return VGPA_ERR_INVALID;
+    const int64_t total4 = N * T * H * W * (C / 4);
+    VGPA_LAUNCH(spatial_norm_silu_kernel, dim3(vae_blocks(total4)), dim3(VAE_THREADS), 0, stream, x, stats, gamma, beta, yb, out, (int)T, (int)H, (int)W,
+                (int)C, (int)G, (int)(C / G), (int)t, (int)h, (int)w, (int)(H / h), (int)(W / w), total4);
+    VGPA_CHECK_LAUNCH();
+    return VGPA_OK;
+}
+
+int32_t vgpa_vae_output(const float* x, void* out, int32_t out_dtype, int64_t N, int64_t THW, hipStream_t stream) {
+    if (!x || !out || N <= 0 || THW <= 0 || N > (1 << 20) || THW > (1LL << 40) || !vae_aligned16(x)) return VGPA_ERR_INVALID;
+    const int64_t total = N * THW;
+    const dim3 grid(vae_blocks(total)), block(VAE_THREADS);
+    if (out_dtype == VGPA_DTYPE_F32) VGPA_LAUNCH((vae_output_kernel<VGPA_DTYPE_F32, false>), grid, block, 0, stream, x, out, THW, total);
+    else if (out_dtype == VGPA_DTYPE_BF16) VGPA_LAUNCH((vae_output_kernel<VGPA_DTYPE_BF16, false>), grid, block, 0, stream, x, out, THW, total);
+    else if (out_dtype == VAE_OUT_U8) VGPA_LAUNCH((vae_output_kernel<VGPA_DTYPE_F32, true>), grid, block, 0, stream, x, out, THW, total);
+    else return VGPA_ERR_INVALID;
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
 }

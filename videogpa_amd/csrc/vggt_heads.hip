@@ -7,6 +7,8 @@
 //                                   (conv_mfma.h), because its outputs are held to a bound that one chain of 9 * 512 fp32 additions does not meet
 //   conv_kernel<.., CV_CONV3D>      the encoder's causal 3x3x3 convolution over the frames of a chunk (vgpa_conv3x3x3_causal_f32) and
 //   conv_kernel<.., CV_POOL_DOWN>   its downsampler with the temporal pooling in the loader (vgpa_vae_downsample_f32): the chunked core again
+//   conv_kernel<.., CV_UP2X>        the decoder's up-sampler (vgpa_vae_upsample_f32): the chunked core over the nearest x2 map (x4 with time), which only
+//                                   the loader's index arithmetic forms
 //   conv_kernel<.., CV_TAIL>        the end of DPTHead._forward_impl (dpt_head.py:229-247) in one launch on the same core: the loader samples the
 //                                   [N,h,w,C] map bilinearly (align_corners=True) at the (H,W) grid and adds the 0.1-scaled UV positional
 //                                   embedding from two separable tables; the epilogue is bias + ReLU, the 1x1 conv 32 -> output_dim, activate_head.
@@ -155,6 +157,22 @@ int32_t vgpa_vae_downsample_f32(const float* x, const float* w_packed, const flo
     a.Wo = (int)((W + 1 - 3) / 2 + 1);
     a.M = (int64_t)a.N * a.Ho * a.Wo;
     return conv_launch<CV_POOL_DOWN>(a, stream);
+}
+
+// CogVideoXUpsample3D in one launch: the 3x3 padding-1 convolution over N * T' frames of 2H x 2W whose loader reads the source at half the index (CV_UP2X)
+int32_t vgpa_vae_upsample_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t N, int64_t T, int64_t H, int64_t W,
+                              int64_t C, int64_t Cout, int32_t compress_time, hipStream_t stream) {
+    if (!x || !w_packed || !out || N <= 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0 || (C & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
+    if (N > (1 << 20) || T > (1 << 20) || H > (1 << 20) || W > (1 << 20) || C > (1 << 20) || Cout > (1 << 20) || N * T > (1 << 29)) return VGPA_ERR_INVALID;
+    if ((compress_time != 0 && compress_time != 1) || !aligned16(x) || !aligned16(w_packed) || out == x) return VGPA_ERR_INVALID;
+    ConvArgs a = {};
+    a.x = x; a.w = w_packed; a.bias = bias; a.out = out;
+    a.Tin = (int)T;
+    a.T = (int)(!compress_time || T == 1 ? T : (T & 1) ? 2 * T - 1 : 2 * T);   // an odd count keeps frame 0 single
+    a.N = (int)(N * a.T); a.H = (int)H; a.W = (int)W; a.Ho = (int)(2 * H); a.Wo = (int)(2 * W);
+    a.Cin = (int)C; a.Cout = (int)Cout; a.ksize = 3; a.stride = 1; a.pad = 1;
+    a.M = (int64_t)a.N * a.Ho * a.Wo;
+    return conv_launch<CV_UP2X>(a, stream);
 }
 
 int32_t vgpa_dpt_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* w2,

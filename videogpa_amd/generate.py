@@ -1,9 +1,20 @@
 """Denoising loop of the reference's generate path (generate/CogVideoX-5B.py:17-31,70-77 -> diffusers
 CogVideoXPipeline.__call__): classifier-free guidance over a [uncond, cond] batch, 3D RoPE tables, the DPM scheduler,
-with the MI355X transformer (RoPE kernel live) and a merged LoRA adapter.  Text encoding (T5) and latent decoding (VAE)
-are third-party networks outside the hot path: the caller passes prompt embeddings in and gets latents out.
+with the MI355X transformer (RoPE kernel live) and a merged LoRA adapter, and the pipeline's decode_latents on the device VAE
+decoder (videogpa_amd.vae with with_decoder=True): `denoise` returns latents, `decode_latents` turns them into `output.frames`.
+Text encoding (T5) is a third-party network outside the hot path: the caller passes prompt embeddings in.
 PARITY UNPINNED (diffusers not vendored): restated from pipeline_cogvideox.py / embeddings.get_3d_rotary_pos_embed."""
 import torch
+
+
+@torch.no_grad()
+def decode_latents(vae, latents, uint8=False):
+    """CogVideoXPipeline.decode_latents: latents [B,F,C,h,w] (what `denoise` returns) -> `vae.decode(latents.permute(0,2,1,3,4) /
+    vae.config.scaling_factor).sample`, the frames [B,3,F',8h,8w] in the VAE's dtype, values in about [-1,1].  uint8=True: the pipeline's
+    postprocess_video on top, [B,F',8h,8w,3] uint8, the layout the scorer takes frames in.  `vae` is an AutoencoderKLCogVideoX built with
+    with_decoder=True; its slicing and tiling switches apply."""
+    z = (1 / vae.config.scaling_factor) * latents.permute(0, 2, 1, 3, 4)
+    return vae.decode_uint8(z) if uint8 else vae.decode(z).sample
 
 
 def rope_3d_tables(num_frames, grid_h, grid_w, head_dim=64, theta=10000.0, device="cuda"):

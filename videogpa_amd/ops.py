@@ -1792,6 +1792,72 @@ def vae_sample(moments, noise=None, scale=1.0, dtype=torch.float32, want=("sampl
     return out
 
 
+# ---- CogVideoX VAE decoder: the entry points above plus these three ------------------------------------------------------------------------
+def vae_upsample_frames(T, compress_time):
+    """frames CogVideoXUpsample3D leaves of T: T without compress_time or of one frame, 2T of an even count, 2T - 1 of an odd one (frame 0 stays single)"""
+    return T if not compress_time or T == 1 else 2 * T - 1 if T % 2 else 2 * T
+
+
+def vae_upsample_f32(x, w_packed, bias=None, compress_time=True):
+    """CogVideoXUpsample3D in one launch: x [N,T,H,W,C] -> [N,T',2H,2W,Cout], conv3x3_pad_f32 (padding 1) of the nearest-neighbour x2 map, which the
+    loader reads as source pixel (y >> 1, x >> 1) of source frame f(t') and never writes.  T' = vae_upsample_frames(T, compress_time); f(t') = t'
+    (T' = T), t' >> 1 (T' = 2T), or 0 for t' = 0 and 1 + (t' - 1) // 2 after it (T' = 2T - 1).  Bit for bit up-sampling first and conv3x3_pad_f32
+    after it."""
+    _heads_in(x, w_packed, bias)
+    if x.dim() != 5:
+        raise RuntimeError(f"vae_upsample_f32: expected [N,T,H,W,C], got {tuple(x.shape)}")
+    N, T, H, W, C = x.shape
+    Cout = w_packed.shape[-1]
+    if tuple(w_packed.shape) != (3, 3, C, Cout) or C % 16 or Cout % 16:
+        raise RuntimeError(f"vae_upsample_f32: weight {tuple(w_packed.shape)} does not fit input channels {C} (multiples of 16)")
+    out = torch.empty(N, vae_upsample_frames(T, compress_time), 2 * H, 2 * W, Cout, device=x.device, dtype=torch.float32)
+    _timed("vae_upsample_f32", 2.0 * out.numel() * 9 * C,
+           lambda: _lib.call("vgpa_vae_upsample_f32", x, w_packed, bias, out, N, T, H, W, C, Cout, 1 if compress_time else 0, _stream()))
+    return out
+
+
+def spatial_norm_silu_f32(f, stats, gamma, beta, yb):
+    """silu(CogVideoXSpatialNorm3D(f, zq)) of f [N,T,H,W,C] channels-last: silu(((f - mean) * rstd * gamma + beta) * Y + B), `stats` [N,G,2] from
+    groupnorm_stats_f32, yb [N,t,h,w,2C] = (Y | B) = conv_y | conv_b of the latent zq at ITS resolution (one conv1x1_f32 with the two weights side
+    by side).  The nearest-neighbour resize to (T,H,W) is a gather in the kernel -- a 1x1 convolution commutes with it exactly -- with upstream's
+    special case: an odd T > 1 takes frame 0 from latent frame 0 and resizes the other frames on their own.  H, W must be multiples of h, w."""
+    _heads_in(f, stats, gamma, beta, yb)
+    if f.dim() != 5 or yb.dim() != 5:
+        raise RuntimeError(f"spatial_norm_silu_f32: expected f [N,T,H,W,C] and yb [N,t,h,w,2C], got {tuple(f.shape)} and {tuple(yb.shape)}")
+    N, T, H, W, C = f.shape
+    n, t, h, w, C2 = yb.shape
+    if n != N or C2 != 2 * C or gamma.numel() != C or beta.numel() != C or stats.dim() != 3 or stats.shape[0] != N or stats.shape[2] != 2:
+        raise RuntimeError(f"spatial_norm_silu_f32: f {tuple(f.shape)}, yb {tuple(yb.shape)}, stats {tuple(stats.shape)} and gamma / beta do not fit")
+    G = stats.shape[1]
+    if C % 4 or C % G or C > 1024:
+        raise RuntimeError(f"spatial_norm_silu_f32: {C} channels in {G} groups is not supported (C a multiple of 4 and of the groups, <= 1024)")
+    if H % h or W % w:
+        raise RuntimeError(f"spatial_norm_silu_f32: a {H} x {W} map over a {h} x {w} latent: the ratios must be integral")
+    if t > T or (T > 1 and T % 2 and t < 2):
+        raise RuntimeError(f"spatial_norm_silu_f32: {t} latent frames do not resize to {T} frames (an odd count takes its frame 0 aside)")
+    out = torch.empty_like(f)
+    _timed("spatial_norm_silu_f32", 8.0 * f.numel(),
+           lambda: _lib.call("vgpa_spatial_norm_silu_f32", f, stats, gamma, beta, yb, out, N, T, H, W, C, G, t, h, w, _stream()), "byte")
+    return out
+
+
+def vae_output(x, dtype=torch.float32, uint8=False):
+    """behind the decoder's conv_out (3 channels padded to 16): x fp32 [N,T,H,W,16] -> [N,3,T,H,W] in `dtype` (fp32 | bf16), channels 0..2 rounded
+    once -- the inverse of vae_input_f32.  uint8=True: the pipeline's postprocess_video instead, [N,T,H,W,3] uint8 =
+    round(clamp(x / 2 + 0.5, 0, 1) * 255), the layout the scorer's frame input takes."""
+    _heads_in(x)
+    if x.dim() != 5 or x.shape[-1] != 16:
+        raise RuntimeError(f"vae_output: expected [N,T,H,W,16], got {tuple(x.shape)}")
+    N, T, H, W, _ = x.shape
+    if uint8:
+        out, code = torch.empty(N, T, H, W, 3, device=x.device, dtype=torch.uint8), 2
+    else:
+        out, code = torch.empty(N, 3, T, H, W, device=x.device, dtype=dtype), _dtype_code(dtype, "vae_output")
+    _timed("vae_output", 4.0 * x.numel() + out.numel() * out.element_size(),
+           lambda: _lib.call("vgpa_vae_output", x, out, code, N, T * H * W, _stream()), "byte")
+    return out
+
+
 # ---- Depth Anything 3's backbone between its blocks, and its camera decoding (csrc/da3.hip): fp32, forward only ---------------------------
 DA3_REF_VIEW_STRATEGIES = {"first": 0, "middle": 1, "saddle_balanced": 2, "saddle_sim_range": 3}
 

@@ -20,7 +20,17 @@ A CLIP of F = 4k + 1 frames (49, 81, 13, ...): diffusers' `_encode`, restated.  
 cache (frame 0 twice in the first batch), GroupNorm over the batch's (T,H,W) per sample -- so the result DEPENDS on the batching, as upstream's
 does -- and down blocks 0 and 1 halving time inside the downsampler's loader (`ops.vae_downsample_f32`).  With tiling every tile runs the frame
 batches with a cache of its own and the blends are per frame.  Any other F > 1 (02_encode.py's "clip shorter than 49 frames, take what there is")
-and the decoder raise NotImplementedError.  Inference only, fp32 arithmetic, channels-last inside: the
+raises NotImplementedError.
+The DECODER is opt-in, `AutoencoderKLCogVideoX(with_decoder=True, ...)` / `from_pretrained(..., with_decoder=True)`: the end of the reference's
+generate scripts (`pipe.vae.enable_tiling(); pipe.vae.enable_slicing()`, `output.frames`; videogpa_amd.generate.decode_latents),
+
+    frames = vae.decode(latents.permute(0, 2, 1, 3, 4) / vae.config.scaling_factor).sample     # [B,16,13,60,90] -> [B,3,49,480,720]
+
+diffusers' `_decode` restated: batches of num_latent_frames_batch_size = 2 latent frames (`latent_frame_batches`, the first longer by F % 2) through the
+whole decoder with the conv cache, every norm a spatial norm conditioned on the batch's latent (`ops.spatial_norm_silu_f32`: the modulation maps stay at
+latent resolution), the up-samplers of blocks 0 and 1 doubling time inside the loader (`ops.vae_upsample_f32`), `tiled_decode` over latent tiles
+(`decode_tile_plan`).  Without the keyword the module is the encoder side alone: `decoder.*` is dropped on load and `decode` raises.  See DESIGN.md
+section 5g.  Inference only, fp32 arithmetic, channels-last inside: the
 convolutions run on the exact-fp32 MFMA kernel of the VGGT heads (`ops.conv3x3_pad_f32`: its form with the padding given per side, for the
 downsampler, and the K sum in short runs, for the accuracy bound of tests/test_gpu_vae.py; `ops.conv1x1_f32` for the shortcuts), GroupNorm + SiLU, the 3-channel stem's layout change and the Gaussian epilogue on csrc/vae.hip.  See DESIGN.md section 5f.
 
@@ -95,6 +105,67 @@ class _Encoder3D(nn.Module):
         self.conv_out = _CausalConv3d(chans[-1], 2 * cfg.latent_channels)
 
 
+class _SpatialNorm3D(nn.Module):
+    """CogVideoXSpatialNorm3D(C, L): GroupNorm(f) * conv_y(zq) + conv_b(zq), zq the latent resized to f; its GroupNorm's eps is 1e-6 whatever the config says"""
+
+    def __init__(self, c, zq_channels, groups):
+        super().__init__()
+        self.norm_layer = nn.GroupNorm(groups, c, eps=1e-6)
+        self.conv_y = _CausalConv3d(zq_channels, c, k=1)
+        self.conv_b = _CausalConv3d(zq_channels, c, k=1)
+
+
+class _DecoderResnetBlock3D(nn.Module):
+    def __init__(self, cin, cout, zq_channels, groups):
+        super().__init__()
+        self.norm1 = _SpatialNorm3D(cin, zq_channels, groups)
+        self.norm2 = _SpatialNorm3D(cout, zq_channels, groups)
+        self.conv1 = _CausalConv3d(cin, cout)
+        self.conv2 = _CausalConv3d(cout, cout)
+        if cin != cout:
+            self.conv_shortcut = nn.Conv3d(cin, cout, 1)
+
+
+class _Upsample3D(nn.Module):
+    def __init__(self, c):
+        super().__init__()
+        self.conv = nn.Conv2d(c, c, 3, padding=1)
+
+
+class _UpBlock3D(nn.Module):
+    def __init__(self, cin, cout, layers, zq_channels, groups, upsample):
+        super().__init__()
+        self.resnets = nn.ModuleList([_DecoderResnetBlock3D(cin if j == 0 else cout, cout, zq_channels, groups) for j in range(layers)])
+        if upsample:
+            self.upsamplers = nn.ModuleList([_Upsample3D(cout)])
+
+
+class _DecoderMidBlock3D(nn.Module):
+    def __init__(self, c, zq_channels, groups):
+        super().__init__()
+        self.resnets = nn.ModuleList([_DecoderResnetBlock3D(c, c, zq_channels, groups) for _ in range(2)])
+
+
+class _Decoder3D(nn.Module):
+    """CogVideoXDecoder3D under upstream's parameter names: the widths reversed, layers_per_block + 1 resnets per up block, an up-sampler on every block
+    but the last, every norm a spatial norm conditioned on the latent"""
+
+    def __init__(self, cfg):
+        super().__init__()
+        rev, groups, L = tuple(reversed(cfg.block_out_channels)), cfg.norm_num_groups, cfg.latent_channels
+        self.conv_in = _CausalConv3d(L, rev[0])
+        self.mid_block = _DecoderMidBlock3D(rev[0], L, groups)
+        self.up_blocks = nn.ModuleList([
+            _UpBlock3D(rev[max(i - 1, 0)], c, cfg.layers_per_block + 1, L, groups, upsample=i < len(rev) - 1) for i, c in enumerate(rev)])
+        self.norm_out = _SpatialNorm3D(rev[-1], L, groups)
+        self.conv_out = _CausalConv3d(rev[-1], cfg.out_channels)
+
+    def resnets(self):
+        """(cache name, resnet) in the order of the forward pass"""
+        return [(f"mid_block.resnets.{j}", r) for j, r in enumerate(self.mid_block.resnets)] + \
+               [(f"up_blocks.{i}.resnets.{j}", r) for i, b in enumerate(self.up_blocks) for j, r in enumerate(b.resnets)]
+
+
 def _fold(conv):
     """a causal Conv3d on one frame -> the packed 2-D weight [3,3,Cin,Cout]: the frame fills all kt temporal taps, so they add (fp32)"""
     return ops.pack_conv_weight(conv.weight.detach().float().sum(dim=2))
@@ -151,6 +222,69 @@ def _resnet_forward_video(p, w3, name, h, groups, eps, cache):
     return cache.conv(name + ".conv2", t, w3[1], p["c2"][1], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
 
 
+def _pack_spatial_norm(n):
+    """a spatial norm's parameters for the kernels: GroupNorm (gamma, beta), and conv_y | conv_b side by side as one 1x1 convolution [L, 2C] with its
+    bias [2C], so that one ops.conv1x1_f32 of the latent gives the (Y | B) map ops.spatial_norm_silu_f32 gathers from"""
+    wy, wb = (c.conv.weight.detach().float().reshape(c.conv.weight.shape[0], -1).t() for c in (n.conv_y, n.conv_b))
+    return dict(gn=(_vec(n.norm_layer.weight), _vec(n.norm_layer.bias)),
+                yb=(torch.cat([wy, wb], dim=1).contiguous(), torch.cat([_vec(n.conv_y.conv.bias), _vec(n.conv_b.conv.bias)])))
+
+
+def _spatial_norm_silu(p, f, zq, groups):
+    """silu(CogVideoXSpatialNorm3D(f, zq)) on f [N,T,H,W,C], zq [N,t,h,w,L]: the modulation maps at the latent's resolution (a 1x1 convolution commutes
+    with the nearest resize exactly), the resize as the kernel's gather"""
+    return ops.spatial_norm_silu_f32(f, ops.groupnorm_stats_f32(f, groups, 1e-6), *p["gn"], ops.conv1x1_f32(zq, *p["yb"]))
+
+
+def _pack_decoder_resnet(r):
+    sc = None
+    if hasattr(r, "conv_shortcut"):
+        w = r.conv_shortcut.weight.detach().float()
+        sc = (w.reshape(w.shape[0], w.shape[1]).t().contiguous(), _vec(r.conv_shortcut.bias))
+    return dict(n1=_pack_spatial_norm(r.norm1), n2=_pack_spatial_norm(r.norm2), c1=(_pack3d(r.conv1.conv), _vec(r.conv1.conv.bias)),
+                c2=(_pack3d(r.conv2.conv), _vec(r.conv2.conv.bias)), sc=sc)
+
+
+def _decoder_resnet_forward(p, name, h, zq, groups, cache):
+    """CogVideoXResnetBlock3D of the decoder on a chunk h [N,T,H,W,C]: norm1(h, zq), SiLU, conv1, norm2(., zq), SiLU, conv2, plus the input (through the
+    1x1x1 shortcut when the width changes; the add is conv2's epilogue)"""
+    t = cache.conv(name + ".conv1", _spatial_norm_silu(p["n1"], h, zq, groups), *p["c1"])
+    t = _spatial_norm_silu(p["n2"], t, zq, groups)
+    return cache.conv(name + ".conv2", t, *p["c2"], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
+
+
+def _blend(prev, cur, extent, dim):
+    """diffusers' blend_v / blend_h in place on `cur`: a linear ramp over its first `extent` rows / columns from the neighbour's last ones"""
+    extent = min(prev.shape[dim], cur.shape[dim], extent)
+    if extent > 0:
+        shape = [1] * cur.dim()
+        shape[dim] = extent
+        t = (torch.arange(extent, device=cur.device, dtype=torch.float32) / extent).reshape(shape)
+        head = cur.narrow(dim, 0, extent)
+        head.copy_(prev.narrow(dim, prev.shape[dim] - extent, extent) * (1 - t) + head * t)
+
+
+def _stitch(tiles, n_rows, n_cols, blend, keep, ydim):
+    """the end of tiled_encode / tiled_decode on channels-last tiles {(row, col): tensor}: row-major, every tile blended in place with the tile above and
+    then the tile to its left (so later blends read already-blended neighbours), cropped to `keep`, concatenated.  `ydim` is the tensors' row axis."""
+    out_rows = []
+    for a in range(n_rows):
+        kept = []
+        for b in range(n_cols):
+            if a > 0:
+                _blend(tiles[a - 1, b], tiles[a, b], blend[0], ydim)
+            if b > 0:
+                _blend(tiles[a, b - 1], tiles[a, b], blend[1], ydim + 1)
+            kept.append(tiles[a, b][(slice(None),) * ydim + (slice(0, keep[0]), slice(0, keep[1]))])
+        out_rows.append(torch.cat(kept, dim=ydim + 1))
+    return torch.cat(out_rows, dim=ydim).contiguous()
+
+
+class DecoderOutput:
+    def __init__(self, sample):
+        self.sample = sample
+
+
 class DiagonalGaussianDistribution:
     """diffusers' class of the same name over the encoder's moments (kept as fp32 [N,h,w,2L] channels-last, [N,T,h,w,2L] of a clip): `mean`, `logvar`
     (clamped to [-30, 20]), `std` = exp(logvar / 2), `mode()` and `sample(generator)` are [N,L,T,h,w] (T = 1 of one frame) in the VAE's dtype, each
@@ -189,7 +323,9 @@ class AutoencoderKLCogVideoX(nn.Module):
     config_name = "config.json"
     weights_name = "diffusion_pytorch_model.safetensors"
 
-    def __init__(self, **kw):
+    def __init__(self, with_decoder=False, **kw):
+        """with_decoder=True adds `self.decoder` (and decode / forward); without it the module is the encoder side alone and `decoder.*` tensors of a
+        checkpoint are dropped.  A constructor keyword, not a config key: it is not kept on `.config`."""
         super().__init__()
         cfg = _Config(DEFAULT_CONFIG)
         cfg.update(kw)                                   # unknown keys are kept on .config (checkpoint configs carry _class_name, _diffusers_version, ...)
@@ -207,8 +343,17 @@ class AutoencoderKLCogVideoX(nn.Module):
                                       f"{cfg.norm_num_groups}: widths must be multiples of 32 (<= 1024) and of the groups, 2 * latent_channels of 16")
         self.config = cfg
         self.encoder = _Encoder3D(cfg)
+        self.decoder = None
+        if with_decoder:
+            if cfg.use_post_quant_conv:
+                raise NotImplementedError("use_post_quant_conv=True is not implemented (no CogVideoX checkpoint sets it)")
+            if cfg.latent_channels % 16 or cfg.out_channels != 3 or cfg.temporal_compression_ratio not in (4, 8):
+                raise NotImplementedError(f"decoder: latent_channels {cfg.latent_channels} (a multiple of 16), out_channels {cfg.out_channels} (3) and "
+                                          f"temporal_compression_ratio {cfg.temporal_compression_ratio} (4 or 8) are what runs on the device")
+            self.decoder = _Decoder3D(cfg)
         self.use_slicing = self.use_tiling = False
         self.num_sample_frames_batch_size = 8                # frames per pass through the encoder (diffusers' _encode); the first pass takes the remainder too
+        self.num_latent_frames_batch_size = 2                # latent frames per pass through the decoder (diffusers' _decode), likewise
         self.tile_sample_min_height = cfg.sample_height // 2
         self.tile_sample_min_width = cfg.sample_width // 2
         down = 2 ** (len(cfg.block_out_channels) - 1)
@@ -249,7 +394,8 @@ class AutoencoderKLCogVideoX(nn.Module):
     def from_pretrained(cls, path, subfolder=None, torch_dtype=None, **kw):
         """diffusers' on-disk layout from a LOCAL directory: <path>/<subfolder>/config.json + diffusion_pytorch_model.safetensors, or its shards
         `diffusion_pytorch_model-0000i-of-0000n.safetensors` listed by `diffusion_pytorch_model.safetensors.index.json`.  `decoder.*` tensors are
-        skipped; a missing or unexpected `encoder.*` tensor, or one of another shape, is an error naming it.  torch_dtype=None keeps float32."""
+        skipped unless with_decoder=True is given; a missing or unexpected tensor, or one of another shape, is an error naming it.  torch_dtype=None
+        keeps float32."""
         from safetensors.torch import load_file
         root = os.path.join(path, subfolder) if subfolder else path
         if not os.path.isdir(root):
@@ -275,8 +421,9 @@ class AutoencoderKLCogVideoX(nn.Module):
         return model
 
     def load_state_dict(self, state_dict, strict=True, assign=False):
-        """strict on the encoder: `decoder.*` (not implemented here) is dropped, every other difference raises with the tensor's name"""
-        sd = {k: v for k, v in state_dict.items() if not k.startswith("decoder.")}
+        """strict: every difference raises with the tensor's name.  An encoder-only module (with_decoder=False) drops `decoder.*` first; one with the
+        decoder is as strict on `decoder.*` as on `encoder.*`."""
+        sd = {k: v for k, v in state_dict.items() if self.decoder is not None or not k.startswith("decoder.")}
         own = self.state_dict()
         missing, unexpected = sorted(k for k in own if k not in sd), sorted(k for k in sd if k not in own)
         wrong = sorted(f"{k}: checkpoint {tuple(sd[k].shape)}, model {tuple(own[k].shape)}" for k in sd if k in own and sd[k].shape != own[k].shape)
@@ -409,27 +556,7 @@ class AutoencoderKLCogVideoX(nn.Module):
             m = self._video_moments(batch) if video else self._moments(batch)
             for k, (a, b, _, _) in enumerate(members):
                 tiles[a, b] = m[k * N:(k + 1) * N]
-
-        def blend(prev, cur, extent, dim):                              # in place on `cur`, reading the neighbour's last rows / columns
-            extent = min(prev.shape[dim], cur.shape[dim], extent)
-            if extent > 0:
-                shape = [1] * cur.dim()
-                shape[dim] = extent
-                t = (torch.arange(extent, device=cur.device, dtype=torch.float32) / extent).reshape(shape)
-                head = cur.narrow(dim, 0, extent)
-                head.copy_(prev.narrow(dim, prev.shape[dim] - extent, extent) * (1 - t) + head * t)
-
-        out_rows = []
-        for a in range(len(rows)):
-            kept = []
-            for b in range(len(cols)):
-                if a > 0:
-                    blend(tiles[a - 1, b], tiles[a, b], blend_h, ydim)
-                if b > 0:
-                    blend(tiles[a, b - 1], tiles[a, b], blend_w, ydim + 1)
-                kept.append(tiles[a, b][(slice(None),) * ydim + (slice(0, keep_h), slice(0, keep_w))])
-            out_rows.append(torch.cat(kept, dim=ydim + 1))
-        return torch.cat(out_rows, dim=ydim).contiguous()
+        return _stitch(tiles, len(rows), len(cols), (blend_h, blend_w), (keep_h, keep_w), ydim)
 
     def _encode(self, x):
         """x [N,3,H,W] (one frame: the folded 2-D path) or [N,3,F,H,W] (a clip) -> the moments, channels-last"""
@@ -461,8 +588,113 @@ class AutoencoderKLCogVideoX(nn.Module):
         dist = DiagonalGaussianDistribution(moments, self.dtype)
         return AutoencoderKLOutput(dist) if return_dict else (dist,)
 
-    def decode(self, *a, **kw):
-        raise NotImplementedError("the CogVideoX VAE decoder is not implemented: this module is the encoder side only")
+    # ------------------------------------------------------------------ decoder (with_decoder=True)
+    def packed_decoder(self):
+        """fp32 kernel-layout copies of the decoder's parameters: causal convolutions [3,3,3,Cin,Cout] (conv_out padded to 16 output channels with zero
+        columns), the spatial norms as _pack_spatial_norm leaves them, the up-samplers' 2-D weights [3,3,C,C]"""
+        dec = self.decoder
 
-    def forward(self, *a, **kw):
-        raise NotImplementedError("AutoencoderKLCogVideoX.forward (encode + decode) is not implemented: call .encode()")
+        def make():
+            w_out, b_out = _pack3d(dec.conv_out.conv), _vec(dec.conv_out.conv.bias)
+            w_out = torch.cat([w_out, w_out.new_zeros(*w_out.shape[:4], 16 - w_out.shape[4])], dim=4).contiguous()
+            b_out = torch.cat([b_out, b_out.new_zeros(16 - b_out.shape[0])])
+            return {"conv_in": (_pack3d(dec.conv_in.conv), _vec(dec.conv_in.conv.bias)), "conv_out": (w_out, b_out),
+                    "norm_out": _pack_spatial_norm(dec.norm_out), "resnets": {name: _pack_decoder_resnet(r) for name, r in dec.resnets()},
+                    "up": {i: (ops.pack_conv_weight(b.upsamplers[0].conv.weight), _vec(b.upsamplers[0].conv.bias))
+                           for i, b in enumerate(dec.up_blocks) if hasattr(b, "upsamplers")}}
+        return self._packed.get("decoder", list(dec.parameters()), make)
+
+    def latent_frame_batches(self, num_frames):
+        """diffusers' _decode: the (start, end) latent frame ranges a latent is decoded in, num_latent_frames_batch_size frames each, the first one longer
+        by the remainder (13 -> (0,3), (3,5), ..., (11,13); up to 3 frames are one batch).  Pure host arithmetic."""
+        size = self.num_latent_frames_batch_size
+        rem = num_frames % size
+        return [(size * i + (0 if i == 0 else rem), min(size * (i + 1) + rem, num_frames)) for i in range(max(num_frames // size, 1))]
+
+    def _chunk_frames(self, zq, cache):
+        """one pass of diffusers' decoder over a chunk of latent frames: zq [N,t,h,w,L] fp32 channels-last -> [N,T,8h,8w,16] fp32 (channels 0..2 are the
+        image, the rest zero), T the frames the up-samplers of blocks 0 and 1 (compress_time) make of t.  Every spatial norm is conditioned on zq."""
+        P, G, dec = self.packed_decoder(), self.config.norm_num_groups, self.decoder
+        n_time = {4: 2, 8: 3}[self.config.temporal_compression_ratio]
+        h = cache.conv("conv_in", zq, *P["conv_in"])
+        for j in range(len(dec.mid_block.resnets)):
+            h = _decoder_resnet_forward(P["resnets"][f"mid_block.resnets.{j}"], f"mid_block.resnets.{j}", h, zq, G, cache)
+        for i, b in enumerate(dec.up_blocks):
+            for j in range(len(b.resnets)):
+                h = _decoder_resnet_forward(P["resnets"][f"up_blocks.{i}.resnets.{j}"], f"up_blocks.{i}.resnets.{j}", h, zq, G, cache)
+            if i in P["up"]:
+                h = ops.vae_upsample_f32(h, *P["up"][i], compress_time=i < n_time)
+        return cache.conv("conv_out", _spatial_norm_silu(P["norm_out"], h, zq, G), *P["conv_out"])
+
+    def _latent_frames(self, z):
+        """z [N,F,h,w,L] fp32 channels-last -> [N,F',8h,8w,16]: diffusers' _decode, the latent frame batches one after the other through the whole
+        decoder, each with the conv cache the one before left.  GroupNorm statistics are per sample and per batch, so the result depends on the batching."""
+        cache, out = None, []
+        for start, end in self.latent_frame_batches(z.shape[1]):
+            cache = _ConvCache(cache)
+            out.append(self._chunk_frames(z[:, start:end].contiguous(), cache))
+            cache.prev = {}
+        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+
+    def decode_tile_plan(self, height, width):
+        """The tile grid of diffusers' tiled_decode for a height x width LATENT: (rows, cols) of (start, size) in latent pixels, the blend extents and the
+        kept tile size in sample pixels"""
+        fh, fw = self.tile_overlap_factor_height, self.tile_overlap_factor_width
+        stride_h, stride_w = int(self.tile_latent_min_height * (1 - fh)), int(self.tile_latent_min_width * (1 - fw))
+        blend_h, blend_w = int(self.tile_sample_min_height * fh), int(self.tile_sample_min_width * fw)
+        rows = [(i, min(self.tile_latent_min_height, height - i)) for i in range(0, height, stride_h)]
+        cols = [(j, min(self.tile_latent_min_width, width - j)) for j in range(0, width, stride_w)]
+        return dict(rows=rows, cols=cols, blend=(blend_h, blend_w), keep=(self.tile_sample_min_height - blend_h, self.tile_sample_min_width - blend_w))
+
+    def _tiled_frames(self, z):
+        """tiled_decode on z [N,F,h,w,L]: every latent tile through the frame-batch loop with a conv cache of its own, the blends per frame in sample pixels"""
+        plan = self.decode_tile_plan(z.shape[2], z.shape[3])
+        rows, cols, N = plan["rows"], plan["cols"], z.shape[0]
+        by_shape = {}                                                   # tiles of one size share a pass through the decoder as a batch
+        for a, (i, th) in enumerate(rows):
+            for b, (j, tw) in enumerate(cols):
+                by_shape.setdefault((th, tw), []).append((a, b, i, j))
+        tiles = {}
+        for (th, tw), members in by_shape.items():
+            frames = self._latent_frames(torch.cat([z[:, :, i:i + th, j:j + tw] for _, _, i, j in members], dim=0))
+            for k, (a, b, _, _) in enumerate(members):
+                tiles[a, b] = frames[k * N:(k + 1) * N]
+        return _stitch(tiles, len(rows), len(cols), plan["blend"], plan["keep"], 2)
+
+    def _decode(self, z):
+        """z [N,L,F,h,w] in the module's dtype -> the frames [N,F',8h,8w,16] fp32 channels-last"""
+        z = z.permute(0, 2, 3, 4, 1).float().contiguous()               # the latent is small: a host-side permute
+        if self.use_tiling and (z.shape[3] > self.tile_latent_min_width or z.shape[2] > self.tile_latent_min_height):
+            return self._tiled_frames(z)
+        return self._latent_frames(z)
+
+    def _decoded_frames(self, z):
+        if self.decoder is None:
+            raise NotImplementedError("this module is the encoder side only: construct it (or call from_pretrained) with with_decoder=True to decode")
+        if z.dim() != 5 or z.shape[1] != self.config.latent_channels:
+            raise RuntimeError(f"decode: expected [B,{self.config.latent_channels},F,h,w], got {tuple(z.shape)}")
+        if not z.is_cuda:
+            raise RuntimeError("videogpa_amd ops need GPU tensors (no CPU fallback)")
+        _forward_only(self, z)
+        z = z.to(self.dtype)
+        if self.use_slicing and z.shape[0] > 1:
+            return torch.cat([self._decode(z[i:i + 1]) for i in range(z.shape[0])], dim=0)
+        return self._decode(z)
+
+    def decode(self, z, return_dict=True):
+        """z [B,L,F,h,w] -> DecoderOutput whose `.sample` is [B,3,F',8h,8w] in the module's dtype, rounded once from fp32; F' = 4 (F - 1) + 1 frames of an
+        odd F (13 -> 49), 4 F of an even one (diffusers' latent frame batches, latent_frame_batches).  z is rounded to the module's dtype first."""
+        frames = self._decoded_frames(z)
+        sample = ops.vae_output(frames, self.dtype)
+        return DecoderOutput(sample) if return_dict else (sample,)
+
+    def decode_uint8(self, z):
+        """decode followed by the pipeline's postprocess_video, from the fp32 frames: [B,F',8h,8w,3] uint8 = round(clamp(x / 2 + 0.5, 0, 1) * 255)"""
+        return ops.vae_output(self._decoded_frames(z), uint8=True)
+
+    def forward(self, sample, sample_posterior=False, return_dict=True, generator=None):
+        """diffusers' forward: encode, the posterior's sample (or its mode), decode"""
+        if self.decoder is None:
+            raise NotImplementedError("AutoencoderKLCogVideoX.forward (encode + decode) needs the decoder: construct the module with with_decoder=True")
+        posterior = self.encode(sample).latent_dist
+        return self.decode(posterior.sample(generator=generator) if sample_posterior else posterior.mode(), return_dict=return_dict)

@@ -540,6 +540,27 @@ int32_t vgpa_spatial_norm_silu_f32(const float* x, const float* stats, const flo
  * postprocess_video).  x is 16-byte aligned. */
 int32_t vgpa_vae_output(const float* x, void* out, int32_t out_dtype, int64_t N, int64_t THW, vgpa_stream_t stream);
 
+/* ---- T5 encoder between its GEMMs (transformers' T5EncoderModel, the CogVideoX text encoder; videogpa_amd/t5.py, csrc/t5.hip): forward only ----
+ * o = softmax(q k^T + bias[h][j - i] + mask[b][j]) v at head_dim 64: T5 attention has no 1/sqrt(d) scale.  q, k, v are bf16 [B,H,S,64] views given
+ * by element strides {batch, head, token} (slices of the fused QKV GEMM output, read in place; strides multiples of 8, bases 16-byte aligned);
+ * o bf16 [B,S,H*64] contiguous.  1 <= S <= 512, anything else is an invalid argument.  bias_delta fp32 [H, 2S-1], indexed by j - i + S - 1 (key j,
+ * query i): the relative-position bias as a per-head Toeplitz table.  mask uint8 [B,S], 1 = keep, or NULL for none: a masked key gets the weight
+ * exactly 0, whatever k and v hold there; every sample must keep at least one key (its rows are NaN otherwise).  Padded query rows are computed like
+ * any other.  bf16 MFMA for both products, fp32 scores / bias add / softmax, the exact two-pass softmax (true row maximum); the row sum adds the
+ * bf16-rounded weights that multiply v.  A sample's result does not depend on B, and NULL equals an all-ones mask bit for bit. */
+int32_t vgpa_t5_attn_fwd(const void* q, const void* k, const void* v, const int64_t* q_strides, const int64_t* k_strides, const int64_t* v_strides,
+                         const float* bias_delta, const uint8_t* mask, void* o, int64_t B, int64_t H, int64_t S, vgpa_stream_t stream);
+/* The fp32 residual stream with T5LayerNorm (RMS only: no mean subtraction, no bias): x_new [M,D] fp32, then
+ *   n = w * x_new * rsqrt(mean(x_new^2) + eps),  w fp32 [D],  stored in n_dtype 0 fp32 | 1 bf16, rounded once.
+ * x_new is  x (y, ids NULL; x_new must be NULL),  x + y (y bf16 [M,D], the GEMM output in front; written to x_new unless that is NULL; never in place),
+ * or the embedding row float(table[ids[row]]) (ids int64 [M], table bf16 [V,D]; x and y NULL, x_new required; an id outside [0,V) gives a row of NaN
+ * and reads nothing).  D a multiple of 64, at most 4096. */
+int32_t vgpa_t5_rms(const float* x, const void* y, const int64_t* ids, const void* table, int64_t V, const float* w, float* x_new, void* n,
+                    int32_t n_dtype, int64_t M, int64_t D, float eps, vgpa_stream_t stream);
+/* T5DenseGatedActDense between its GEMMs: u bf16 [M, 2 d_ff] (one GEMM against wi_0 | wi_1) -> g bf16 [M, d_ff] = gelu_new(u[:, :d_ff]) * u[:, d_ff:],
+ * the tanh GELU and the product in fp32, rounded once.  d_ff a multiple of 8. */
+int32_t vgpa_t5_gated_gelu(const void* u, void* g, int64_t M, int64_t d_ff, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

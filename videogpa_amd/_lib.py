@@ -114,6 +114,9 @@ SIGNATURES = {
     "vgpa_vae_upsample_f32": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),
     "vgpa_spatial_norm_silu_f32": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, I64, I64, I64, P]),
     "vgpa_vae_output": (I32, [P, P, I32, I64, I64, P]),
+    "vgpa_t5_attn_fwd": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, P]),
+    "vgpa_t5_rms": (I32, [P, P, P, P, I64, P, P, P, I32, I64, I64, F32, P]),
+    "vgpa_t5_gated_gelu": (I32, [P, P, I64, I64, P]),
 }
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library

@@ -2,7 +2,10 @@
 CogVideoXPipeline.__call__): classifier-free guidance over a [uncond, cond] batch, 3D RoPE tables, the DPM scheduler,
 with the MI355X transformer (RoPE kernel live) and a merged LoRA adapter, and the pipeline's decode_latents on the device VAE
 decoder (videogpa_amd.vae with with_decoder=True): `denoise` returns latents, `decode_latents` turns them into `output.frames`.
-Text encoding (T5) is a third-party network outside the hot path: the caller passes prompt embeddings in.
+Text encoding runs on the device too (videogpa_amd.t5.T5EncoderModel): `encode_prompt` turns token ids into the prompt embeddings `denoise` takes, so
+the whole path prompt ids -> embeddings -> denoise -> VAE decode -> frames stays on the GPU.  Tokenisation is the caller's: the sentencepiece
+tokenizer is string work on the host (`tokenizer(prompt, padding="max_length", max_length=226, truncation=True, add_special_tokens=True,
+return_tensors="pt").input_ids`, as the pipeline calls it).
 PARITY UNPINNED (diffusers not vendored): restated from pipeline_cogvideox.py / embeddings.get_3d_rotary_pos_embed."""
 import torch
 
@@ -15,6 +18,24 @@ def decode_latents(vae, latents, uint8=False):
     with_decoder=True; its slicing and tiling switches apply."""
     z = (1 / vae.config.scaling_factor) * latents.permute(0, 2, 1, 3, 4)
     return vae.decode_uint8(z) if uint8 else vae.decode(z).sample
+
+
+@torch.no_grad()
+def encode_prompt(text_encoder, input_ids, negative_input_ids=None, num_videos_per_prompt=1, dtype=None):
+    """CogVideoXPipeline.encode_prompt / _get_t5_prompt_embeds behind the tokenizer: `text_encoder(input_ids)[0]` with NO attention mask (the
+    pipeline passes none), cast to `dtype` (default: the encoder's), each prompt's embeddings repeated num_videos_per_prompt times in a row ->
+    (prompt_embeds, negative_prompt_embeds), each [B * num_videos_per_prompt, S, d_model], ready for `denoise`.  input_ids / negative_input_ids are
+    int [B,S] as the tokenizer pads them (max_length 226).  The pipeline encodes the negative prompt "" when guidance is on and none is given: pass
+    the ids of "" for that; with negative_input_ids=None the second result is None (and `denoise` falls back to zeros, which the pipeline never does)."""
+    def one(ids):
+        e = text_encoder(ids)[0]
+        e = e.to(dtype=dtype or e.dtype)
+        b, s, _ = e.shape
+        return e.repeat(1, num_videos_per_prompt, 1).view(b * num_videos_per_prompt, s, -1)
+
+    if negative_input_ids is not None and tuple(negative_input_ids.shape) != tuple(input_ids.shape):
+        raise ValueError(f"encode_prompt: negative_input_ids {tuple(negative_input_ids.shape)} and input_ids {tuple(input_ids.shape)} differ in shape")
+    return one(input_ids), None if negative_input_ids is None else one(negative_input_ids)
 
 
 def rope_3d_tables(num_frames, grid_h, grid_w, head_dim=64, theta=10000.0, device="cuda"):

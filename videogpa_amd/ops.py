@@ -1949,3 +1949,89 @@ def da3_pose_decode(pose_enc, image_size_hw):
     H, W = image_size_hw
     _timed("da3_pose_decode", 4.0 * n * 30, lambda: _lib.call("vgpa_da3_pose_decode", pose_enc, n, float(H), float(W), ext, intr, _stream()), "byte")
     return ext, intr
+
+
+# ---- T5 encoder between its GEMMs (csrc/t5.hip): forward only -------------------------------------------------------------------------------
+T5_MAX_S = 512
+
+
+def _t5_forward_only(name, *ts):
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError(f"{name} is forward only: call it under torch.no_grad()")
+
+
+def t5_attention(q, k, v, bias_delta, mask=None):
+    """softmax(q k^T + bias[h][j - i] + mask[b][j]) v, no 1/sqrt(d) scale.  q, k, v bf16 [B,S,H,64] views (slices of the fused QKV GEMM output, read in
+    place; last dim contiguous); bias_delta fp32 [H, 2S-1] indexed by j - i + S - 1; mask None | uint8 / bool [B,S], 1 = keep (every sample must keep
+    a key) -> o bf16 [B,S,H*64].  S <= 512."""
+    for t in (q, k, v):
+        _req(t, torch.bfloat16, contiguous=False)
+    _req(bias_delta, torch.float32)
+    _t5_forward_only("t5_attention", q, k, v, bias_delta)
+    if q.dim() != 4 or q.shape[-1] != 64 or k.shape != q.shape or v.shape != q.shape or any(t.stride(3) != 1 for t in (q, k, v)):
+        raise RuntimeError(f"t5_attention: q, k, v must be [B,S,H,64] views with a contiguous last dim, got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+    B, S, H, _ = q.shape
+    if S < 1 or S > T5_MAX_S:
+        raise RuntimeError(f"t5_attention: 1 <= S <= {T5_MAX_S}, got {S}")
+    if tuple(bias_delta.shape) != (H, 2 * S - 1):
+        raise RuntimeError(f"t5_attention: bias_delta must be [H, 2S-1] = {(H, 2 * S - 1)}, got {tuple(bias_delta.shape)}")
+    if mask is not None:
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8) if mask.is_contiguous() else mask.to(torch.uint8)
+        _req(mask, torch.uint8)
+        if tuple(mask.shape) != (B, S):
+            raise RuntimeError(f"t5_attention: mask must be [B,S] = {(B, S)}, got {tuple(mask.shape)}")
+    o = torch.empty(B, S, H * 64, device=q.device, dtype=torch.bfloat16)
+    st = [_i64x3(t.stride(0), t.stride(2), t.stride(1)) for t in (q, k, v)]
+    _timed("t5_attn_fwd", 4.0 * B * H * S * S * 64,
+           lambda: _lib.call("vgpa_t5_attn_fwd", q, k, v, st[0], st[1], st[2], bias_delta, mask, o, B, H, S, _stream()))
+    return o
+
+
+def t5_rms(x, w, y=None, eps=1e-6, n_dtype=torch.bfloat16, keep_stream=True):
+    """The fp32 residual stream with T5LayerNorm: x fp32 [..., D], y (bf16, the GEMM output in front) or None; x_new = x + y;
+    n = w * x_new * rsqrt(mean(x_new^2) + eps) in n_dtype (w fp32 [D]) -> (x_new | None, n).  x_new is None without y, and with keep_stream=False
+    (the final norm, behind which nobody reads the stream).  D a multiple of 64, at most 4096."""
+    _req(x, torch.float32)
+    _req(w, torch.float32)
+    if y is not None:
+        _req(y, torch.bfloat16)
+    _t5_forward_only("t5_rms", x, y, w)
+    D = x.shape[-1]
+    if D % 64 or D > 4096 or w.numel() != D or (y is not None and y.shape != x.shape) or n_dtype not in _DT or x.numel() == 0:
+        raise RuntimeError(f"t5_rms: x {tuple(x.shape)}, y and w {tuple(w.shape)} do not fit (D a multiple of 64, at most 4096; fp32 or bf16 output)")
+    x_new = torch.empty_like(x) if (y is not None and keep_stream) else None
+    n = torch.empty(x.shape, device=x.device, dtype=n_dtype)
+    M = x.numel() // D
+    nbytes = 4.0 + (2.0 if y is not None else 0.0) + (4.0 if x_new is not None else 0.0) + n.element_size()
+    _timed("t5_rms", nbytes * M * D, lambda: _lib.call("vgpa_t5_rms", x, y, None, None, 0, w, x_new, n, _DT[n_dtype], M, D, float(eps), _stream()), "byte")
+    return x_new, n
+
+
+def t5_embed_rms(ids, table, w, eps=1e-6):
+    """The first norm of the network fused with the embedding gather: ids int64 [...], table bf16 [V,D], w fp32 [D] ->
+    (x fp32 [..., D] = table[ids], n bf16 = T5LayerNorm(x)).  An id outside [0,V) gives a row of NaN."""
+    _req(ids, torch.int64)
+    _req(table, torch.bfloat16)
+    _req(w, torch.float32)
+    _t5_forward_only("t5_embed_rms", table, w)
+    if table.dim() != 2 or table.shape[1] % 64 or table.shape[1] > 4096 or w.numel() != table.shape[1] or ids.numel() == 0:
+        raise RuntimeError(f"t5_embed_rms: table {tuple(table.shape)} and w {tuple(w.shape)} do not fit (D a multiple of 64, at most 4096)")
+    V, D = table.shape
+    M = ids.numel()
+    x = torch.empty(*ids.shape, D, device=table.device, dtype=torch.float32)
+    n = torch.empty(*ids.shape, D, device=table.device, dtype=torch.bfloat16)
+    _timed("t5_embed_rms", 8.0 * M * D + 8.0 * M, lambda: _lib.call("vgpa_t5_rms", None, None, ids, table, V, w, x, n, 1, M, D, float(eps), _stream()), "byte")
+    return x, n
+
+
+def t5_gated_gelu(u):
+    """u bf16 [..., 2 d_ff] (the output of one GEMM against wi_0 | wi_1) -> bf16 [..., d_ff] = gelu_new(u[..., :d_ff]) * u[..., d_ff:]"""
+    _req(u, torch.bfloat16)
+    _t5_forward_only("t5_gated_gelu", u)
+    F2 = u.shape[-1]
+    if F2 % 16 or u.numel() == 0:
+        raise RuntimeError(f"t5_gated_gelu: the last dim holds both halves, d_ff a multiple of 8; got {tuple(u.shape)}")
+    g = torch.empty(*u.shape[:-1], F2 // 2, device=u.device, dtype=torch.bfloat16)
+    _timed("t5_gated_gelu", 3.0 * u.numel(), lambda: _lib.call("vgpa_t5_gated_gelu", u, g, u.numel() // F2, F2 // 2, _stream()), "byte")
+    return g

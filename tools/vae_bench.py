@@ -5,15 +5,9 @@ median of 20 timed runs.  Each row is split with ops.KernelTimer (event pairs ar
 GroupNorm passes (statistics + apply) and the rest = the untimed median minus those two: the layout and sampling kernels, torch's tile crops, blends
 and concatenations, and the gaps between launches.  TFLOP/s is over the algorithmic FLOPs of the convolutions (true Cin = 3 for the stem).
     python tools/vae_bench.py [--quick] [--json PATH]"""
-import json
-import os
-import statistics
-import sys
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+from vae_bench_common import main, median_ms, seeded_vae
 
 F32_MATRIX_PEAK = 157.3e12
 CFG3_STEP_S = 4.39          # VERDICT.md: BASELINE configs[2], the I2V training step this encode is part of
@@ -36,36 +30,10 @@ def conv_flops(vae, B, H, W):
     return B * fl
 
 
-def _median_ms(f, warmup, runs):
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        f()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms), min(ms), max(ms)
-
-
 def run(dev, quick=False, height=480, width=720):
     from videogpa_amd import ops
-    from videogpa_amd.vae import AutoencoderKLCogVideoX
     warmup, runs, split_runs = (2, 5, 2) if quick else (5, 20, 3)
-    g = torch.Generator().manual_seed(0)
-    vae = AutoencoderKLCogVideoX()
-    with torch.no_grad():
-        for name, p in vae.named_parameters():          # O(1) activations: He-scaled convolutions over the 27 taps one frame fills, GroupNorm near identity
-            if p.dim() >= 4:
-                p.copy_(torch.randn(p.shape, generator=g) * (1.0 / p[0].numel()) ** 0.5)
-            elif "norm" in name and name.endswith("weight"):
-                p.copy_(1.0 + 0.2 * torch.randn(p.shape, generator=g))
-            else:
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-    vae = vae.to(device=dev, dtype=torch.bfloat16).requires_grad_(False).eval()
+    vae, g = seeded_vae(dev)
     rows = {"height": height, "width": width, "warmup": warmup, "runs": runs, "cfg3_step_s": CFG3_STEP_S, "cases": {}}
     with torch.no_grad():
         for tiled in (False, True):
@@ -74,7 +42,7 @@ def run(dev, quick=False, height=480, width=720):
                 x = (torch.rand(B, 3, 1, height, width, generator=g) * 2 - 1).to(device=dev, dtype=torch.bfloat16)
                 f = lambda: vae.encode(x).latent_dist.sample()
                 torch.cuda.reset_peak_memory_stats(dev)
-                med, lo, hi = _median_ms(f, warmup, runs)
+                med, lo, hi = median_ms(f, warmup, runs)
                 peak_gb = torch.cuda.max_memory_allocated(dev) / 1e9
                 ops.TIMER = ops.KernelTimer()
                 try:
@@ -102,15 +70,4 @@ def run(dev, quick=False, height=480, width=720):
 
 
 if __name__ == "__main__":
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--json", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("vae_bench.py measures on the GPU: no device found")
-    out = run(torch.device("cuda", 0), a.quick)
-    if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(out, f, indent=1)
+    main("vae_bench.py", run, print_json=False)             # the rows are printed as they are measured

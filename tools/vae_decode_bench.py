@@ -7,56 +7,16 @@ and tiling on as generate/CogVideoX-5B.py sets them, through generate.decode_lat
                           as the decode calls it, and ops.conv3x3_pad_f32 on an already up-sampled [N * T',2H,2W,C] map, so the same output M; median
                           HIP-event ms, TFLOP/s of each, and their ratio (the loader reads a quarter of the rows the plain convolution reads)
     python tools/vae_decode_bench.py [--quick] [--json PATH]"""
-import json
-import os
-import statistics
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _median_ms(f, warmup, runs):
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        f()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms)
-
-
-def _seeded_vae(dev):
-    from videogpa_amd.vae import AutoencoderKLCogVideoX
-    g = torch.Generator().manual_seed(0)
-    vae = AutoencoderKLCogVideoX(with_decoder=True)
-    with torch.no_grad():
-        for name, p in vae.named_parameters():          # O(1) activations: He-scaled convolutions, norms near identity, conv_y around 1, conv_b small
-            if ".conv_y." in name or ".conv_b." in name:
-                p.copy_((1.0 if name.endswith("conv_y.conv.bias") else 0.0) + 0.1 * torch.randn(p.shape, generator=g) / (4.0 if p.dim() > 1 else 1.0))
-            elif p.dim() >= 4:
-                p.copy_(torch.randn(p.shape, generator=g) * (1.0 / p[0].numel()) ** 0.5)
-            elif "norm" in name and name.endswith("weight"):
-                p.copy_(1.0 + 0.2 * torch.randn(p.shape, generator=g))
-            else:
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-    vae = vae.to(device=dev, dtype=torch.bfloat16).requires_grad_(False).eval()
-    vae.enable_slicing()
-    vae.enable_tiling()
-    return vae, g
+from vae_bench_common import clip_seconds, kernel_entries, main, median_ms, seeded_vae
 
 
 def run(dev, quick=False, latent_frames=13, height=60, width=90):
     from videogpa_amd import generate, ops
-    vae, g = _seeded_vae(dev)
+    vae, g = seeded_vae(dev, with_decoder=True)
+    vae.enable_slicing()
+    vae.enable_tiling()
     warmup, runs, shape_runs = (1, 1, 3) if quick else (1, 3, 7)
     latents = (0.7 * torch.randn(1, latent_frames, 16, height, width, generator=g)).to(device=dev, dtype=vae.dtype)
     decode = lambda: generate.decode_latents(vae, latents)
@@ -79,32 +39,8 @@ def run(dev, quick=False, latent_frames=13, height=60, width=90):
         out["frames_shape"] = list(frames.shape)
         out["frames_finite"] = bool(torch.isfinite(frames.float()).all())
         del frames
-        for _ in range(warmup - 1):
-            decode()
-        torch.cuda.synchronize()
-        secs = []
-        for _ in range(runs):
-            torch.cuda.reset_peak_memory_stats(dev)
-            t0 = time.perf_counter()
-            decode()
-            torch.cuda.synchronize()
-            secs.append(time.perf_counter() - t0)
-        out["seconds_per_clip"] = statistics.median(secs)
-        out["seconds_min_max"] = [min(secs), max(secs)]
-        out["peak_allocated_gb"] = torch.cuda.max_memory_allocated(dev) / 1e9
-        ops.TIMER = ops.KernelTimer()
-        try:
-            decode()
-            torch.cuda.synchronize()
-            summary = ops.TIMER.summary()
-        finally:
-            ops.TIMER = None
-        out["entries"] = {}
-        for name, s in summary.items():
-            rate = s["work_per_launch"] * s["launches"] / (s["total_ms"] * 1e-3)
-            out["entries"][name] = {"launches": s["launches"], "total_ms": s["total_ms"],
-                                    ("tflops" if s["unit"] == "flop" else "gbytes_per_s"): rate / (1e12 if s["unit"] == "flop" else 1e9)}
-        out["conv_tflop_per_clip"] = sum(s["work_per_launch"] * s["launches"] for s in summary.values() if s["unit"] == "flop") / 1e12
+        out.update(clip_seconds(decode, dev, warmup - 1, runs))
+        out.update(kernel_entries(decode))
         # the up-sampler against the plain chunked convolution at the same output M: the largest call of each of the three up-sampling blocks
         out["upsamplers"] = []
         by_width = {}
@@ -116,9 +52,9 @@ def run(dev, quick=False, latent_frames=13, height=60, width=90):
             N, T, H, W, C, ct = key
             To = ops.vae_upsample_frames(T, ct)
             x, w, b = torch.randn(N, T, H, W, C, device=dev), torch.randn(3, 3, C, C, device=dev) * 0.02, torch.zeros(C, device=dev)
-            ms_up = _median_ms(lambda: ops.vae_upsample_f32(x, w, b, compress_time=ct), 2, shape_runs)
+            ms_up = median_ms(lambda: ops.vae_upsample_f32(x, w, b, compress_time=ct), 2, shape_runs)[0]
             x2 = torch.randn(N * To, 2 * H, 2 * W, C, device=dev)
-            ms_2d = _median_ms(lambda: ops.conv3x3_pad_f32(x2, w, b), 2, shape_runs)
+            ms_2d = median_ms(lambda: ops.conv3x3_pad_f32(x2, w, b), 2, shape_runs)[0]
             flop = 2.0 * N * To * 4 * H * W * 9 * C * C
             out["upsamplers"].append({"N": N, "T": T, "T_out": To, "H": H, "W": W, "C": C, "compress_time": ct,
                                       "calls_per_clip": sum(c for k, c in calls.items() if (k[4], k[5]) == (C, ct)),
@@ -129,16 +65,4 @@ def run(dev, quick=False, latent_frames=13, height=60, width=90):
 
 
 if __name__ == "__main__":
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--json", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("vae_decode_bench.py measures on the GPU: no device found")
-    res = run(torch.device("cuda", 0), a.quick)
-    print(json.dumps(res))
-    if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    main("vae_decode_bench.py", run)

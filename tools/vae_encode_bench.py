@@ -7,54 +7,16 @@
                           as the encode calls it, and ops.conv3x3_pad_f32 (the 2-D chunked kernel) at the same (Cin,Cout,H,W) over N * T frames, so the same
                           M; median HIP-event ms, TFLOP/s of each, and their ratio (expected >= 0.9: the same core with a longer K loop)
     python tools/vae_encode_bench.py [--quick] [--json PATH]"""
-import json
-import os
-import statistics
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-
-
-def _median_ms(f, warmup, runs):
-    for _ in range(warmup):
-        f()
-    torch.cuda.synchronize()
-    ms = []
-    for _ in range(runs):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        f()
-        e1.record()
-        torch.cuda.synchronize()
-        ms.append(e0.elapsed_time(e1))
-    return statistics.median(ms)
-
-
-def _seeded_vae(dev):
-    from videogpa_amd.vae import AutoencoderKLCogVideoX
-    g = torch.Generator().manual_seed(0)
-    vae = AutoencoderKLCogVideoX()
-    with torch.no_grad():
-        for name, p in vae.named_parameters():          # O(1) activations: He-scaled convolutions, GroupNorm near identity
-            if p.dim() >= 4:
-                p.copy_(torch.randn(p.shape, generator=g) * (1.0 / p[0].numel()) ** 0.5)
-            elif "norm" in name and name.endswith("weight"):
-                p.copy_(1.0 + 0.2 * torch.randn(p.shape, generator=g))
-            else:
-                p.copy_(0.1 * torch.randn(p.shape, generator=g))
-    vae = vae.to(device=dev, dtype=torch.bfloat16).requires_grad_(False).eval()
-    vae.enable_slicing()
-    vae.enable_tiling()
-    return vae, g
+from vae_bench_common import clip_seconds, kernel_entries, main, median_ms, seeded_vae
 
 
 def run(dev, quick=False, frames=49, height=480, width=720, top=8):
     from videogpa_amd import ops
-    vae, g = _seeded_vae(dev)
+    vae, g = seeded_vae(dev)
+    vae.enable_slicing()
+    vae.enable_tiling()
     warmup, runs, shape_runs = (1, 1, 3) if quick else (1, 3, 7)
     v = (torch.rand(1, 3, frames, height, width, generator=g) * 2 - 1).to(dev)
     encode = lambda: vae.encode(v.to(vae.dtype)).latent_dist.sample()
@@ -73,32 +35,8 @@ def run(dev, quick=False, frames=49, height=480, width=720, top=8):
         finally:
             ops.conv3d_causal_f32 = real
         out["latent_shape"] = list(z.shape)
-        for _ in range(warmup - 1):
-            encode()
-        torch.cuda.synchronize()
-        secs = []
-        for _ in range(runs):
-            torch.cuda.reset_peak_memory_stats(dev)
-            t0 = time.perf_counter()
-            encode()
-            torch.cuda.synchronize()
-            secs.append(time.perf_counter() - t0)
-        out["seconds_per_clip"] = statistics.median(secs)
-        out["seconds_min_max"] = [min(secs), max(secs)]
-        out["peak_allocated_gb"] = torch.cuda.max_memory_allocated(dev) / 1e9
-        ops.TIMER = ops.KernelTimer()
-        try:
-            encode()
-            torch.cuda.synchronize()
-            summary = ops.TIMER.summary()
-        finally:
-            ops.TIMER = None
-        out["entries"] = {}
-        for name, s in summary.items():
-            rate = s["work_per_launch"] * s["launches"] / (s["total_ms"] * 1e-3)
-            out["entries"][name] = {"launches": s["launches"], "total_ms": s["total_ms"],
-                                    ("tflops" if s["unit"] == "flop" else "gbytes_per_s"): rate / (1e12 if s["unit"] == "flop" else 1e9)}
-        out["conv_tflop_per_clip"] = sum(s["work_per_launch"] * s["launches"] for s in summary.values() if s["unit"] == "flop") / 1e12
+        out.update(clip_seconds(encode, dev, warmup - 1, runs))
+        out.update(kernel_entries(encode))
         # the 3-D kernel against the 2-D chunked one at the same widths and the same M, heaviest shapes first
         flop = lambda k: 2.0 * k[0] * k[1] * k[2] * k[3] * k[5] * 27 * k[4]
         out["shapes"] = []
@@ -106,9 +44,9 @@ def run(dev, quick=False, frames=49, height=480, width=720, top=8):
             N, T, H, W, Cin, Cout = key
             x = torch.randn(N, T, H, W, Cin, device=dev)
             w3, w2, b = torch.randn(3, 3, 3, Cin, Cout, device=dev) * 0.02, torch.randn(3, 3, Cin, Cout, device=dev) * 0.02, torch.zeros(Cout, device=dev)
-            ms3 = _median_ms(lambda: ops.conv3d_causal_f32(x, w3, b), 2, shape_runs)
+            ms3 = median_ms(lambda: ops.conv3d_causal_f32(x, w3, b), 2, shape_runs)[0]
             x2 = x.view(N * T, H, W, Cin)
-            ms2 = _median_ms(lambda: ops.conv3x3_pad_f32(x2, w2, b), 2, shape_runs)
+            ms2 = median_ms(lambda: ops.conv3x3_pad_f32(x2, w2, b), 2, shape_runs)[0]
             tf3, tf2 = flop(key) / ms3 / 1e9, flop(key) / 3 / ms2 / 1e9
             out["shapes"].append({"N": N, "T": T, "H": H, "W": W, "Cin": Cin, "Cout": Cout, "calls_per_clip": calls[key],
                                   "share_of_conv3d_flop": flop(key) * calls[key] / sum(flop(k) * c for k, c in calls.items()),
@@ -118,16 +56,4 @@ def run(dev, quick=False, frames=49, height=480, width=720, top=8):
 
 
 if __name__ == "__main__":
-    import argparse
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--quick", action="store_true")
-    ap.add_argument("--json", default=None)
-    a = ap.parse_args()
-    if not torch.cuda.is_available():
-        raise SystemExit("vae_encode_bench.py measures on the GPU: no device found")
-    res = run(torch.device("cuda", 0), a.quick)
-    print(json.dumps(res))
-    if a.json:
-        os.makedirs(os.path.dirname(os.path.abspath(a.json)), exist_ok=True)
-        with open(a.json, "w") as f:
-            json.dump(res, f, indent=1)
+    main("vae_encode_bench.py", run)

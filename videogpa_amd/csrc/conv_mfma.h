@@ -1,4 +1,5 @@
-// The exact-fp32 MFMA convolution core shared by csrc/vggt_heads.hip and csrc/dualdpt.hip: conv_kernel<.., MODE> and its launcher.
+// The exact-fp32 MFMA convolution core: conv_kernel<.., MODE>, its launcher and the argument checks the entry points share.  Instantiated by
+// csrc/vggt_heads.hip (CV_CONV, CV_TAIL), csrc/dualdpt.hip (CV_AUX_TAIL) and csrc/vae_conv.hip (the four chunked modes of the CogVideoX VAE).
 //   CV_CONV      3x3 (stride 1 | 2; pad 1, or one-sided: ConvArgs.pad) or 1x1 convolution with the fused ReLU / bias / residual adds
 //   CV_CONV_CHUNKED  the same convolution with its K sum cut into runs of CV_CHUNK_ITERS * 16 products: every run starts from zero and is added to a
 //                second accumulator when it ends.  One chain of n fp32 additions carries a rounding error that grows like sqrt(n) times the size of the
@@ -427,4 +428,24 @@ static int32_t conv_launch(const ConvArgs& a, hipStream_t stream) {
     }
     VGPA_CHECK_LAUNCH();
     return VGPA_OK;
+}
+
+// The plain 2-D entry (CV_CONV, CV_CONV_CHUNKED): the checks, the ConvArgs fill and the launch of x [N,H,W,Cin] under a ksize x ksize window with pad_lo zero
+// rows / columns in front and pad_hi behind
+template <int MODE>
+static int32_t conv_entry(const float* x, const float* w, const float* bias, const float* res, const float* res2, float* out, int64_t N, int64_t H,
+                          int64_t W, int64_t Cin, int64_t Cout, int ksize, int64_t stride, int pad_lo, int pad_hi, int32_t flags, hipStream_t stream) {
+    if (!x || !w || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
+    if ((stride != 1 && stride != 2) || (flags & ~(CV_RELU_IN | CV_RELU_RES)) || H > (1 << 30) || W > (1 << 30) || Cin > (1 << 20) || Cout > (1 << 20))
+        return VGPA_ERR_INVALID;
+    if (!aligned16(x) || !aligned16(w)) return VGPA_ERR_INVALID;
+    ConvArgs a = {};
+    a.x = x; a.w = w; a.bias = bias; a.res = res; a.res2 = res2; a.out = out;
+    a.N = (int)N; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout; a.ksize = ksize; a.stride = (int)stride; a.flags = flags;
+    a.pad = pad_lo;
+    if (H + pad_lo + pad_hi < ksize || W + pad_lo + pad_hi < ksize) return VGPA_ERR_INVALID;
+    a.Ho = (int)((H + pad_lo + pad_hi - ksize) / stride + 1);          // the centred 3x3 (pad 1 | 1): (H - 1) / stride + 1; the 1x1: H
+    a.Wo = (int)((W + pad_lo + pad_hi - ksize) / stride + 1);
+    a.M = N * a.Ho * a.Wo;
+    return conv_launch<MODE>(a, stream);
 }

@@ -1,5 +1,5 @@
-// CogVideoX VAE encoder on one frame (diffusers' autoencoder_kl_cogvideox.py), the part around its convolutions, which run on conv_kernel of
-// vggt_heads.hip (the 3-D causal kernels fold into 2-D ones at load time: videogpa_amd/vae.py; on a clip they are its CV_CONV3D and CV_POOL_DOWN modes, and
+// CogVideoX VAE encoder on one frame (diffusers' autoencoder_kl_cogvideox.py), the part around its convolutions, which run on conv_kernel through the
+// entry points of vae_conv.hip (the 3-D causal kernels fold into 2-D ones at load time: videogpa_amd/vae.py; on a clip they are its CV_CONV3D and CV_POOL_DOWN modes, and
 // the kernels below see the clip's frames as part of the pixel extent HW).  Everything fp32, channels-last (NHWC), forward only:
 //   vae_input_kernel     layout change in front of conv_in: [N,3,H,W] fp32 | bf16 -> [N,H,W,16] fp32, channels 3..15 = 0, so that the stem is a 16-channel
 //                        convolution with zero weight rows

@@ -3,12 +3,6 @@
 //   conv_kernel<.., CV_CONV>        3x3 (stride 1 | 2, pad 1, or 0 | 1 in front and 0 | 1 behind) or 1x1 convolution as an implicit GEMM on v_mfma_f32_32x32x2_f32 (exact fp32:
 //                                   a k-ordered fmaf chain, only the summation order differs from torch's conv2d), with the fused pieces a
 //                                   ResidualConvUnit / FeatureFusionBlock needs: out = conv(relu?(x)) + bias? + relu?(res)? + res2?
-//   conv_kernel<.., CV_CONV_CHUNKED> the convolution of the CogVideoX VAE encoder (vgpa_conv3x3_pad_f32): padding per side, and the K sum in short runs
-//                                   (conv_mfma.h), because its outputs are held to a bound that one chain of 9 * 512 fp32 additions does not meet
-//   conv_kernel<.., CV_CONV3D>      the encoder's causal 3x3x3 convolution over the frames of a chunk (vgpa_conv3x3x3_causal_f32) and
-//   conv_kernel<.., CV_POOL_DOWN>   its downsampler with the temporal pooling in the loader (vgpa_vae_downsample_f32): the chunked core again
-//   conv_kernel<.., CV_UP2X>        the decoder's up-sampler (vgpa_vae_upsample_f32): the chunked core over the nearest x2 map (x4 with time), which only
-//                                   the loader's index arithmetic forms
 //   conv_kernel<.., CV_TAIL>        the end of DPTHead._forward_impl (dpt_head.py:229-247) in one launch on the same core: the loader samples the
 //                                   [N,h,w,C] map bilinearly (align_corners=True) at the (H,W) grid and adds the 0.1-scaled UV positional
 //                                   embedding from two separable tables; the epilogue is bias + ReLU, the 1x1 conv 32 -> output_dim, activate_head.
@@ -16,7 +10,8 @@
 //   upsample_kernel                 NHWC align_corners=True bilinear resize (+ the same separable embedding)
 //   attn_small_kernel               fp32 softmax attention of the camera trunk, S <= 128 tokens, one workgroup per (batch, head)
 //
-// The convolution core, with its GEMM view, tile shapes and LDS layout, lives in conv_mfma.h (csrc/dualdpt.hip instantiates a third mode of it).
+// The convolution core, with its GEMM view, tile shapes and LDS layout, lives in conv_mfma.h (csrc/dualdpt.hip instantiates a third mode of it,
+// csrc/vae_conv.hip the chunked modes of the CogVideoX VAE).
 #include "conv_mfma.h"
 
 __global__ __launch_bounds__(256) void upsample_kernel(const float* __restrict__ x, int h, int w, int C, int Ho, int Wo, float sy, float sx,
@@ -92,24 +87,6 @@ __global__ __launch_bounds__(AT_THREADS) void attn_small_kernel(const float* __r
     }
 }
 
-template <int MODE>
-static int32_t conv_entry(const float* x, const float* w, const float* bias, const float* res, const float* res2, float* out, int64_t N, int64_t H,
-                          int64_t W, int64_t Cin, int64_t Cout, int ksize, int64_t stride, int pad_lo, int pad_hi, int32_t flags, hipStream_t stream) {
-    if (!x || !w || !out || N <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
-    if ((stride != 1 && stride != 2) || (flags & ~(CV_RELU_IN | CV_RELU_RES)) || H > (1 << 30) || W > (1 << 30) || Cin > (1 << 20) || Cout > (1 << 20))
-        return VGPA_ERR_INVALID;
-    if (!aligned16(x) || !aligned16(w)) return VGPA_ERR_INVALID;
-    ConvArgs a = {};
-    a.x = x; a.w = w; a.bias = bias; a.res = res; a.res2 = res2; a.out = out;
-    a.N = (int)N; a.H = (int)H; a.W = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout; a.ksize = ksize; a.stride = (int)stride; a.flags = flags;
-    a.pad = pad_lo;
-    if (H + pad_lo + pad_hi < ksize || W + pad_lo + pad_hi < ksize) return VGPA_ERR_INVALID;
-    a.Ho = (int)((H + pad_lo + pad_hi - ksize) / stride + 1);          // the centred 3x3 (pad 1 | 1): (H - 1) / stride + 1; the 1x1: H
-    a.Wo = (int)((W + pad_lo + pad_hi - ksize) / stride + 1);
-    a.M = N * a.Ho * a.Wo;
-    return conv_launch<MODE>(a, stream);
-}
-
 extern "C" {
 
 int32_t vgpa_conv3x3_f32(const float* x, const float* w_packed, const float* bias, const float* res, const float* res2, float* out, int64_t N,
@@ -120,59 +97,6 @@ int32_t vgpa_conv3x3_f32(const float* x, const float* w_packed, const float* bia
 int32_t vgpa_conv1x1_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t M, int64_t Cin, int64_t Cout,
                          hipStream_t stream) {
     return conv_entry<CV_CONV>(x, w_packed, bias, nullptr, nullptr, out, 1, 1, M, Cin, Cout, 1, 1, 0, 0, 0, stream);
-}
-
-int32_t vgpa_conv3x3_pad_f32(const float* x, const float* w_packed, const float* bias, const float* res, float* out, int64_t N, int64_t H, int64_t W,
-                             int64_t Cin, int64_t Cout, int64_t stride, int32_t pad_lo, int32_t pad_hi, hipStream_t stream) {
-    if (pad_lo < 0 || pad_lo > 1 || pad_hi < 0 || pad_hi > 1) return VGPA_ERR_INVALID;
-    return conv_entry<CV_CONV_CHUNKED>(x, w_packed, bias, res, nullptr, out, N, H, W, Cin, Cout, 3, stride, pad_lo, pad_hi, 0, stream);
-}
-
-// The causal 3x3x3 convolution over the frames of a chunk (videogpa_amd/vae.py): only the loader knows about time, see CV_CONV3D in conv_mfma.h
-int32_t vgpa_conv3x3x3_causal_f32(const float* x, const float* prev, const float* w_packed, const float* bias, const float* res, float* out, int64_t N,
-                                  int64_t T, int64_t H, int64_t W, int64_t Cin, int64_t Cout, hipStream_t stream) {
-    if (!x || !w_packed || !out || N <= 0 || T <= 0 || H <= 0 || W <= 0 || Cin <= 0 || Cout <= 0 || (Cin & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
-    if (N > (1 << 20) || T > (1 << 20) || H > (1 << 20) || W > (1 << 20) || Cin > (1 << 20) || Cout > (1 << 20) || N * T > (1 << 30)) return VGPA_ERR_INVALID;
-    if (!aligned16(x) || !aligned16(prev) || !aligned16(w_packed) || out == x || out == prev) return VGPA_ERR_INVALID;
-    ConvArgs a = {};
-    a.x = x; a.prev = prev; a.w = w_packed; a.bias = bias; a.res = res; a.out = out;
-    a.N = (int)N; a.T = (int)T; a.H = a.Ho = (int)H; a.W = a.Wo = (int)W; a.Cin = (int)Cin; a.Cout = (int)Cout; a.ksize = 3; a.stride = 1; a.pad = 1;
-    a.M = N * T * H * W;
-    return conv_launch<CV_CONV3D>(a, stream);
-}
-
-// CogVideoXDownsample3D in one launch: the one-sided stride-2 convolution above over N * T' frames, whose loader pools the frame pairs (CV_POOL_DOWN)
-int32_t vgpa_vae_downsample_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t N, int64_t T, int64_t H, int64_t W,
-                                int64_t C, int64_t Cout, int32_t compress_time, hipStream_t stream) {
-    if (!x || !w_packed || !out || N <= 0 || T <= 0 || H < 2 || W < 2 || C <= 0 || Cout <= 0 || (C & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
-    if (N > (1 << 20) || T > (1 << 20) || H > (1 << 20) || W > (1 << 20) || C > (1 << 20) || Cout > (1 << 20) || N * T > (1 << 30)) return VGPA_ERR_INVALID;
-    if ((compress_time != 0 && compress_time != 1) || !aligned16(x) || !aligned16(w_packed) || out == x) return VGPA_ERR_INVALID;
-    if (!compress_time || T == 1)                                          // nothing to pool: the frames are samples of the 2-D convolution
-        return conv_entry<CV_CONV_CHUNKED>(x, w_packed, bias, nullptr, nullptr, out, N * T, H, W, C, Cout, 3, 2, 0, 1, 0, stream);
-    ConvArgs a = {};
-    a.x = x; a.w = w_packed; a.bias = bias; a.out = out;
-    a.Tin = (int)T; a.T = (int)((T + 1) / 2);
-    a.N = (int)(N * a.T); a.H = (int)H; a.W = (int)W; a.Cin = (int)C; a.Cout = (int)Cout; a.ksize = 3; a.stride = 2; a.pad = 0;
-    a.Ho = (int)((H + 1 - 3) / 2 + 1);                                     // one zero row / column behind the last, none in front
-    a.Wo = (int)((W + 1 - 3) / 2 + 1);
-    a.M = (int64_t)a.N * a.Ho * a.Wo;
-    return conv_launch<CV_POOL_DOWN>(a, stream);
-}
-
-// CogVideoXUpsample3D in one launch: the 3x3 padding-1 convolution over N * T' frames of 2H x 2W whose loader reads the source at half the index (CV_UP2X)
-int32_t vgpa_vae_upsample_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t N, int64_t T, int64_t H, int64_t W,
-                              int64_t C, int64_t Cout, int32_t compress_time, hipStream_t stream) {
-    if (!x || !w_packed || !out || N <= 0 || T <= 0 || H <= 0 || W <= 0 || C <= 0 || Cout <= 0 || (C & 15) || (Cout & 15)) return VGPA_ERR_INVALID;
-    if (N > (1 << 20) || T > (1 << 20) || H > (1 << 20) || W > (1 << 20) || C > (1 << 20) || Cout > (1 << 20) || N * T > (1 << 29)) return VGPA_ERR_INVALID;
-    if ((compress_time != 0 && compress_time != 1) || !aligned16(x) || !aligned16(w_packed) || out == x) return VGPA_ERR_INVALID;
-    ConvArgs a = {};
-    a.x = x; a.w = w_packed; a.bias = bias; a.out = out;
-    a.Tin = (int)T;
-    a.T = (int)(!compress_time || T == 1 ? T : (T & 1) ? 2 * T - 1 : 2 * T);   // an odd count keeps frame 0 single
-    a.N = (int)(N * a.T); a.H = (int)H; a.W = (int)W; a.Ho = (int)(2 * H); a.Wo = (int)(2 * W);
-    a.Cin = (int)C; a.Cout = (int)Cout; a.ksize = 3; a.stride = 1; a.pad = 1;
-    a.M = (int64_t)a.N * a.Ho * a.Wo;
-    return conv_launch<CV_UP2X>(a, stream);
 }
 
 int32_t vgpa_dpt_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* w2,

@@ -1400,20 +1400,28 @@ def pack_conv_weight(w):
     return w.detach().float().permute(2, 3, 1, 0).contiguous()
 
 
+def _conv_out(name, x, w_packed, taps, out_shape, *res, refuse=None):
+    """what the convolution wrappers share: w_packed must be [*taps, Cin, Cout] for x's Cin channels, both widths multiples of 16; returns the empty fp32
+    output [*out_shape, Cout], whose shape every residual that is given must have.  `refuse` is the wrapper's own complaint about the call's geometry,
+    raised behind the weight check (out_shape is not looked at then)"""
+    Cin, Cout = x.shape[-1], w_packed.shape[-1]
+    if tuple(w_packed.shape) != (*taps, Cin, Cout) or Cin % 16 or Cout % 16:
+        raise RuntimeError(f"{name}: weight {tuple(w_packed.shape)} does not fit input channels {Cin} (multiples of 16)")
+    if refuse:
+        raise RuntimeError(f"{name}: {refuse}")
+    out = torch.empty(*out_shape, Cout, device=x.device, dtype=torch.float32)
+    if any(r is not None and r.shape != out.shape for r in res):
+        raise RuntimeError(f"{name}: residual shape differs from the output's")
+    return out
+
+
 def conv3x3_f32(x, w_packed, bias=None, res=None, res2=None, relu_in=False, relu_res=False, stride=1):
     """x [N,H,W,Cin] -> conv3x3(relu?(x), pad 1, stride) + bias? + relu?(res)? + res2? as [N,Ho,Wo,Cout]; w_packed [3,3,Cin,Cout]"""
     _heads_in(x, w_packed, bias, res, res2)
     N, H, W, Cin = x.shape
-    Cout = w_packed.shape[-1]
-    if tuple(w_packed.shape) != (3, 3, Cin, Cout) or Cin % 16 or Cout % 16:
-        raise RuntimeError(f"conv3x3_f32: weight {tuple(w_packed.shape)} does not fit input channels {Cin} (multiples of 16)")
-    Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
-    out = torch.empty(N, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
-    for r in (res, res2):
-        if r is not None and r.shape != out.shape:
-            raise RuntimeError("conv3x3_f32: residual shape differs from the output's")
+    out = _conv_out("conv3x3_f32", x, w_packed, (3, 3), (N, (H - 1) // stride + 1, (W - 1) // stride + 1), res, res2)
     _timed("conv3x3_f32", 2.0 * out.numel() * 9 * Cin,
-           lambda: _lib.call("vgpa_conv3x3_f32", x, w_packed, bias, res, res2, out, N, H, W, Cin, Cout, stride,
+           lambda: _lib.call("vgpa_conv3x3_f32", x, w_packed, bias, res, res2, out, N, H, W, Cin, out.shape[-1], stride,
                              (1 if relu_in else 0) | (2 if relu_res else 0), _stream()))
     return out
 
@@ -1651,7 +1659,7 @@ def lpips_layer_f32(f0, f1, w, relu=False, total=None, accumulate=False, out=Non
     return out
 
 
-# ---- CogVideoX VAE encoder around the convolutions (csrc/vae.hip): fp32, channels-last, forward only ---------------------------------------
+# ---- CogVideoX VAE encoder: its convolutions (csrc/vae_conv.hip) and what stands around them (csrc/vae.hip): fp32, channels-last, forward only ---
 def _dtype_code(dtype, name):
     if dtype not in (torch.float32, torch.bfloat16):
         raise RuntimeError(f"{name}: float32 or bfloat16, got {dtype}")
@@ -1665,17 +1673,12 @@ def conv3x3_pad_f32(x, w_packed, bias=None, res=None, stride=1, pad_lo=1, pad_hi
     error is a fraction of conv3x3_f32's single chain at the same speed class; the two agree to that rounding, not bit for bit."""
     _heads_in(x, w_packed, bias, res)
     N, H, W, Cin = x.shape
-    Cout = w_packed.shape[-1]
-    if tuple(w_packed.shape) != (3, 3, Cin, Cout) or Cin % 16 or Cout % 16:
-        raise RuntimeError(f"conv3x3_pad_f32: weight {tuple(w_packed.shape)} does not fit input channels {Cin} (multiples of 16)")
-    if stride not in (1, 2) or pad_lo not in (0, 1) or pad_hi not in (0, 1) or min(H, W) + pad_lo + pad_hi < 3:
-        raise RuntimeError(f"conv3x3_pad_f32: stride {stride}, padding ({pad_lo}, {pad_hi}) on a {H} x {W} map is not supported")
-    Ho, Wo = (H + pad_lo + pad_hi - 3) // stride + 1, (W + pad_lo + pad_hi - 3) // stride + 1
-    out = torch.empty(N, Ho, Wo, Cout, device=x.device, dtype=torch.float32)
-    if res is not None and res.shape != out.shape:
-        raise RuntimeError("conv3x3_pad_f32: residual shape differs from the output's")
+    bad = stride not in (1, 2) or pad_lo not in (0, 1) or pad_hi not in (0, 1) or min(H, W) + pad_lo + pad_hi < 3
+    out = _conv_out("conv3x3_pad_f32", x, w_packed, (3, 3),
+                    () if bad else (N, (H + pad_lo + pad_hi - 3) // stride + 1, (W + pad_lo + pad_hi - 3) // stride + 1), res,
+                    refuse=f"stride {stride}, padding ({pad_lo}, {pad_hi}) on a {H} x {W} map is not supported" if bad else None)
     _timed("conv3x3_pad_f32", 2.0 * out.numel() * 9 * Cin,
-           lambda: _lib.call("vgpa_conv3x3_pad_f32", x, w_packed, bias, res, out, N, H, W, Cin, Cout, stride, pad_lo, pad_hi, _stream()))
+           lambda: _lib.call("vgpa_conv3x3_pad_f32", x, w_packed, bias, res, out, N, H, W, Cin, out.shape[-1], stride, pad_lo, pad_hi, _stream()))
     return out
 
 
@@ -1694,16 +1697,11 @@ def conv3d_causal_f32(x, w_packed, bias=None, res=None, prev=None):
     if x.dim() != 5:
         raise RuntimeError(f"conv3d_causal_f32: expected [N,T,H,W,Cin], got {tuple(x.shape)}")
     N, T, H, W, Cin = x.shape
-    Cout = w_packed.shape[-1]
-    if tuple(w_packed.shape) != (3, 3, 3, Cin, Cout) or Cin % 16 or Cout % 16:
-        raise RuntimeError(f"conv3d_causal_f32: weight {tuple(w_packed.shape)} does not fit input channels {Cin} (multiples of 16)")
-    if prev is not None and tuple(prev.shape) != (N, 2, H, W, Cin):
-        raise RuntimeError(f"conv3d_causal_f32: prev {tuple(prev.shape)} is not [{N},2,{H},{W},{Cin}]")
-    out = torch.empty(N, T, H, W, Cout, device=x.device, dtype=torch.float32)
-    if res is not None and res.shape != out.shape:
-        raise RuntimeError("conv3d_causal_f32: residual shape differs from the output's")
+    bad = prev is not None and tuple(prev.shape) != (N, 2, H, W, Cin)
+    out = _conv_out("conv3d_causal_f32", x, w_packed, (3, 3, 3), (N, T, H, W), res,
+                    refuse=f"prev {tuple(prev.shape)} is not [{N},2,{H},{W},{Cin}]" if bad else None)
     _timed("conv3d_causal_f32", 2.0 * out.numel() * 27 * Cin,
-           lambda: _lib.call("vgpa_conv3x3x3_causal_f32", x, prev, w_packed, bias, res, out, N, T, H, W, Cin, Cout, _stream()))
+           lambda: _lib.call("vgpa_conv3x3x3_causal_f32", x, prev, w_packed, bias, res, out, N, T, H, W, Cin, out.shape[-1], _stream()))
     return out
 
 
@@ -1715,15 +1713,10 @@ def vae_downsample_f32(x, w_packed, bias=None, compress_time=True):
     if x.dim() != 5:
         raise RuntimeError(f"vae_downsample_f32: expected [N,T,H,W,C], got {tuple(x.shape)}")
     N, T, H, W, C = x.shape
-    Cout = w_packed.shape[-1]
-    if tuple(w_packed.shape) != (3, 3, C, Cout) or C % 16 or Cout % 16:
-        raise RuntimeError(f"vae_downsample_f32: weight {tuple(w_packed.shape)} does not fit input channels {C} (multiples of 16)")
-    if min(H, W) < 2:
-        raise RuntimeError(f"vae_downsample_f32: a {H} x {W} map is too small")
-    To = (T + 1) // 2 if compress_time else T
-    out = torch.empty(N, To, (H - 2) // 2 + 1, (W - 2) // 2 + 1, Cout, device=x.device, dtype=torch.float32)
+    out = _conv_out("vae_downsample_f32", x, w_packed, (3, 3), (N, (T + 1) // 2 if compress_time else T, (H - 2) // 2 + 1, (W - 2) // 2 + 1),
+                    refuse=f"a {H} x {W} map is too small" if min(H, W) < 2 else None)
     _timed("vae_downsample_f32", 2.0 * out.numel() * 9 * C,
-           lambda: _lib.call("vgpa_vae_downsample_f32", x, w_packed, bias, out, N, T, H, W, C, Cout, 1 if compress_time else 0, _stream()))
+           lambda: _lib.call("vgpa_vae_downsample_f32", x, w_packed, bias, out, N, T, H, W, C, out.shape[-1], 1 if compress_time else 0, _stream()))
     return out
 
 
@@ -1807,12 +1800,9 @@ def vae_upsample_f32(x, w_packed, bias=None, compress_time=True):
     if x.dim() != 5:
         raise RuntimeError(f"vae_upsample_f32: expected [N,T,H,W,C], got {tuple(x.shape)}")
     N, T, H, W, C = x.shape
-    Cout = w_packed.shape[-1]
-    if tuple(w_packed.shape) != (3, 3, C, Cout) or C % 16 or Cout % 16:
-        raise RuntimeError(f"vae_upsample_f32: weight {tuple(w_packed.shape)} does not fit input channels {C} (multiples of 16)")
-    out = torch.empty(N, vae_upsample_frames(T, compress_time), 2 * H, 2 * W, Cout, device=x.device, dtype=torch.float32)
+    out = _conv_out("vae_upsample_f32", x, w_packed, (3, 3), (N, vae_upsample_frames(T, compress_time), 2 * H, 2 * W))
     _timed("vae_upsample_f32", 2.0 * out.numel() * 9 * C,
-           lambda: _lib.call("vgpa_vae_upsample_f32", x, w_packed, bias, out, N, T, H, W, C, Cout, 1 if compress_time else 0, _stream()))
+           lambda: _lib.call("vgpa_vae_upsample_f32", x, w_packed, bias, out, N, T, H, W, C, out.shape[-1], 1 if compress_time else 0, _stream()))
     return out
 
 

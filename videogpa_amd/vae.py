@@ -1,6 +1,19 @@
-"""CogVideoX's VAE, encoder side, on the device: the drop-in for `diffusers.AutoencoderKLCogVideoX` where the reference's I2V trainer uses it --
+"""CogVideoX's VAE on the device: the drop-in for `diffusers.AutoencoderKLCogVideoX` where the reference uses it -- the encoder in the I2V trainer and in
+the offline data preparation, the decoder (opt-in) at the end of the generate scripts.
+
+SHARED by both sides.  Inference only, fp32 arithmetic, channels-last inside.  The convolutions run on the exact-fp32 MFMA core of the VGGT heads through
+the entry points of csrc/vae_conv.hip (`ops.conv3x3_pad_f32`: its form with the padding given per side, for the downsampler, and the K sum in short runs,
+for the accuracy bound of tests/test_gpu_vae.py; `ops.conv3d_causal_f32`, the 3x3x3 mode of the same core; `ops.conv1x1_f32` for the shortcuts);
+GroupNorm + SiLU, the 3-channel stem's layout change, the Gaussian epilogue, the spatial norm and the output kernel are csrc/vae.hip.  Each decision
+of diffusers' scheme is made once: the frame batches (`_ranges`) go one after the other through a whole network (`_batched`), every causal convolution
+reading the last two frames of its input in the batch before from the conv cache (`_ConvCache`; frame 0 twice in the first batch), GroupNorm over the
+batch's (T,H,W) per sample -- so the result DEPENDS on the batching, as upstream's does.  With tiling (`_tile_plan`, `_tiled`) every tile runs the frame
+batches with a cache of its own and the blends are per frame.  The resnet is one body (`_resnet`) under its folded 2-D, cached 3-D and spatially
+conditioned forms, and slicing is one loop (`_sliced`).
+
+The ENCODER, where the reference's I2V trainer uses it --
 `vae.encode(image[:, :, None]).latent_dist.sample() * vae.config.scaling_factor` inside every training step
-(train/CogVideoX-I2V-5B/03_train.py:94-97,121-128).
+(train/CogVideoX-I2V-5B/03_train.py:94-97,121-128):
 
     from videogpa_amd.vae import AutoencoderKLCogVideoX
     vae = AutoencoderKLCogVideoX.from_pretrained(model_path, subfolder="vae", torch_dtype=torch.bfloat16).cuda()
@@ -12,27 +25,23 @@ tiling on (train/CogVideoX-{5B,I2V-5B,1.5-5B}/02_encode.py):
 
     z = vae.encode(v.to(vae.dtype)).latent_dist.sample()                    # v [B,3,F,H,W], F = 4k + 1 -> [B,16,(F-1)/4+1,H/8,W/8]
 
-ONE frame: a causal 3-D convolution sees its only frame repeated in time, so each folds into a 2-D convolution whose weight is the sum of the
-temporal taps (in fp32, from the checkpoint's values), and the temporal pooling of the downsamplers is the identity.
-A CLIP of F = 4k + 1 frames (49, 81, 13, ...): diffusers' `_encode`, restated.  The frames go through the whole encoder in batches
-(`frame_batches`: num_sample_frames_batch_size = 8 frames each, the first one longer by F % 8), every causal convolution
-(`ops.conv3d_causal_f32`, the 3x3x3 mode of the same MFMA core) reading the last two frames of its input in the batch before from the conv
-cache (frame 0 twice in the first batch), GroupNorm over the batch's (T,H,W) per sample -- so the result DEPENDS on the batching, as upstream's
-does -- and down blocks 0 and 1 halving time inside the downsampler's loader (`ops.vae_downsample_f32`).  With tiling every tile runs the frame
-batches with a cache of its own and the blends are per frame.  Any other F > 1 (02_encode.py's "clip shorter than 49 frames, take what there is")
-raises NotImplementedError.
+ONE frame is a path of its own (`_moments`): a causal 3-D convolution sees its only frame repeated in time, so each folds into a 2-D convolution whose
+weight is the sum of the temporal taps (in fp32, from the checkpoint's values), and the temporal pooling of the downsamplers is the identity.
+A CLIP of F = 4k + 1 frames (49, 81, 13, ...) is diffusers' `_encode`, restated (`_chunk_moments` under `_batched`): batches of
+num_sample_frames_batch_size = 8 frames (`frame_batches`, the first one longer by F % 8), down blocks 0 and 1 halving time inside the downsampler's
+loader (`ops.vae_downsample_f32`).  Any other F > 1 (02_encode.py's "clip shorter than 49 frames, take what there is") raises NotImplementedError.
+Both walk the encoder through `_encoder_body`, with their own operations.  See DESIGN.md section 5f.
+
 The DECODER is opt-in, `AutoencoderKLCogVideoX(with_decoder=True, ...)` / `from_pretrained(..., with_decoder=True)`: the end of the reference's
 generate scripts (`pipe.vae.enable_tiling(); pipe.vae.enable_slicing()`, `output.frames`; videogpa_amd.generate.decode_latents),
 
     frames = vae.decode(latents.permute(0, 2, 1, 3, 4) / vae.config.scaling_factor).sample     # [B,16,13,60,90] -> [B,3,49,480,720]
 
-diffusers' `_decode` restated: batches of num_latent_frames_batch_size = 2 latent frames (`latent_frame_batches`, the first longer by F % 2) through the
-whole decoder with the conv cache, every norm a spatial norm conditioned on the batch's latent (`ops.spatial_norm_silu_f32`: the modulation maps stay at
-latent resolution), the up-samplers of blocks 0 and 1 doubling time inside the loader (`ops.vae_upsample_f32`), `tiled_decode` over latent tiles
+diffusers' `_decode` restated (`_chunk_frames` under `_batched`): batches of num_latent_frames_batch_size = 2 latent frames (`latent_frame_batches`, the
+first longer by F % 2), every norm a spatial norm conditioned on the batch's latent (`ops.spatial_norm_silu_f32`: the modulation maps stay at latent
+resolution), the up-samplers of blocks 0 and 1 doubling time inside the loader (`ops.vae_upsample_f32`), `tiled_decode` over latent tiles
 (`decode_tile_plan`).  Without the keyword the module is the encoder side alone: `decoder.*` is dropped on load and `decode` raises.  See DESIGN.md
-section 5g.  Inference only, fp32 arithmetic, channels-last inside: the
-convolutions run on the exact-fp32 MFMA kernel of the VGGT heads (`ops.conv3x3_pad_f32`: its form with the padding given per side, for the
-downsampler, and the K sum in short runs, for the accuracy bound of tests/test_gpu_vae.py; `ops.conv1x1_f32` for the shortcuts), GroupNorm + SiLU, the 3-channel stem's layout change and the Gaussian epilogue on csrc/vae.hip.  See DESIGN.md section 5f.
+section 5g.
 
 PARITY UNPINNED (diffusers is neither installed nor vendored): the network, its parameter names, the tiled-encode scheme, the frame batching and
 the conv-cache scheme are restated from diffusers' autoencoder_kl_cogvideox.py.  The loader is strict, so the first real checkpoint shows at once if a name here is wrong."""
@@ -104,6 +113,11 @@ class _Encoder3D(nn.Module):
         self.norm_out = nn.GroupNorm(groups, chans[-1], eps=eps)
         self.conv_out = _CausalConv3d(chans[-1], 2 * cfg.latent_channels)
 
+    def resnets(self):
+        """(cache name, resnet) in the order of the forward pass"""
+        return [(f"down_blocks.{i}.resnets.{j}", r) for i, b in enumerate(self.down_blocks) for j, r in enumerate(b.resnets)] + \
+               [(f"mid_block.resnets.{j}", r) for j, r in enumerate(self.mid_block.resnets)]
+
 
 class _SpatialNorm3D(nn.Module):
     """CogVideoXSpatialNorm3D(C, L): GroupNorm(f) * conv_y(zq) + conv_b(zq), zq the latent resized to f; its GroupNorm's eps is 1e-6 whatever the config says"""
@@ -171,31 +185,46 @@ def _fold(conv):
     return ops.pack_conv_weight(conv.weight.detach().float().sum(dim=2))
 
 
+def _pack3d(conv):
+    """a causal Conv3d as it is -> the packed 3-D weight [3,3,3,Cin,Cout] of ops.conv3d_causal_f32"""
+    return ops.pack_conv3d_weight(conv.weight)
+
+
 def _vec(p):
     return p.detach().float().contiguous()
 
 
-def _pack_resnet(r):
-    """fp32 kernel-layout copies of a resnet's parameters: GroupNorm (gamma, beta), folded convolutions (weight, bias), the 1x1x1 shortcut as [Cin,Cout]"""
+def _group_norm(n):
+    return _vec(n.weight), _vec(n.bias)
+
+
+def _pack_spatial_norm(n):
+    """a spatial norm's parameters for the kernels: GroupNorm (gamma, beta), and conv_y | conv_b side by side as one 1x1 convolution [L, 2C] with its
+    bias [2C], so that one ops.conv1x1_f32 of the latent gives the (Y | B) map ops.spatial_norm_silu_f32 gathers from"""
+    wy, wb = (c.conv.weight.detach().float().reshape(c.conv.weight.shape[0], -1).t() for c in (n.conv_y, n.conv_b))
+    return dict(gn=_group_norm(n.norm_layer),
+                yb=(torch.cat([wy, wb], dim=1).contiguous(), torch.cat([_vec(n.conv_y.conv.bias), _vec(n.conv_b.conv.bias)])))
+
+
+def _pack_block(r, norm, pack):
+    """fp32 kernel-layout copies of a resnet's parameters: the norms as `norm` leaves them, the convolutions (weight as `pack` leaves it, bias), the
+    1x1x1 shortcut as ([Cin,Cout], bias) or None"""
     sc = None
     if hasattr(r, "conv_shortcut"):
         w = r.conv_shortcut.weight.detach().float()
         sc = (w.reshape(w.shape[0], w.shape[1]).t().contiguous(), _vec(r.conv_shortcut.bias))
-    return dict(n1=(_vec(r.norm1.weight), _vec(r.norm1.bias)), n2=(_vec(r.norm2.weight), _vec(r.norm2.bias)),
-                c1=(_fold(r.conv1.conv), _vec(r.conv1.conv.bias)), c2=(_fold(r.conv2.conv), _vec(r.conv2.conv.bias)), sc=sc)
+    return dict(n1=norm(r.norm1), n2=norm(r.norm2), c1=(pack(r.conv1.conv), _vec(r.conv1.conv.bias)),
+                c2=(pack(r.conv2.conv), _vec(r.conv2.conv.bias)), sc=sc)
 
 
-def _resnet_forward(p, h, groups, eps):
-    """CogVideoXResnetBlock3D of the encoder (no time embedding, no spatial norm) on h [N,H,W,C]: norm1, SiLU, conv1, norm2, SiLU, conv2, plus the
-    input (through the shortcut convolution when the width changes), the add fused into conv2's epilogue"""
-    t = ops.conv3x3_pad_f32(ops.groupnorm_silu_f32(h, *p["n1"], groups, eps), *p["c1"])
-    t = ops.groupnorm_silu_f32(t, *p["n2"], groups, eps)
-    return ops.conv3x3_pad_f32(t, *p["c2"], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
+def _pack_resnet(r):
+    """an encoder resnet: GroupNorm (gamma, beta), folded convolutions"""
+    return _pack_block(r, _group_norm, _fold)
 
 
-def _pack3d(conv):
-    """a causal Conv3d as it is -> the packed 3-D weight [3,3,3,Cin,Cout] of ops.conv3d_causal_f32"""
-    return ops.pack_conv3d_weight(conv.weight)
+def _pack_decoder_resnet(r):
+    """a decoder resnet: spatial norms, the causal convolutions with their temporal taps"""
+    return _pack_block(r, _pack_spatial_norm, _pack3d)
 
 
 class _ConvCache:
@@ -215,42 +244,54 @@ class _ConvCache:
         return ops.conv3d_causal_f32(x, w, b, res=res, prev=prev)
 
 
-def _resnet_forward_video(p, w3, name, h, groups, eps, cache):
-    """_resnet_forward on a chunk h [N,T,H,W,C]: GroupNorm over the chunk's (T,H,W), the causal convolutions with their cache"""
-    t = cache.conv(name + ".conv1", ops.groupnorm_silu_f32(h, *p["n1"], groups, eps), w3[0], p["c1"][1])
-    t = ops.groupnorm_silu_f32(t, *p["n2"], groups, eps)
-    return cache.conv(name + ".conv2", t, w3[1], p["c2"][1], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
-
-
-def _pack_spatial_norm(n):
-    """a spatial norm's parameters for the kernels: GroupNorm (gamma, beta), and conv_y | conv_b side by side as one 1x1 convolution [L, 2C] with its
-    bias [2C], so that one ops.conv1x1_f32 of the latent gives the (Y | B) map ops.spatial_norm_silu_f32 gathers from"""
-    wy, wb = (c.conv.weight.detach().float().reshape(c.conv.weight.shape[0], -1).t() for c in (n.conv_y, n.conv_b))
-    return dict(gn=(_vec(n.norm_layer.weight), _vec(n.norm_layer.bias)),
-                yb=(torch.cat([wy, wb], dim=1).contiguous(), torch.cat([_vec(n.conv_y.conv.bias), _vec(n.conv_b.conv.bias)])))
-
-
 def _spatial_norm_silu(p, f, zq, groups):
     """silu(CogVideoXSpatialNorm3D(f, zq)) on f [N,T,H,W,C], zq [N,t,h,w,L]: the modulation maps at the latent's resolution (a 1x1 convolution commutes
     with the nearest resize exactly), the resize as the kernel's gather"""
     return ops.spatial_norm_silu_f32(f, ops.groupnorm_stats_f32(f, groups, 1e-6), *p["gn"], ops.conv1x1_f32(zq, *p["yb"]))
 
 
-def _pack_decoder_resnet(r):
-    sc = None
-    if hasattr(r, "conv_shortcut"):
-        w = r.conv_shortcut.weight.detach().float()
-        sc = (w.reshape(w.shape[0], w.shape[1]).t().contiguous(), _vec(r.conv_shortcut.bias))
-    return dict(n1=_pack_spatial_norm(r.norm1), n2=_pack_spatial_norm(r.norm2), c1=(_pack3d(r.conv1.conv), _vec(r.conv1.conv.bias)),
-                c2=(_pack3d(r.conv2.conv), _vec(r.conv2.conv.bias)), sc=sc)
+def _resnet(p, h, norm, conv):
+    """CogVideoXResnetBlock3D on channels-last h: norm1, SiLU, conv1, norm2, SiLU, conv2, plus the input (through the 1x1x1 shortcut convolution when
+    the width changes), the add fused into conv2's epilogue.  `norm(i, x)` is norm i with its SiLU and `conv(i, x, res)` convolution i, in the form
+    of the three callers below"""
+    t = norm(2, conv(1, norm(1, h), None))
+    return conv(2, t, h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
+
+
+def _resnet_forward(p, h, groups, eps):
+    """the encoder's resnet (no time embedding, no spatial norm) on one frame h [N,H,W,C]: the folded 2-D convolutions"""
+    return _resnet(p, h, lambda i, x: ops.groupnorm_silu_f32(x, *p[f"n{i}"], groups, eps),
+                   lambda i, x, res: ops.conv3x3_pad_f32(x, *p[f"c{i}"], res=res))
+
+
+def _resnet_forward_video(p, w3, name, h, groups, eps, cache):
+    """the encoder's resnet on a chunk h [N,T,H,W,C]: GroupNorm over the chunk's (T,H,W), the causal convolutions (weights w3) with their cache"""
+    return _resnet(p, h, lambda i, x: ops.groupnorm_silu_f32(x, *p[f"n{i}"], groups, eps),
+                   lambda i, x, res: cache.conv(f"{name}.conv{i}", x, w3[i - 1], p[f"c{i}"][1], res=res))
 
 
 def _decoder_resnet_forward(p, name, h, zq, groups, cache):
-    """CogVideoXResnetBlock3D of the decoder on a chunk h [N,T,H,W,C]: norm1(h, zq), SiLU, conv1, norm2(., zq), SiLU, conv2, plus the input (through the
-    1x1x1 shortcut when the width changes; the add is conv2's epilogue)"""
-    t = cache.conv(name + ".conv1", _spatial_norm_silu(p["n1"], h, zq, groups), *p["c1"])
-    t = _spatial_norm_silu(p["n2"], t, zq, groups)
-    return cache.conv(name + ".conv2", t, *p["c2"], res=h if p["sc"] is None else ops.conv1x1_f32(h, *p["sc"]))
+    """the decoder's resnet on a chunk h [N,T,H,W,C]: both norms spatial norms conditioned on zq, the causal convolutions with their cache"""
+    return _resnet(p, h, lambda i, x: _spatial_norm_silu(p[f"n{i}"], x, zq, groups),
+                   lambda i, x, res: cache.conv(f"{name}.conv{i}", x, *p[f"c{i}"], res=res))
+
+
+def _ranges(num, size):
+    """diffusers' _encode / _decode: the (start, end) ranges `num` frames go through a network in, `size` frames each, the first one longer by the
+    remainder (up to 2 * size - 1 frames are one batch).  Pure host arithmetic."""
+    rem = num % size
+    return [(size * i + (0 if i == 0 else rem), min(size * (i + 1) + rem, num)) for i in range(max(num // size, 1))]
+
+
+def _batched(x, tdim, ranges, chunk):
+    """the frames of x (axis tdim) in `ranges`, one batch after the other through `chunk(frames, cache)`, each with the conv cache the one before left;
+    the outputs [N,T',...] joined in time.  GroupNorm statistics are per sample and per batch, as upstream, so the result depends on the batching."""
+    cache, out = None, []
+    for start, end in ranges:
+        cache = _ConvCache(cache)
+        out.append(chunk(x.narrow(tdim, start, end - start), cache))
+        cache.prev = {}                                                  # the chunk before's frames are no longer needed
+    return out[0] if len(out) == 1 else torch.cat(out, dim=1)
 
 
 def _blend(prev, cur, extent, dim):
@@ -278,6 +319,22 @@ def _stitch(tiles, n_rows, n_cols, blend, keep, ydim):
             kept.append(tiles[a, b][(slice(None),) * ydim + (slice(0, keep[0]), slice(0, keep[1]))])
         out_rows.append(torch.cat(kept, dim=ydim + 1))
     return torch.cat(out_rows, dim=ydim).contiguous()
+
+
+def _tiled(x, ydim, plan, run, out_ydim):
+    """tiled_encode / tiled_decode: the tiles of `plan` cut out of x (its row axis ydim), those of one size through `run` as one batch, the results
+    (row axis out_ydim) blended and joined by _stitch"""
+    rows, cols, N = plan["rows"], plan["cols"], x.shape[0]
+    by_shape = {}                                                       # tiles of one size share a pass through the network as a batch
+    for a, (i, th) in enumerate(rows):
+        for b, (j, tw) in enumerate(cols):
+            by_shape.setdefault((th, tw), []).append((a, b, i, j))
+    tiles = {}
+    for (th, tw), members in by_shape.items():
+        out = run(torch.cat([x.narrow(ydim, i, th).narrow(ydim + 1, j, tw) for _, _, i, j in members], dim=0))
+        for k, (a, b, _, _) in enumerate(members):
+            tiles[a, b] = out[k * N:(k + 1) * N]
+    return _stitch(tiles, len(rows), len(cols), plan["blend"], plan["keep"], out_ydim)
 
 
 class DecoderOutput:
@@ -354,14 +411,16 @@ class AutoencoderKLCogVideoX(nn.Module):
         self.use_slicing = self.use_tiling = False
         self.num_sample_frames_batch_size = 8                # frames per pass through the encoder (diffusers' _encode); the first pass takes the remainder too
         self.num_latent_frames_batch_size = 2                # latent frames per pass through the decoder (diffusers' _decode), likewise
-        self.tile_sample_min_height = cfg.sample_height // 2
-        self.tile_sample_min_width = cfg.sample_width // 2
-        down = 2 ** (len(cfg.block_out_channels) - 1)
-        self.tile_latent_min_height = int(self.tile_sample_min_height / down)
-        self.tile_latent_min_width = int(self.tile_sample_min_width / down)
+        self._set_tile_sample_min(cfg.sample_height // 2, cfg.sample_width // 2)
         self.tile_overlap_factor_height = 1 / 6
         self.tile_overlap_factor_width = 1 / 5
         self._packed = _PackedCache()
+
+    def _set_tile_sample_min(self, height, width):
+        """the tile size in sample pixels and, from it, in latent pixels"""
+        down = 2 ** (len(self.config.block_out_channels) - 1)
+        self.tile_sample_min_height, self.tile_sample_min_width = height, width
+        self.tile_latent_min_height, self.tile_latent_min_width = int(height / down), int(width / down)
 
     # ------------------------------------------------------------------ diffusers' switches
     def enable_slicing(self):
@@ -374,11 +433,7 @@ class AutoencoderKLCogVideoX(nn.Module):
 
     def enable_tiling(self, tile_sample_min_height=None, tile_sample_min_width=None, tile_overlap_factor_height=None, tile_overlap_factor_width=None):
         self.use_tiling = True
-        self.tile_sample_min_height = tile_sample_min_height or self.tile_sample_min_height
-        self.tile_sample_min_width = tile_sample_min_width or self.tile_sample_min_width
-        down = 2 ** (len(self.config.block_out_channels) - 1)
-        self.tile_latent_min_height = int(self.tile_sample_min_height / down)
-        self.tile_latent_min_width = int(self.tile_sample_min_width / down)
+        self._set_tile_sample_min(tile_sample_min_height or self.tile_sample_min_height, tile_sample_min_width or self.tile_sample_min_width)
         self.tile_overlap_factor_height = tile_overlap_factor_height or self.tile_overlap_factor_height
         self.tile_overlap_factor_width = tile_overlap_factor_width or self.tile_overlap_factor_width
 
@@ -432,28 +487,41 @@ class AutoencoderKLCogVideoX(nn.Module):
                 f"{what}: {', '.join(keys)}" for what, keys in (("missing", missing), ("unexpected", unexpected), ("shape mismatch", wrong)) if keys))
         return super().load_state_dict(sd, strict=strict, assign=assign)
 
-    # ------------------------------------------------------------------ kernel-layout copies
-    def _resnets(self):
-        enc = self.encoder
-        return [r for b in enc.down_blocks for r in b.resnets] + list(enc.mid_block.resnets)
+    # ------------------------------------------------------------------ what encode and decode share
+    def _sliced(self, x, run):
+        """behind an entry's own checks: x on the device and in the module's dtype, through `run` whole or, with slicing on, one sample at a time"""
+        if not x.is_cuda:
+            raise RuntimeError("videogpa_amd ops need GPU tensors (no CPU fallback)")
+        _forward_only(self, x)
+        x = x.to(self.dtype)
+        if self.use_slicing and x.shape[0] > 1:
+            return torch.cat([run(x[i:i + 1]) for i in range(x.shape[0])], dim=0)
+        return run(x)
 
+    def _tile_plan(self, height, width, cut, kept):
+        """The tile grid of diffusers' tiled_encode / tiled_decode over a height x width map of the side that is cut into tiles of `cut` = (h, w):
+        (rows, cols) of (start, size) in its pixels, the blend extents and the kept tile size in pixels of the other side, where a tile is `kept` =
+        (h, w) and the results are blended"""
+        fh, fw = self.tile_overlap_factor_height, self.tile_overlap_factor_width
+        (cut_h, cut_w), (kept_h, kept_w) = cut, kept
+        blend_h, blend_w = int(kept_h * fh), int(kept_w * fw)
+        rows = [(i, min(cut_h, height - i)) for i in range(0, height, int(cut_h * (1 - fh)))]
+        cols = [(j, min(cut_w, width - j)) for j in range(0, width, int(cut_w * (1 - fw)))]
+        return dict(rows=rows, cols=cols, blend=(blend_h, blend_w), keep=(kept_h - blend_h, kept_w - blend_w))
+
+    # ------------------------------------------------------------------ encoder: kernel-layout copies
     def packed(self):
         """fp32 kernel-layout copies of every parameter (temporal taps folded, the stem padded to 16 input channels with zero rows), rebuilt when a
-        parameter changes or moves"""
+        parameter changes or moves.  The resnets are keyed by `_Encoder3D.resnets()`'s names, the downsamplers by their block's index."""
         enc = self.encoder
 
         def make():
             w_in = _fold(enc.conv_in.conv)
             w_in = torch.cat([w_in, w_in.new_zeros(3, 3, 16 - w_in.shape[2], w_in.shape[3])], dim=2).contiguous()
-            out = {"conv_in": (w_in, _vec(enc.conv_in.conv.bias)), "conv_out": (_fold(enc.conv_out.conv), _vec(enc.conv_out.conv.bias)),
-                   "norm_out": (_vec(enc.norm_out.weight), _vec(enc.norm_out.bias)), "resnets": {}, "down": {}}
-            for r in self._resnets():
-                out["resnets"][id(r)] = _pack_resnet(r)
-            for b in enc.down_blocks:
-                if hasattr(b, "downsamplers"):
-                    c = b.downsamplers[0].conv
-                    out["down"][id(b)] = (ops.pack_conv_weight(c.weight), _vec(c.bias))
-            return out
+            return {"conv_in": (w_in, _vec(enc.conv_in.conv.bias)), "conv_out": (_fold(enc.conv_out.conv), _vec(enc.conv_out.conv.bias)),
+                    "norm_out": _group_norm(enc.norm_out), "resnets": {name: _pack_resnet(r) for name, r in enc.resnets()},
+                    "down": {i: (ops.pack_conv_weight(b.downsamplers[0].conv.weight), _vec(b.downsamplers[0].conv.bias))
+                             for i, b in enumerate(enc.down_blocks) if hasattr(b, "downsamplers")}}
         return self._packed.get("all", list(self.parameters()), make)
 
     def packed_video(self):
@@ -465,105 +533,67 @@ class AutoencoderKLCogVideoX(nn.Module):
             w_in = _pack3d(enc.conv_in.conv)
             w_in = torch.cat([w_in, w_in.new_zeros(3, 3, 3, 16 - w_in.shape[3], w_in.shape[4])], dim=3).contiguous()
             return {"conv_in": w_in, "conv_out": _pack3d(enc.conv_out.conv),
-                    "resnets": {id(r): (_pack3d(r.conv1.conv), _pack3d(r.conv2.conv)) for r in self._resnets()}}
+                    "resnets": {name: (_pack3d(r.conv1.conv), _pack3d(r.conv2.conv)) for name, r in enc.resnets()}}
         return self._packed.get("video", list(self.parameters()), make)
 
     def frame_batches(self, num_frames):
         """diffusers' _encode: the (start, end) frame ranges a clip is encoded in, num_sample_frames_batch_size frames each, the first one longer by the
-        remainder (49 -> (0,9), (9,17), ..., (41,49); up to 15 frames are one batch).  Pure host arithmetic."""
-        size = self.num_sample_frames_batch_size
-        rem = num_frames % size
-        return [(size * i + (0 if i == 0 else rem), min(size * (i + 1) + rem, num_frames)) for i in range(max(num_frames // size, 1))]
+        remainder (49 -> (0,9), (9,17), ..., (41,49); up to 15 frames are one batch)"""
+        return _ranges(num_frames, self.num_sample_frames_batch_size)
 
-    # ------------------------------------------------------------------ forward
-    def _moments(self, x):
-        """x [N,3,H,W] in the module's dtype -> the encoder's output [N,H/8,W/8,2L] fp32 channels-last"""
-        P, G, eps = self.packed(), self.config.norm_num_groups, self.config.norm_eps
+    # ------------------------------------------------------------------ encoder: forward
+    def _encoder_body(self, h, resnet, down, what):
+        """the encoder between conv_in and norm_out on channels-last h: `resnet(name, h)` for every resnet, `down(i, h)` behind down block i"""
         enc = self.encoder
-        h = ops.conv3x3_pad_f32(ops.vae_input_f32(x.contiguous()), *P["conv_in"])
-
-        def resnet(r, h):
-            return _resnet_forward(P["resnets"][id(r)], h, G, eps)
-
-        for b in enc.down_blocks:
-            for r in b.resnets:
-                h = resnet(r, h)
+        for i, b in enumerate(enc.down_blocks):
+            for j in range(len(b.resnets)):
+                h = resnet(f"down_blocks.{i}.resnets.{j}", h)
             if hasattr(b, "downsamplers"):
-                if min(h.shape[1], h.shape[2]) < 2:
-                    raise RuntimeError(f"the image is too small: a {h.shape[1]} x {h.shape[2]} map reached a downsampler")
-                h = ops.conv3x3_pad_f32(h, *P["down"][id(b)], stride=2, pad_lo=0, pad_hi=1)      # temporal pooling: the identity on one frame
-        for r in enc.mid_block.resnets:
-            h = resnet(r, h)
+                if min(h.shape[-3], h.shape[-2]) < 2:
+                    raise RuntimeError(f"the {what} is too small: a {h.shape[-3]} x {h.shape[-2]} map reached a downsampler")
+                h = down(i, h)
+        for j in range(len(enc.mid_block.resnets)):
+            h = resnet(f"mid_block.resnets.{j}", h)
+        return h
+
+    def _moments(self, x):
+        """x [N,3,H,W] in the module's dtype -> the encoder's output [N,H/8,W/8,2L] fp32 channels-last: the folded 2-D path of one frame"""
+        P, G, eps = self.packed(), self.config.norm_num_groups, self.config.norm_eps
+        h = ops.conv3x3_pad_f32(ops.vae_input_f32(x.contiguous()), *P["conv_in"])
+        h = self._encoder_body(h, lambda name, h: _resnet_forward(P["resnets"][name], h, G, eps),
+                               lambda i, h: ops.conv3x3_pad_f32(h, *P["down"][i], stride=2, pad_lo=0, pad_hi=1),      # temporal pooling: the identity on one frame
+                               "image")
         return ops.conv3x3_pad_f32(ops.groupnorm_silu_f32(h, *P["norm_out"], G, eps), *P["conv_out"])
 
     def _chunk_moments(self, x, cache):
         """one pass of diffusers' encoder over a chunk of frames: x [N,3,T,H,W] in the module's dtype -> [N,T',H/8,W/8,2L] fp32 channels-last, T' the
         frames left by the temporal pooling of down blocks 0 and 1.  `cache` is this pass's _ConvCache (it reads the chunk before's, it keeps its own)."""
         P, V, G, eps = self.packed(), self.packed_video(), self.config.norm_num_groups, self.config.norm_eps
-        enc = self.encoder
         N, _, T, H, W = x.shape
         n_time = {4: 2, 8: 3}.get(self.config.temporal_compression_ratio, 0)
         frames = ops.vae_input_f32(x.transpose(1, 2).contiguous().view(N * T, 3, H, W)).view(N, T, H, W, 16)       # the 3-channel tensor: a host-side permute
         h = cache.conv("conv_in", frames, V["conv_in"], P["conv_in"][1])
-
-        def resnet(name, r, h):
-            return _resnet_forward_video(P["resnets"][id(r)], V["resnets"][id(r)], name, h, G, eps, cache)
-
-        for i, b in enumerate(enc.down_blocks):
-            for j, r in enumerate(b.resnets):
-                h = resnet(f"down_blocks.{i}.resnets.{j}", r, h)
-            if hasattr(b, "downsamplers"):
-                if min(h.shape[2], h.shape[3]) < 2:
-                    raise RuntimeError(f"the clip is too small: a {h.shape[2]} x {h.shape[3]} map reached a downsampler")
-                h = ops.vae_downsample_f32(h, *P["down"][id(b)], compress_time=i < n_time)
-        for j, r in enumerate(enc.mid_block.resnets):
-            h = resnet(f"mid_block.resnets.{j}", r, h)
+        h = self._encoder_body(h, lambda name, h: _resnet_forward_video(P["resnets"][name], V["resnets"][name], name, h, G, eps, cache),
+                               lambda i, h: ops.vae_downsample_f32(h, *P["down"][i], compress_time=i < n_time), "clip")
         return cache.conv("conv_out", ops.groupnorm_silu_f32(h, *P["norm_out"], G, eps), V["conv_out"], P["conv_out"][1])
 
     def _video_moments(self, x):
-        """x [N,3,F,H,W] -> [N,(F-1)/4+1,H/8,W/8,2L]: diffusers' _encode, the frame batches one after the other through the whole encoder, each with the
-        conv cache the one before left.  GroupNorm statistics are per sample and per batch of frames, as upstream, so the result depends on the batching."""
-        cache, out = None, []
-        for start, end in self.frame_batches(x.shape[2]):
-            cache = _ConvCache(cache)
-            out.append(self._chunk_moments(x[:, :, start:end], cache))
-            cache.prev = {}                                              # the chunk before's frames are no longer needed
-        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+        """x [N,3,F,H,W] -> [N,(F-1)/4+1,H/8,W/8,2L]: diffusers' _encode, the frame batches through the whole encoder"""
+        return _batched(x, 2, self.frame_batches(x.shape[2]), self._chunk_moments)
 
     def tile_plan(self, height, width):
         """The tile grid of diffusers' tiled_encode for a height x width image: (rows, cols) of (start, size) in pixels, the blend extents and the kept
         tile size in latent pixels"""
-        fh, fw = self.tile_overlap_factor_height, self.tile_overlap_factor_width
-        stride_h, stride_w = int(self.tile_sample_min_height * (1 - fh)), int(self.tile_sample_min_width * (1 - fw))
-        blend_h, blend_w = int(self.tile_latent_min_height * fh), int(self.tile_latent_min_width * fw)
-        rows = [(i, min(self.tile_sample_min_height, height - i)) for i in range(0, height, stride_h)]
-        cols = [(j, min(self.tile_sample_min_width, width - j)) for j in range(0, width, stride_w)]
-        return dict(rows=rows, cols=cols, blend=(blend_h, blend_w), keep=(self.tile_latent_min_height - blend_h, self.tile_latent_min_width - blend_w))
-
-    def _tiled_moments(self, x):
-        """x [N,3,H,W] (one frame) or [N,3,F,H,W] (a clip: every tile runs the frame batches with a conv cache of its own, the blends are per frame)"""
-        video = x.dim() == 5
-        plan = self.tile_plan(x.shape[-2], x.shape[-1])
-        rows, cols, (blend_h, blend_w), (keep_h, keep_w) = plan["rows"], plan["cols"], plan["blend"], plan["keep"]
-        N, ydim = x.shape[0], 2 if video else 1                         # the moments are [N,h,w,2L] or [N,T',h,w,2L]
-        by_shape = {}                                                   # tiles of one size share a pass through the encoder as a batch
-        for a, (i, th) in enumerate(rows):
-            for b, (j, tw) in enumerate(cols):
-                by_shape.setdefault((th, tw), []).append((a, b, i, j))
-        tiles = {}
-        for (th, tw), members in by_shape.items():
-            batch = torch.cat([x[..., i:i + th, j:j + tw] for _, _, i, j in members], dim=0)
-            m = self._video_moments(batch) if video else self._moments(batch)
-            for k, (a, b, _, _) in enumerate(members):
-                tiles[a, b] = m[k * N:(k + 1) * N]
-        return _stitch(tiles, len(rows), len(cols), (blend_h, blend_w), (keep_h, keep_w), ydim)
+        return self._tile_plan(height, width, (self.tile_sample_min_height, self.tile_sample_min_width), (self.tile_latent_min_height, self.tile_latent_min_width))
 
     def _encode(self, x):
-        """x [N,3,H,W] (one frame: the folded 2-D path) or [N,3,F,H,W] (a clip) -> the moments, channels-last"""
+        """x [N,3,H,W] (one frame: the folded 2-D path) or [N,3,F,H,W] (a clip) -> the moments [N,h,w,2L] or [N,T',h,w,2L], channels-last.  Tiled: every
+        tile of a clip runs the frame batches with a conv cache of its own, the blends are per frame."""
         H, W = x.shape[-2], x.shape[-1]
+        run = self._video_moments if x.dim() == 5 else self._moments
         if self.use_tiling and (W > self.tile_sample_min_width or H > self.tile_sample_min_height):
-            return self._tiled_moments(x)
-        return self._video_moments(x) if x.dim() == 5 else self._moments(x)
+            return _tiled(x, x.dim() - 2, self.tile_plan(H, W), run, x.dim() - 3)
+        return run(x)
 
     def encode(self, x, return_dict=True):
         """x [B,3,F,H,W], F = 1 or F = 4k + 1 (the model's clip lengths: 49, 81, 13, ...) -> AutoencoderKLOutput whose `.latent_dist` is the
@@ -575,17 +605,7 @@ class AutoencoderKLCogVideoX(nn.Module):
         if F != 1 and F % 4 != 1:
             raise NotImplementedError(f"encode of {F} frames: one frame (the I2V conditioning image) or 4k + 1 frames (the model's clip lengths, "
                                       "02_encode.py's 49) run on the device; a clip of another length is refused, not padded or cut")
-        if not x.is_cuda:
-            raise RuntimeError("videogpa_amd ops need GPU tensors (no CPU fallback)")
-        _forward_only(self, x)
-        x = x.to(self.dtype)
-        if F == 1:
-            x = x[:, :, 0]
-        if self.use_slicing and x.shape[0] > 1:
-            moments = torch.cat([self._encode(x[i:i + 1]) for i in range(x.shape[0])], dim=0)
-        else:
-            moments = self._encode(x)
-        dist = DiagonalGaussianDistribution(moments, self.dtype)
+        dist = DiagonalGaussianDistribution(self._sliced(x, lambda s: self._encode(s[:, :, 0] if F == 1 else s)), self.dtype)
         return AutoencoderKLOutput(dist) if return_dict else (dist,)
 
     # ------------------------------------------------------------------ decoder (with_decoder=True)
@@ -606,66 +626,44 @@ class AutoencoderKLCogVideoX(nn.Module):
 
     def latent_frame_batches(self, num_frames):
         """diffusers' _decode: the (start, end) latent frame ranges a latent is decoded in, num_latent_frames_batch_size frames each, the first one longer
-        by the remainder (13 -> (0,3), (3,5), ..., (11,13); up to 3 frames are one batch).  Pure host arithmetic."""
-        size = self.num_latent_frames_batch_size
-        rem = num_frames % size
-        return [(size * i + (0 if i == 0 else rem), min(size * (i + 1) + rem, num_frames)) for i in range(max(num_frames // size, 1))]
+        by the remainder (13 -> (0,3), (3,5), ..., (11,13); up to 3 frames are one batch)"""
+        return _ranges(num_frames, self.num_latent_frames_batch_size)
 
     def _chunk_frames(self, zq, cache):
         """one pass of diffusers' decoder over a chunk of latent frames: zq [N,t,h,w,L] fp32 channels-last -> [N,T,8h,8w,16] fp32 (channels 0..2 are the
         image, the rest zero), T the frames the up-samplers of blocks 0 and 1 (compress_time) make of t.  Every spatial norm is conditioned on zq."""
         P, G, dec = self.packed_decoder(), self.config.norm_num_groups, self.decoder
         n_time = {4: 2, 8: 3}[self.config.temporal_compression_ratio]
+        zq = zq.contiguous()
         h = cache.conv("conv_in", zq, *P["conv_in"])
+
+        def resnet(name, h):
+            return _decoder_resnet_forward(P["resnets"][name], name, h, zq, G, cache)
+
         for j in range(len(dec.mid_block.resnets)):
-            h = _decoder_resnet_forward(P["resnets"][f"mid_block.resnets.{j}"], f"mid_block.resnets.{j}", h, zq, G, cache)
+            h = resnet(f"mid_block.resnets.{j}", h)
         for i, b in enumerate(dec.up_blocks):
             for j in range(len(b.resnets)):
-                h = _decoder_resnet_forward(P["resnets"][f"up_blocks.{i}.resnets.{j}"], f"up_blocks.{i}.resnets.{j}", h, zq, G, cache)
+                h = resnet(f"up_blocks.{i}.resnets.{j}", h)
             if i in P["up"]:
                 h = ops.vae_upsample_f32(h, *P["up"][i], compress_time=i < n_time)
         return cache.conv("conv_out", _spatial_norm_silu(P["norm_out"], h, zq, G), *P["conv_out"])
 
     def _latent_frames(self, z):
-        """z [N,F,h,w,L] fp32 channels-last -> [N,F',8h,8w,16]: diffusers' _decode, the latent frame batches one after the other through the whole
-        decoder, each with the conv cache the one before left.  GroupNorm statistics are per sample and per batch, so the result depends on the batching."""
-        cache, out = None, []
-        for start, end in self.latent_frame_batches(z.shape[1]):
-            cache = _ConvCache(cache)
-            out.append(self._chunk_frames(z[:, start:end].contiguous(), cache))
-            cache.prev = {}
-        return out[0] if len(out) == 1 else torch.cat(out, dim=1)
+        """z [N,F,h,w,L] fp32 channels-last -> [N,F',8h,8w,16]: diffusers' _decode, the latent frame batches through the whole decoder"""
+        return _batched(z, 1, self.latent_frame_batches(z.shape[1]), self._chunk_frames)
 
     def decode_tile_plan(self, height, width):
         """The tile grid of diffusers' tiled_decode for a height x width LATENT: (rows, cols) of (start, size) in latent pixels, the blend extents and the
         kept tile size in sample pixels"""
-        fh, fw = self.tile_overlap_factor_height, self.tile_overlap_factor_width
-        stride_h, stride_w = int(self.tile_latent_min_height * (1 - fh)), int(self.tile_latent_min_width * (1 - fw))
-        blend_h, blend_w = int(self.tile_sample_min_height * fh), int(self.tile_sample_min_width * fw)
-        rows = [(i, min(self.tile_latent_min_height, height - i)) for i in range(0, height, stride_h)]
-        cols = [(j, min(self.tile_latent_min_width, width - j)) for j in range(0, width, stride_w)]
-        return dict(rows=rows, cols=cols, blend=(blend_h, blend_w), keep=(self.tile_sample_min_height - blend_h, self.tile_sample_min_width - blend_w))
-
-    def _tiled_frames(self, z):
-        """tiled_decode on z [N,F,h,w,L]: every latent tile through the frame-batch loop with a conv cache of its own, the blends per frame in sample pixels"""
-        plan = self.decode_tile_plan(z.shape[2], z.shape[3])
-        rows, cols, N = plan["rows"], plan["cols"], z.shape[0]
-        by_shape = {}                                                   # tiles of one size share a pass through the decoder as a batch
-        for a, (i, th) in enumerate(rows):
-            for b, (j, tw) in enumerate(cols):
-                by_shape.setdefault((th, tw), []).append((a, b, i, j))
-        tiles = {}
-        for (th, tw), members in by_shape.items():
-            frames = self._latent_frames(torch.cat([z[:, :, i:i + th, j:j + tw] for _, _, i, j in members], dim=0))
-            for k, (a, b, _, _) in enumerate(members):
-                tiles[a, b] = frames[k * N:(k + 1) * N]
-        return _stitch(tiles, len(rows), len(cols), plan["blend"], plan["keep"], 2)
+        return self._tile_plan(height, width, (self.tile_latent_min_height, self.tile_latent_min_width), (self.tile_sample_min_height, self.tile_sample_min_width))
 
     def _decode(self, z):
-        """z [N,L,F,h,w] in the module's dtype -> the frames [N,F',8h,8w,16] fp32 channels-last"""
+        """z [N,L,F,h,w] in the module's dtype -> the frames [N,F',8h,8w,16] fp32 channels-last.  Tiled: every latent tile through the frame batches
+        with a conv cache of its own, the blends per frame in sample pixels."""
         z = z.permute(0, 2, 3, 4, 1).float().contiguous()               # the latent is small: a host-side permute
         if self.use_tiling and (z.shape[3] > self.tile_latent_min_width or z.shape[2] > self.tile_latent_min_height):
-            return self._tiled_frames(z)
+            return _tiled(z, 2, self.decode_tile_plan(z.shape[2], z.shape[3]), self._latent_frames, 2)
         return self._latent_frames(z)
 
     def _decoded_frames(self, z):
@@ -673,13 +671,7 @@ class AutoencoderKLCogVideoX(nn.Module):
             raise NotImplementedError("this module is the encoder side only: construct it (or call from_pretrained) with with_decoder=True to decode")
         if z.dim() != 5 or z.shape[1] != self.config.latent_channels:
             raise RuntimeError(f"decode: expected [B,{self.config.latent_channels},F,h,w], got {tuple(z.shape)}")
-        if not z.is_cuda:
-            raise RuntimeError("videogpa_amd ops need GPU tensors (no CPU fallback)")
-        _forward_only(self, z)
-        z = z.to(self.dtype)
-        if self.use_slicing and z.shape[0] > 1:
-            return torch.cat([self._decode(z[i:i + 1]) for i in range(z.shape[0])], dim=0)
-        return self._decode(z)
+        return self._sliced(z, self._decode)
 
     def decode(self, z, return_dict=True):
         """z [B,L,F,h,w] -> DecoderOutput whose `.sample` is [B,3,F',8h,8w] in the module's dtype, rounded once from fp32; F' = 4 (F - 1) + 1 frames of an

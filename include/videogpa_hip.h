@@ -307,6 +307,28 @@ size_t vgpa_preprocess_workspace_bytes(int32_t T, int32_t H, int32_t W, int32_t 
 int32_t vgpa_preprocess_frames(const void* frames, int32_t T, int32_t H, int32_t W, int32_t mode, float* out, void* workspace,
                                size_t ws_bytes, vgpa_stream_t stream);
 
+/* PIL `Image.resize((out_w, out_h), filter)` of uint8 frames [T, H, W, 3] -> uint8 [T, out_h, out_w, 3], bit-exact with Pillow's 8-bit ImagingResample
+ * (the same two passes as above).  filter 0 = BICUBIC, 1 = LANCZOS (sinc(x) sinc(x / 3), support 3).  generate/CogVideoX-5B-I2V.py -> diffusers
+ * VaeImageProcessor.preprocess (Lanczos to 720 x 480); replicate.py:201 (bicubic first). */
+size_t vgpa_image_resize_workspace_bytes(int32_t T, int32_t H, int32_t W, int32_t out_h, int32_t out_w, int32_t filter);
+int32_t vgpa_image_resize(const void* frames, int32_t T, int32_t H, int32_t W, int32_t out_h, int32_t out_w, int32_t filter, void* out,
+                          void* workspace, size_t ws_bytes, vgpa_stream_t stream);
+/* uint8 [T, H, W, 3] -> [T, 3, H, W] (dtype 0 | 1) = x / 255 * 2 - 1, formed in fp32 in that order and rounded once */
+int32_t vgpa_image_to_pm1(const void* image_u8, int64_t T, int64_t H, int64_t W, int32_t dtype, void* out, vgpa_stream_t stream);
+
+/* ---- one sampler step of the generate loop: guidance + v-prediction + scheduler update + the next transformer input, one pass
+ * (diffusers CogVideoXImageToVideoPipeline.__call__ loop body behind the transformer; generate/CogVideoX-5B-I2V.py:70-89).
+ *   v = v_u + g (v_c - v_u) when `guided` (v is [2B, N] = [uncond | cond]), else v [B, N];   x0 = sa x - sb v;
+ *   x_next = k_x x + k_0 x0 + k_old x0_old + k_n noise     (a NULL x0_old / noise leaves its term out)
+ * N = F C hw.  v in v_dtype; x, noise, image_latents [B, F, C_img, hw], x_next and packed in dtype; x0_old and x0 (may be NULL) fp32.
+ * packed (NULL with image_latents NULL): [packed_groups * B, F, C + C_img, hw], channels [0, C) = x_next, [C, C + C_img) = image_latents, for each
+ * of the 1 | 2 groups.  C hw and C_img hw must be multiples of 8 (VGPA_ERR_INVALID otherwise, nothing is launched).  fp32 arithmetic without
+ * contraction, one rounding at each store. */
+int32_t vgpa_sampler_step(const void* v, int32_t v_dtype, int32_t guided, const void* x, const float* x0_old, const void* noise,
+                          const void* image_latents, int64_t B, int64_t F, int64_t C, int64_t C_img, int64_t hw, int32_t dtype, float g,
+                          float sa, float sb, float k_x, float k_0, float k_old, float k_n, void* x_next, float* x0, void* packed,
+                          int32_t packed_groups, vgpa_stream_t stream);
+
 /* ---- optimizer on one flat fp32 buffer of all LoRA parameters: gradient_clip_val=1.0 + torch.optim.AdamW,
  * train/CogVideoX-5B/03_train.py:208-213,266.  norm_out[0] = grad_scale * ||grad||_2. */
 size_t vgpa_grad_norm_workspace_bytes(void);

@@ -228,6 +228,77 @@ def flow_noise_velocity_paired(x_pair, noise, sigma, xt_fp32=True):
     return xt, v
 
 
+# --------------------------------------------------------------------------------------------- sampler step of the generate loop
+def sampler_step(v, x, coef, guidance_scale=None, x0_old=None, noise=None, image_latents=None, out=None):
+    """One pass of csrc/sampler.hip behind the transformer: guidance, the v-prediction data estimate, the scheduler's update and the next input.
+        v = v_u + g (v_c - v_u)  (guidance_scale given: v is [2B, ...] = [uncond | cond]; None: v [B, ...] as it is),   x0 = sa x - sb v,
+        x_next = k_x x + k_0 x0 + k_old x0_old + k_n noise
+    `coef` is a scheduler's step_coefficients(i) (Python floats; k_old / k_n None leave the term out, and then x0_old / noise are not read).
+    v: the model output in its own dtype (bf16 | fp32); x, noise, image_latents [B,F,C_img,h,w]: the latent dtype; x0_old: fp32.
+    -> (x_next [latent dtype], x0 [fp32], packed): packed is None without image_latents, else the next transformer input
+    [G*B, F, C + C_img, h, w] (G = 2 under guidance) = cat([cat([x_next] * G), cat([image_latents] * G)], dim=2), written by the same pass.
+    `out`: an (x_next, x0, packed) triple of a previous call to write into (none of them may be an input of this call)."""
+    _req(v), _req(x)
+    if x.dim() != 5:
+        raise RuntimeError(f"sampler_step: x is [B,F,C,h,w], got {tuple(x.shape)}")
+    B, F, C, h, w = x.shape
+    G = 1 if guidance_scale is None else 2
+    if tuple(v.shape) != (G * B, F, C, h, w):
+        raise RuntimeError(f"sampler_step: v {tuple(v.shape)} is not [{G * B},{F},{C},{h},{w}]")
+    use_old, use_noise = coef["k_old"] is not None, coef["k_n"] is not None
+    if use_old:
+        if x0_old is None or tuple(_req(x0_old, torch.float32).shape) != tuple(x.shape):
+            raise RuntimeError("sampler_step: these coefficients use the history: x0_old must be fp32 of x's shape")
+    if use_noise:
+        if noise is None or tuple(_req(noise, x.dtype).shape) != tuple(x.shape):
+            raise RuntimeError("sampler_step: these coefficients use noise: it must have x's shape and dtype")
+    C_img = 0
+    if image_latents is not None:
+        _req(image_latents, x.dtype)
+        C_img = image_latents.shape[2] if image_latents.dim() == 5 else 0
+        if tuple(image_latents.shape) != (B, F, C_img, h, w) or C_img == 0:
+            raise RuntimeError(f"sampler_step: image_latents {tuple(image_latents.shape)} is not [{B},{F},C_img,{h},{w}]")
+    if out is None:
+        out = (torch.empty_like(x), torch.empty(x.shape, dtype=torch.float32, device=x.device),
+               None if image_latents is None else torch.empty(G * B, F, C + C_img, h, w, dtype=x.dtype, device=x.device))
+    x_next, x0, packed = out
+    _lib.call("vgpa_sampler_step", v, _dtype_code(v.dtype, "sampler_step"), G - 1, x, x0_old if use_old else None, noise if use_noise else None,
+              image_latents, B, F, C, C_img, h * w, _dtype_code(x.dtype, "sampler_step"), float(guidance_scale or 0.0), coef["sa"], coef["sb"],
+              coef["k_x"], coef["k_0"], coef["k_old"] or 0.0, coef["k_n"] or 0.0, x_next, x0, packed, G, _stream())
+    return x_next, x0, packed
+
+
+# --------------------------------------------------------------------------------------------- PIL-exact image resize (csrc/preprocess.hip)
+RESIZE_FILTERS = {"bicubic": 0, "lanczos": 1}
+
+
+def image_resize(frames, out_h, out_w, filter="lanczos"):
+    """uint8 [T,H,W,3] -> uint8 [T,out_h,out_w,3] = PIL `Image.resize((out_w, out_h), BICUBIC | LANCZOS)` of every frame, bit for bit (Pillow's 8-bit
+    ImagingResample: two passes, 22-bit fixed weights, a clip after each pass)"""
+    _req(frames, torch.uint8)
+    if frames.dim() != 4 or frames.shape[-1] != 3 or filter not in RESIZE_FILTERS:
+        raise RuntimeError(f"image_resize: expected uint8 [T,H,W,3] and a filter of {sorted(RESIZE_FILTERS)}, got {tuple(frames.shape)}, {filter!r}")
+    T, H, W, _ = frames.shape
+    code = RESIZE_FILTERS[filter]
+    out = torch.empty(T, int(out_h), int(out_w), 3, dtype=torch.uint8, device=frames.device)
+    ws_bytes = _lib.query("vgpa_image_resize_workspace_bytes", T, H, W, int(out_h), int(out_w), code)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=frames.device)
+    _lib.call("vgpa_image_resize", frames, T, H, W, int(out_h), int(out_w), code, out, ws, ws_bytes, _stream())
+    return out
+
+
+def image_to_pm1(frames, dtype=torch.float32):
+    """uint8 [T,H,W,3] -> [T,3,H,W] in `dtype` (fp32 | bf16) = x / 255 * 2 - 1, formed in fp32 in that order and rounded once (diffusers
+    VaeImageProcessor: pil_to_numpy / 255, then normalize 2 x - 1)"""
+    _req(frames, torch.uint8)
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError(f"image_to_pm1: expected uint8 [T,H,W,3], got {tuple(frames.shape)}")
+    T, H, W, _ = frames.shape
+    out = torch.empty(T, 3, H, W, dtype=dtype, device=frames.device)
+    _lib.call("vgpa_image_to_pm1", frames, T, H, W, _dtype_code(dtype, "image_to_pm1"), out, _stream())
+    return out
+
+
 # --------------------------------------------------------------------------------------------- AdaLN-Zero pieces
 class _LNModulateFn(torch.autograd.Function):
     @staticmethod

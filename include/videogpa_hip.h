@@ -316,6 +316,19 @@ int32_t vgpa_image_resize(const void* frames, int32_t T, int32_t H, int32_t W, i
 /* uint8 [T, H, W, 3] -> [T, 3, H, W] (dtype 0 | 1) = x / 255 * 2 - 1, formed in fp32 in that order and rounded once */
 int32_t vgpa_image_to_pm1(const void* image_u8, int64_t T, int64_t H, int64_t W, int32_t dtype, void* out, vgpa_stream_t stream);
 
+/* ---- Depth Anything 3 input processing (depth_anything_3/utils/io/input_processor.py, api.py:_add_processed_images; csrc/da3_input.hip).
+ * vgpa_da3_resize: cv2.resize of uint8 frames [T, H, W, 3] with OpenCV's 8-bit semantics restated (not pinned to a build: see the file header).
+ *   mode 0 = INTER_AREA (out_h <= H and out_w <= W, VGPA_ERR_INVALID otherwise: nothing is launched), 1 = INTER_CUBIC (any size).
+ *   Destination, exactly one of: out_u8 uint8 [T, out_h, out_w, 3] (x, processed, table NULL), or the last stage's pair as the resize's epilogue
+ *   (out_u8 NULL): x fp32 [T, 3, out_h, out_w] = (u / 255 - mean) / std in torchvision's order and roundings, processed uint8 [T, out_h, out_w, 3]
+ *   = table[c][u], table uint8 [3][256] on the device.  The workspace holds the tap tables (0 bytes on the integer-scale area path).
+ * vgpa_da3_normalize: that last stage alone on the box (top, left, h, w) of image_u8 [T, H, W, 3]. */
+size_t vgpa_da3_resize_workspace_bytes(int32_t H, int32_t W, int32_t out_h, int32_t out_w, int32_t mode);
+int32_t vgpa_da3_resize(const void* frames, int32_t T, int32_t H, int32_t W, int32_t out_h, int32_t out_w, int32_t mode, void* out_u8, float* x,
+                        void* processed, const void* table, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
+int32_t vgpa_da3_normalize(const void* image_u8, int32_t T, int32_t H, int32_t W, int32_t top, int32_t left, int32_t h, int32_t w, float* x,
+                           void* processed, const void* table, vgpa_stream_t stream);
+
 /* ---- one sampler step of the generate loop: guidance + v-prediction + scheduler update + the next transformer input, one pass
  * (diffusers CogVideoXImageToVideoPipeline.__call__ loop body behind the transformer; generate/CogVideoX-5B-I2V.py:70-89).
  *   v = v_u + g (v_c - v_u) when `guided` (v is [2B, N] = [uncond | cond]), else v [B, N];   x0 = sa x - sb v;

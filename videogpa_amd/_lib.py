@@ -74,6 +74,9 @@ SIGNATURES = {
     "vgpa_image_resize_workspace_bytes": (SZ, [I32, I32, I32, I32, I32, I32]),
     "vgpa_image_resize": (I32, [P, I32, I32, I32, I32, I32, I32, P, P, SZ, P]),
     "vgpa_image_to_pm1": (I32, [P, I64, I64, I64, I32, P, P]),
+    "vgpa_da3_resize_workspace_bytes": (SZ, [I32, I32, I32, I32, I32]),
+    "vgpa_da3_resize": (I32, [P, I32, I32, I32, I32, I32, I32, P, P, P, P, P, SZ, P]),
+    "vgpa_da3_normalize": (I32, [P, I32, I32, I32, I32, I32, I32, I32, P, P, P, P]),
     "vgpa_sampler_step": (I32, [P, I32, I32, P, P, P, P, I64, I64, I64, I64, I64, I32, F32, F32, F32, F32, F32, F32, F32, P, P, P, I32, P]),
     "vgpa_project_points_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_project_points": (I32, [P, P, P, F32, P, P, P, I32, I64, I64, I64, I64, P, P, P, SZ, P]),

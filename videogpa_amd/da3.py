@@ -12,12 +12,15 @@ runs for `depth` / `depth_conf` / `ray` / `ray_conf` / `extrinsics` / `intrinsic
                             csrc/dualdpt.hip
     DepthAnything3Net       da3.py:40-221 without cam_enc, the GS heads, ray-pose and exported feature layers
     DA3Cameras              backbone + camera decoder only, for callers that want the cameras and bring no head
+    DepthAnything3          depth_anything_3/api.py:48-446: `inference(frames of any size)` -> `Prediction`; the input processing in front of the network is
+                            videogpa_amd/da3_input.py on csrc/da3_input.hip
 
 Precision is that of vggt.DinoVisionTransformer, which this backbone extends: an fp32 residual stream (csrc/dino_stream.hip), bf16 GEMM and attention
 operands, fp32 outputs -- the bf16-autocast evaluation upstream uses; bf16 parameters, or fp32 parameters under torch.autocast(dtype=torch.bfloat16).
 Blocks without QK-norm are vggt.DinoBlock itself; blocks with it put ops.qknorm_attention (QK-norm + RoPE + flash attention) on the same stream.  What
 sits between the blocks is csrc/da3.hip: the selected view stays in a device buffer from the selection to the last tap.  The head, the camera
 decoder and the pose decoding compute in fp32 with autocast off, as upstream (da3.py:139).  Forward only."""
+import dataclasses
 import functools
 import itertools
 
@@ -347,7 +350,8 @@ class DepthAnything3Net(nn.Module):
     """depth_anything_3/model/da3.py:40-221: `forward(x [B,S,3,H,W] normalised, H and W multiples of 14, ..., aux=True)` -> the head's dict (depth,
     depth_conf and, with aux, ray, ray_conf) plus `extrinsics [B,S,3,4]` (world-to-camera) / `intrinsics [B,S,3,3]` when there is a `cam_dec`.  The
     backbone runs in whatever precision the caller set (bf16 autocast in the scorer); head, camera decoder and pose decoding run with autocast off.
-    Not built: cam_enc (given extrinsics / intrinsics), the GS heads, ray-pose, exported feature layers and the input resizing of api.py."""
+    Not built: cam_enc (given extrinsics / intrinsics), the GS heads, ray-pose and exported feature layers.  The input resizing of api.py is
+    `DepthAnything3` below, not this class."""
 
     PATCH_SIZE = 14
     SKIPPED_PREFIXES = ("cam_enc.", "gs_head.", "gs_adapter.")
@@ -409,3 +413,81 @@ class DepthAnything3Net(nn.Module):
             if self.cam_dec is not None:
                 output.extrinsics, output.intrinsics = decode_cameras(self.cam_dec(feats[-1][1]), (H, W))
         return output
+
+
+# ------------------------------------------------------------------------------------------------------------------------ the API class
+@dataclasses.dataclass
+class Prediction:
+    """depth_anything_3/specs.py:35-45, the fields this path fills, as DEVICE tensors (`.cpu().numpy()` is the caller's): depth [T,h,w], conf [T,h,w],
+    extrinsics [T,3,4] (world-to-camera), intrinsics [T,3,3], processed_images uint8 [T,h,w,3]"""
+    depth: torch.Tensor
+    is_metric: int = 0
+    conf: torch.Tensor = None
+    extrinsics: torch.Tensor = None
+    intrinsics: torch.Tensor = None
+    processed_images: torch.Tensor = None
+
+
+class DepthAnything3(nn.Module):
+    """depth_anything_3/api.py:48-446 over `DepthAnything3Net`: `inference(frames)` takes uint8 frames of ANY size -- InputProcessor on the device
+    (videogpa_amd/da3_input.py: cv2-style area / cubic resizing to `process_res`, centre crop, normalisation), the network under no_grad + bf16
+    autocast with aux=False, and a `Prediction`.  `.model` is the network, so a DA3 checkpoint's `model.*` keys load by name.  Not built, and refused
+    with NotImplementedError as the network refuses them: caller-given extrinsics / intrinsics (cam_enc, Umeyama alignment), infer_gs, use_ray_pose,
+    exports.  Weights come from local files only."""
+
+    def __init__(self, model_name="da3-large", model=None, process_res=504, process_res_method="upper_bound_resize"):
+        """`model`: a ready `DepthAnything3Net` (any configuration) instead of the preset `model_name` names.  `process_res` / `process_res_method`:
+        what `inference` uses when its caller names none -- `VideoProcessor` calls `inference(frames)` bare, as the reference does, so a scorer that
+        wants another processing size than upstream's 504 sets it here"""
+        super().__init__()
+        from .da3_input import InputProcessor
+        self.model_name = model_name
+        self.process_res, self.process_res_method = process_res, process_res_method
+        self.model = (model if model is not None else DepthAnything3Net.from_preset(model_name)).eval()
+        self.input_processor = InputProcessor
+        self.device = None
+
+    @classmethod
+    def from_pretrained(cls, path, preset="da3-large"):
+        """a DA3 checkpoint directory or file on the LOCAL file system (never the network); `preset` names its configuration"""
+        return cls(preset, model=DepthAnything3Net.from_pretrained(path, preset=preset)).eval()
+
+    def load_state_dict(self, state_dict, strict=True, **kw):
+        return self.model.load_state_dict(state_dict, strict=strict, **kw)
+
+    def forward(self, image, extrinsics=None, intrinsics=None, export_feat_layers=None, infer_gs=False, use_ray_pose=False,
+                ref_view_strategy="saddle_balanced"):
+        """api.py:99-131: image [B,N,3,H,W] normalised, on the model's device -> the network's dict (depth, depth_conf, extrinsics, intrinsics)"""
+        with torch.no_grad(), torch.autocast(image.device.type, dtype=torch.bfloat16, enabled=image.device.type == "cuda"):
+            return self.model(image, extrinsics, intrinsics, export_feat_layers or (), infer_gs, use_ray_pose, ref_view_strategy, aux=False)
+
+    def inference(self, image, extrinsics=None, intrinsics=None, align_to_input_ext_scale=True, infer_gs=False, use_ray_pose=False,
+                  ref_view_strategy="saddle_balanced", render_exts=None, render_ixts=None, render_hw=None, process_res=None,
+                  process_res_method=None, export_dir=None, export_format="mini_npz", export_feat_layers=None, **export_kwargs):
+        """api.py:133-273: frames (a list of uint8 [H,W,3] or uint8 [T,H,W,3], host or device) -> Prediction at the processed size.  `process_res` /
+        `process_res_method` default to the instance's (504, "upper_bound_resize" unless the constructor was told otherwise)"""
+        if extrinsics is not None or intrinsics is not None:
+            raise NotImplementedError("given extrinsics / intrinsics need cam_enc and the Umeyama pose alignment, which are not built")
+        if infer_gs:
+            raise NotImplementedError("infer_gs: the Gaussian-splatting heads are not built")
+        if use_ray_pose:
+            raise NotImplementedError("use_ray_pose: the ray-based pose estimation is not built (cameras come from cam_dec)")
+        if export_dir is not None or render_exts is not None or render_ixts is not None or render_hw is not None:
+            raise NotImplementedError("export_dir / export_format / render_*: the export formats are host I/O outside the on-device path")
+        if export_feat_layers is not None and len(export_feat_layers):
+            raise NotImplementedError("export_feat_layers: auxiliary feature maps are not built (no VideoGPA path asks for them)")
+        device = self._get_model_device()
+        x, _, _, processed = self.input_processor(device).process(image, None, None, self.process_res if process_res is None else process_res,
+                                                                  self.process_res_method if process_res_method is None else process_res_method)
+        out = self.forward(x, ref_view_strategy=ref_view_strategy)
+        cams = {k: out[k].squeeze(0) if out.get(k) is not None else None for k in ("extrinsics", "intrinsics")}
+        return Prediction(depth=out["depth"].squeeze(0), conf=out["depth_conf"].squeeze(0), processed_images=processed, **cams)
+
+    def _get_model_device(self):
+        """api.py:423-446"""
+        if self.device is None:
+            t = next(itertools.chain(self.parameters(), self.buffers()), None)
+            if t is None:
+                raise ValueError("No tensor found in model")
+            self.device = t.device
+        return self.device

@@ -299,6 +299,53 @@ def image_to_pm1(frames, dtype=torch.float32):
     return out
 
 
+# --------------------------------------------------------------------------------------------- Depth Anything 3 input processing (csrc/da3_input.hip)
+DA3_RESIZE_MODES = {"area": 0, "cubic": 1}
+
+
+def _da3_frames(frames, name):
+    _req(frames, torch.uint8)
+    if frames.dim() != 4 or frames.shape[-1] != 3:
+        raise RuntimeError(f"{name}: expected uint8 [T,H,W,3], got {tuple(frames.shape)}")
+    return frames.shape[:3]
+
+
+def _da3_pair(frames, T, h, w, table):
+    _req(table, torch.uint8)
+    if tuple(table.shape) != (3, 256):
+        raise RuntimeError(f"processed_images table: expected uint8 [3,256], got {tuple(table.shape)}")
+    return (torch.empty(1, T, 3, h, w, dtype=torch.float32, device=frames.device), torch.empty(T, h, w, 3, dtype=torch.uint8, device=frames.device))
+
+
+def da3_resize(frames, out_h, out_w, mode, table=None):
+    """uint8 [T,H,W,3] -> cv2.resize(frame, (out_w, out_h), INTER_AREA | INTER_CUBIC) of every frame, OpenCV's 8-bit semantics restated (the header of
+    csrc/da3_input.hip says which).  Without `table`: uint8 [T,out_h,out_w,3].  With `table` (uint8 [3,256] on the device, da3_input.processed_table) the
+    last stage is the resize's epilogue: (x fp32 [1,T,3,out_h,out_w] ImageNet-normalised, processed_images uint8 [T,out_h,out_w,3]), the resized uint8
+    image never written.  "area" refuses out > in (RuntimeError, nothing launched)."""
+    T, H, W = _da3_frames(frames, "da3_resize")
+    if mode not in DA3_RESIZE_MODES:
+        raise RuntimeError(f"da3_resize: mode is one of {sorted(DA3_RESIZE_MODES)}, got {mode!r}")
+    code, out_h, out_w = DA3_RESIZE_MODES[mode], int(out_h), int(out_w)
+    if table is None:
+        out, x, proc = torch.empty(T, out_h, out_w, 3, dtype=torch.uint8, device=frames.device), None, None
+    else:
+        out, (x, proc) = None, _da3_pair(frames, T, out_h, out_w, table)
+    ws_bytes = _lib.query("vgpa_da3_resize_workspace_bytes", H, W, out_h, out_w, code)
+    ws = torch.empty(max(ws_bytes, 1), dtype=torch.uint8, device=frames.device)
+    _lib.call("vgpa_da3_resize", frames, T, H, W, out_h, out_w, code, out, x, proc, table, ws, ws_bytes, _stream())
+    return out if table is None else (x, proc)
+
+
+def da3_normalize(frames, table, box=None):
+    """The last stage alone: uint8 [T,H,W,3] and an optional crop box (top, left, h, w) -> (x fp32 [1,T,3,h,w] = ToTensor then Normalize in torchvision's
+    order and roundings, processed_images uint8 [T,h,w,3] = table[c][u]) in one launch"""
+    T, H, W = _da3_frames(frames, "da3_normalize")
+    top, left, h, w = (0, 0, H, W) if box is None else (int(v) for v in box)
+    x, proc = _da3_pair(frames, T, h, w, table)
+    _lib.call("vgpa_da3_normalize", frames, T, H, W, top, left, h, w, x, proc, table, _stream())
+    return x, proc
+
+
 # --------------------------------------------------------------------------------------------- AdaLN-Zero pieces
 class _LNModulateFn(torch.autograd.Function):
     @staticmethod

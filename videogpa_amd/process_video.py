@@ -3,10 +3,11 @@
 contract and the same `compute_metrics` dispatch by metric name ("Consistency_Score" -> (score, motion_norm) tuple,
 "MVCS" -> needs depths / intrinsics / extrinsics, anything else -> compute(gt=, rep=)).
 
-What is NOT here: the input resizing of Depth Anything 3's api.py (cv2), and video decoding.  VGGT itself -- DINOv2
+What is NOT here: video decoding.  VGGT itself -- DINOv2
 patch embedding, aggregator, camera head, depth and point heads -- is `videogpa_amd.vggt.VGGT` (pass it as `vggt_model=VGGT(...)`; any
-other `model(images) -> predictions` works the same way).  Depth Anything 3 -- backbone, DualDPT depth head, camera decoder -- is
-`videogpa_amd.da3.DepthAnything3Net` (pass it as `da3_model=...` with frames already sized to multiples of 14).  Anything else is passed in:
+other `model(images) -> predictions` works the same way).  Depth Anything 3 -- input resizing, backbone, DualDPT depth head, camera decoder -- is
+`videogpa_amd.da3.DepthAnything3` (pass it as `da3_model=...`: frames of any size, `model.inference(frames)` as upstream); the bare
+`videogpa_amd.da3.DepthAnything3Net` is taken too, with frames already sized to multiples of 14.  Anything else is passed in:
   * `frame_sampler(video_path, n_frames) -> uint8 [T,H,W,3]`      (utils/video_utils.py:19-44, decord + cv2 upstream)
   * backbone "vggt":  `backbone_fn(frames) -> dict` with the keys utils/model_utils.py:89-122 returns
       images [T,3,H,W] in [0,1], world_points_from_depth [T,H,W,3], depth_conf [T,H,W], depth, and either
@@ -32,11 +33,15 @@ class VideoProcessor:
         `vggt_model(images [1,T,3,h,518]) -> predictions` is the bare VGGT network: with it the wrapper of utils/model_utils.py:89-122
         (device preprocessing in front, batch squeeze and pose decoding behind) runs here instead of inside `backbone_fn`.
         `da3_model(x [1,T,3,H,W], aux=False) -> {depth, depth_conf, extrinsics, intrinsics}` is the bare Depth Anything 3 network
-        (videogpa_amd.da3.DepthAnything3Net): with it the normalisation in front and the batch squeeze behind run here (`_run_da3`)."""
+        (videogpa_amd.da3.DepthAnything3Net): with it the normalisation in front and the batch squeeze behind run here (`_run_da3`).  A `da3_model`
+        that has `inference` (videogpa_amd.da3.DepthAnything3) is called as the reference calls it and takes frames of any size (`_run_da3_api`)."""
         if vggt_model is not None and backbone_fn is None:
             backbone_fn = lambda frames: self._run_vggt(vggt_model, frames)
         if da3_model is not None and backbone_fn is None:
-            backbone_fn = lambda frames: self._run_da3(da3_model, frames)
+            if hasattr(da3_model, "inference"):        # videogpa_amd.da3.DepthAnything3: called as the reference calls it, frames of any size
+                backbone_fn = lambda frames: self._run_da3_api(da3_model, frames)
+            else:
+                backbone_fn = lambda frames: self._run_da3(da3_model, frames)
         self.device = device or "cuda"
         self.metrics = metrics
         self.backbone = self._resolve_backbone(backbone, model_name)
@@ -93,8 +98,18 @@ class VideoProcessor:
             preds["world_points_from_depth"] = preds["world_points"]
         return preds
 
+    def _run_da3_api(self, model, frames):
+        """pipelines/process_video.py:139: `model.inference([frames[i] ...])` of a `videogpa_amd.da3.DepthAnything3` on `self.device`; the metrics are then
+        computed at the processed size against its `processed_images`, as upstream"""
+        dev = torch.device(self.device)
+        if hasattr(model, "to") and hasattr(model, "eval"):
+            model = model.to(dev).eval()
+            if hasattr(model, "device"):
+                model.device = dev
+        return model.inference(list(frames))
+
     def _run_da3(self, model, frames):
-        """depth_anything_3/api.py:133-273 around the network, without its cv2 input resizing: uint8 frames [T,H,W,3] (array, tensor or list), H and W
+        """depth_anything_3/api.py:133-273 around the bare network, without its input resizing (that is `DepthAnything3`, `_run_da3_api`): uint8 frames [T,H,W,3] (array, tensor or list), H and W
         multiples of 14 -> ImageNet normalisation on the device, the forward under no_grad + bf16 autocast with aux=False (the scorer reads depth and
         conf only), and an object with what `_build_da3_predictions` reads, as device tensors: .processed_images [T,H,W,3] (the input frames), .depth
         [T,H,W], .conf [T,H,W], .extrinsics [T,3,4], .intrinsics [T,3,3]"""
@@ -108,7 +123,8 @@ class VideoProcessor:
         H, W = frames.shape[1:3]
         if H % 14 or W % 14:
             raise ValueError(f"da3_model takes frames sized to multiples of 14, got {H} x {W}: the input resizing of depth_anything_3/api.py "
-                             "(cv2) is the caller's")
+                             "is not part of the bare network; pass da3_model=videogpa_amd.da3.DepthAnything3(model=net), whose inference() resizes "
+                             "frames of any size on the device")
         if hasattr(model, "to") and hasattr(model, "eval"):
             model = model.to(dev).eval()
         frames = frames.to(dev)

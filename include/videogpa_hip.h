@@ -596,6 +596,37 @@ int32_t vgpa_t5_rms(const float* x, const void* y, const int64_t* ids, const voi
  * the tanh GELU and the product in fp32, rounded once.  d_ff a multiple of 8. */
 int32_t vgpa_t5_gated_gelu(const void* u, void* g, int64_t M, int64_t d_ff, vgpa_stream_t stream);
 
+/* ---- SuperPoint keypoint extractor (lightglue.SuperPoint; videogpa_amd/superpoint.py, csrc/superpoint.hip): fp32, channels-last, forward only ----
+ * The 1x1 convolution of vgpa_conv1x1_f32 over relu(x): the producer stored its output before the ReLU.  Same kernel, same sums. */
+int32_t vgpa_conv1x1_relu_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t M, int64_t Cin, int64_t Cout,
+                              vgpa_stream_t stream);
+/* Frames -> conv1a's output before its ReLU, out [T,Ho,Wo,64], in one launch.  mode 0: src uint8 [T,H,W,3] RGB, gray = (9798 R + 19235 G + 3735 B +
+ * 16384) >> 15 (cv2's 8-bit RGB2GRAY restated from memory, not pinned), value = table[gray], table fp32 [256] made on the host as g / 255.0.
+ * mode 1: src fp32 [T,1,H,W].  mode 3: src fp32 [T,3,H,W], value = 0.299 R + 0.587 G + 0.114 B.  table is NULL unless mode 0.  The value image is
+ * resized to (Ho, Wo) as F.interpolate(mode="bilinear", align_corners=False) does in fp32: scale = in / out, src = max(scale (dst + 0.5) - 0.5, 0),
+ * both lerps in torch's order; equal sizes copy exactly.  Then the 3x3 convolution 1 -> 64 with zero padding: w [3][3][1][64], bias [64], 16-byte
+ * aligned like out.  gray, if not NULL, receives the resized value image [T,Ho,Wo]. */
+int32_t vgpa_sp_input_conv1a(const void* src, int32_t mode, const float* table, const float* w, const float* bias, float* out, float* gray, int64_t T,
+                             int64_t H, int64_t W, int64_t Ho, int64_t Wo, vgpa_stream_t stream);
+/* Detector head: x [T,h,w,256] (convPa before its ReLU, 16-byte aligned) -> score [T,8h,8w]: relu, the 1x1 convolution w [256][65] + bias [65],
+ * softmax over the 65, the last (dustbin) channel dropped, channel c of cell (cy, cx) to pixel (8 cy + c / 8, 8 cx + c % 8). */
+int32_t vgpa_sp_head_f32(const float* x, const float* w, const float* bias, float* score, int64_t T, int64_t h, int64_t wd, vgpa_stream_t stream);
+/* simple_nms of lightglue/superpoint.py on score [T,Hs,Ws] (finite values): mask = s == maxpool(s); twice { supp = maxpool(mask) > 0;
+ * s' = where(supp, 0, s); mask |= (s' == maxpool(s')) & ~supp }; out = where(mask, s, 0), windows (2 radius + 1)^2 padded with -inf, radius 1..4.
+ * Exact comparisons only: equal to torch bit for bit.  Then the outer `border` rows and columns are set to -1.  Never in place. */
+int32_t vgpa_sp_nms_f32(const float* score, float* out, int64_t T, int64_t Hs, int64_t Ws, int32_t radius, int32_t border, vgpa_stream_t stream);
+/* Keypoints of nms [T,Hs,Ws]: the pixels with nms > threshold.  A frame with at most kcap of them keeps all, in row-major order; a frame with more
+ * keeps the kcap highest, in descending score, equal scores in row-major order (at the cut too).  kp fp32 [T,kcap,2] = (x, y), sc fp32 [T,kcap],
+ * counts int32 [T]; rows past a frame's count are not written.  kcap <= 4096 or kcap >= Hs Ws.  Deterministic.  workspace 256-byte aligned. */
+size_t vgpa_sp_select_workspace_bytes(int64_t T, int64_t Hs, int64_t Ws);
+int32_t vgpa_sp_select(const float* nms, float threshold, int64_t T, int64_t Hs, int64_t Ws, int64_t kcap, float* kp, float* sc, int32_t* counts,
+                       void* workspace, size_t ws_bytes, vgpa_stream_t stream);
+/* sample_descriptors with s = 8 on the raw descriptor map dmap [T,h,w,256] (convDb's output, 16-byte aligned): out [T,kcap,256] row i of frame t =
+ * normalize(bilinear(normalize(dmap))) at kp [T,kcap,2], for i < counts[t]; normalize is x / max(|x|_2, 1e-12), the sample grid_sample's
+ * (align_corners=True, zeros outside) at ((kp - 3.5) / (8 w - 4.5), (.. h ..)) mapped to [-1, 1]. */
+int32_t vgpa_sp_sample_desc_f32(const float* dmap, const float* kp, const int32_t* counts, float* out, int64_t T, int64_t h, int64_t wd, int64_t kcap,
+                                vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

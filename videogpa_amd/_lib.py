@@ -124,6 +124,13 @@ SIGNATURES = {
     "vgpa_t5_attn_fwd": (I32, [P, P, P, P, P, P, P, P, P, I64, I64, I64, P]),
     "vgpa_t5_rms": (I32, [P, P, P, P, I64, P, P, P, I32, I64, I64, F32, P]),
     "vgpa_t5_gated_gelu": (I32, [P, P, I64, I64, P]),
+    "vgpa_conv1x1_relu_f32": (I32, [P, P, P, P, I64, I64, I64, P]),
+    "vgpa_sp_input_conv1a": (I32, [P, I32, P, P, P, P, P, I64, I64, I64, I64, I64, P]),
+    "vgpa_sp_head_f32": (I32, [P, P, P, P, I64, I64, I64, P]),
+    "vgpa_sp_nms_f32": (I32, [P, P, I64, I64, I64, I32, I32, P]),
+    "vgpa_sp_select_workspace_bytes": (SZ, [I64, I64, I64]),
+    "vgpa_sp_select": (I32, [P, F32, I64, I64, I64, I64, P, P, P, P, SZ, P]),
+    "vgpa_sp_sample_desc_f32": (I32, [P, P, P, P, I64, I64, I64, I64, P]),
 }
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library

@@ -99,6 +99,11 @@ int32_t vgpa_conv1x1_f32(const float* x, const float* w_packed, const float* bia
     return conv_entry<CV_CONV>(x, w_packed, bias, nullptr, nullptr, out, 1, 1, M, Cin, Cout, 1, 1, 0, 0, 0, stream);
 }
 
+int32_t vgpa_conv1x1_relu_f32(const float* x, const float* w_packed, const float* bias, float* out, int64_t M, int64_t Cin, int64_t Cout,
+                              hipStream_t stream) {
+    return conv_entry<CV_CONV>(x, w_packed, bias, nullptr, nullptr, out, 1, 1, M, Cin, Cout, 1, 1, 0, 0, CV_RELU_IN, stream);
+}
+
 int32_t vgpa_dpt_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1, const float* w2,
                           const float* b2, float* preds, float* conf, int64_t N, int64_t h, int64_t w, int64_t C, int64_t H, int64_t W,
                           int32_t output_dim, int32_t activation, hipStream_t stream) {

@@ -2143,3 +2143,106 @@ def t5_gated_gelu(u):
     g = torch.empty(*u.shape[:-1], F2 // 2, device=u.device, dtype=torch.bfloat16)
     _timed("t5_gated_gelu", 3.0 * u.numel(), lambda: _lib.call("vgpa_t5_gated_gelu", u, g, u.numel() // F2, F2 // 2, _stream()), "byte")
     return g
+
+
+# ---- SuperPoint around its convolutions (csrc/superpoint.hip): fp32, channels-last, forward only -------------------------------------------------
+def conv1x1_relu_f32(x, w_packed, bias=None):
+    """conv1x1_f32 of relu(x): for a producer that stored its output before the ReLU"""
+    _heads_in(x, w_packed, bias)
+    Cin, Cout = w_packed.shape
+    if x.shape[-1] != Cin or Cin % 16 or Cout % 16:
+        raise RuntimeError(f"conv1x1_relu_f32: weight {tuple(w_packed.shape)} does not fit input {tuple(x.shape)} (channels in multiples of 16)")
+    out = torch.empty(*x.shape[:-1], Cout, device=x.device, dtype=torch.float32)
+    M = out.numel() // Cout
+    _timed("conv1x1_relu_f32", 2.0 * M * Cin * Cout, lambda: _lib.call("vgpa_conv1x1_relu_f32", x, w_packed, bias, out, M, Cin, Cout, _stream()))
+    return out
+
+
+def sp_gray_table(device=None):
+    """g / 255.0 for the 256 bytes as the reference's `_frame2tensor` forms it: float64 division, then .float()"""
+    t = (torch.arange(256, dtype=torch.float64) / 255.0).float()
+    return t if device is None else t.to(device)
+
+
+def sp_input_conv1a(src, w_packed, bias, size=None, table=None, return_gray=False):
+    """uint8 RGB frames [T,H,W,3], or a float image [T,1,H,W] / [T,3,H,W] -> conv1a's pre-ReLU output [T,Ho,Wo,64] (gray conversion, g / 255 through
+    `table`, bilinear resize to `size` = (Ho, Wo), the 1 -> 64 convolution); with return_gray also the resized gray image [T,Ho,Wo]"""
+    _heads_in(w_packed, bias)
+    _req(src)
+    if src.dtype == torch.uint8:
+        if src.dim() != 4 or src.shape[-1] != 3:
+            raise RuntimeError(f"sp_input_conv1a: uint8 frames are [T,H,W,3], got {tuple(src.shape)}")
+        mode, (T, H, W) = 0, src.shape[:3]
+        table = sp_gray_table(src.device) if table is None else _req(table, torch.float32)
+        if table.numel() != 256:
+            raise RuntimeError("sp_input_conv1a: the gray table holds 256 values")
+    elif src.dtype == torch.float32 and src.dim() == 4 and src.shape[1] in (1, 3):
+        _heads_in(src)
+        mode, T, (H, W), table = int(src.shape[1]), src.shape[0], src.shape[2:], None
+    else:
+        raise RuntimeError(f"sp_input_conv1a: expected uint8 [T,H,W,3] or fp32 [T,1|3,H,W], got {src.dtype} {tuple(src.shape)}")
+    if tuple(w_packed.shape) != (3, 3, 1, 64) or bias.numel() != 64:
+        raise RuntimeError(f"sp_input_conv1a: conv1a is [3,3,1,64] with 64 biases, got {tuple(w_packed.shape)}")
+    Ho, Wo = (H, W) if size is None else size
+    out = torch.empty(T, Ho, Wo, 64, device=src.device, dtype=torch.float32)
+    gray = torch.empty(T, Ho, Wo, device=src.device, dtype=torch.float32) if return_gray else None
+    _timed("sp_input_conv1a", float(src.numel() * src.element_size() + 4 * out.numel()),
+           lambda: _lib.call("vgpa_sp_input_conv1a", src, mode, table, w_packed, bias, out, gray, T, H, W, Ho, Wo, _stream()), "byte")
+    return (out, gray) if return_gray else out
+
+
+def sp_head_f32(x, w, bias):
+    """convPa's pre-ReLU map [T,h,w,256] -> the score image [T,8h,8w]: relu, 1x1 to 65 (w [256,65]), softmax, dustbin dropped, depth-to-space"""
+    _heads_in(x, w, bias)
+    if x.dim() != 4 or x.shape[-1] != 256 or tuple(w.shape) != (256, 65) or bias.numel() != 65:
+        raise RuntimeError(f"sp_head_f32: expected x [T,h,w,256], w [256,65], bias [65], got {tuple(x.shape)}, {tuple(w.shape)}, {tuple(bias.shape)}")
+    T, h, wd, _ = x.shape
+    score = torch.empty(T, 8 * h, 8 * wd, device=x.device, dtype=torch.float32)
+    _timed("sp_head_f32", 2.0 * T * h * wd * 256 * 65, lambda: _lib.call("vgpa_sp_head_f32", x, w, bias, score, T, h, wd, _stream()))
+    return score
+
+
+def sp_nms_f32(score, radius=4, border=0):
+    """lightglue's simple_nms (three rounds, exact) of score [T,Hs,Ws], then the outer `border` rows and columns set to -1"""
+    _heads_in(score)
+    if score.dim() != 3 or not 1 <= int(radius) <= 4 or int(border) < 0:
+        raise RuntimeError(f"sp_nms_f32: expected [T,Hs,Ws], radius 1..4 and border >= 0, got {tuple(score.shape)}, {radius}, {border}")
+    T, Hs, Ws = score.shape
+    out = torch.empty_like(score)
+    _timed("sp_nms_f32", 8.0 * score.numel(), lambda: _lib.call("vgpa_sp_nms_f32", score, out, T, Hs, Ws, int(radius), int(border), _stream()), "byte")
+    return out
+
+
+SP_MAX_CUT = 4096   # a cut sorts its survivors in LDS
+
+
+def sp_select(nms, threshold, max_num_keypoints=None):
+    """pixels of nms [T,Hs,Ws] above `threshold`: (keypoints [T,K,2] as (x, y), scores [T,K], counts int32 [T]), rows past a frame's count unwritten.
+    All of them in row-major order when they fit `max_num_keypoints`; else the top ones in descending score, ties in row-major order."""
+    _heads_in(nms)
+    T, Hs, Ws = nms.shape
+    k = Hs * Ws if max_num_keypoints is None else min(int(max_num_keypoints), Hs * Ws)
+    if k < 1 or (SP_MAX_CUT < k < Hs * Ws):
+        raise RuntimeError(f"sp_select: max_num_keypoints is 1..{SP_MAX_CUT} or None, got {max_num_keypoints}")
+    kp = torch.empty(T, k, 2, device=nms.device, dtype=torch.float32)
+    sc = torch.empty(T, k, device=nms.device, dtype=torch.float32)
+    counts = torch.empty(T, device=nms.device, dtype=torch.int32)
+    ws_bytes = _lib.query("vgpa_sp_select_workspace_bytes", T, Hs, Ws)
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=nms.device)
+    _timed("sp_select", 12.0 * nms.numel(),
+           lambda: _lib.call("vgpa_sp_select", nms, float(threshold), T, Hs, Ws, k, kp, sc, counts, ws, ws_bytes, _stream()), "byte")
+    return kp, sc, counts
+
+
+def sp_sample_desc_f32(dmap, kp, counts):
+    """sample_descriptors (s = 8) of the raw descriptor map [T,h,w,256] at kp [T,K,2] -> [T,K,256], rows below counts[t] only"""
+    _heads_in(dmap, kp)
+    _req(counts, torch.int32)
+    T, h, wd, C = dmap.shape
+    if C != 256 or kp.dim() != 3 or kp.shape[0] != T or kp.shape[2] != 2 or counts.numel() != T:
+        raise RuntimeError(f"sp_sample_desc_f32: expected dmap [T,h,w,256], kp [T,K,2], counts [T], got {tuple(dmap.shape)}, {tuple(kp.shape)}")
+    K = kp.shape[1]
+    out = torch.empty(T, K, 256, device=dmap.device, dtype=torch.float32)
+    _timed("sp_sample_desc_f32", 4.0 * 5 * T * K * 256,
+           lambda: _lib.call("vgpa_sp_sample_desc_f32", dmap, kp, counts, out, T, h, wd, K, _stream()), "byte")
+    return out

@@ -2,8 +2,8 @@
 (utils/projection_utils.py), `get_colored_pointcloud` (utils/pointcloud_utils.py), `Metric` / `MSEMetric`
 / `PSNRMetric` / `SSIMMetric` (metrics/base.py, metrics/mse.py), `compute_motion_score_vectorized` / `Consistency_Score`
 (metrics/consistency_score.py) and the geometry half of `EpipolarMetric` (metrics/epipolar.py:161-213).
-Kernels: videogpa_amd/csrc/{scorer,scorer2,scorer_ssim}.hip.  Third-party networks (LPIPS-VGG, SIFT / LightGlue matchers, VGGT / DA3
-backbones) are outside the hot path: they are passed in as callables / precomputed matches."""
+Kernels: videogpa_amd/csrc/{scorer,scorer2,scorer_ssim}.hip.  Networks (LPIPS-VGG, SuperPoint in front of the caller's LightGlue, VGGT / DA3
+backbones) are passed in: the project's own device modules, or third-party callables / precomputed matches (SIFT, LightGlue's transformer)."""
 from abc import ABC, abstractmethod
 from typing import Any
 
@@ -330,9 +330,73 @@ def epipolar_errors(pts1_list, pts2_list, return_F=False):
     return (err, Fm.view(P, 3, 3)) if return_F else err
 
 
+def _rbd(d):
+    """lightglue.utils.rbd: drop the batch axis of every entry"""
+    return {k: v[0] if isinstance(v, (torch.Tensor, np.ndarray, list)) else v for k, v in d.items()}
+
+
+class LightGlueMatcher:
+    """The reference's LightGlueMatcher (metrics/epipolar.py:72-139) with the two networks passed in.  `extractor` is SuperPoint on the device
+    (videogpa_amd.superpoint.SuperPoint: gray conversion, / 255, resize, network, NMS, selection and descriptors all run there);
+    `matcher({'image0': feats0, 'image1': feats1}) -> {'matches': ...}` is the caller's LightGlue, the one third-party piece left.
+    Unlike the reference, nothing is swallowed: an exception inside either network reaches the caller."""
+
+    def __init__(self, min_matches: int = 20, device: str = "cuda", extractor=None, matcher=None):
+        if matcher is None:
+            raise RuntimeError("LightGlueMatcher: the LightGlue transformer is not implemented on the device yet; pass matcher=lightglue.LightGlue("
+                               "features='superpoint').eval().cuda() (or any callable that maps {'image0': feats0, 'image1': feats1} to {'matches': ...})")
+        if extractor is None:
+            from .superpoint import SuperPoint
+            extractor = SuperPoint(max_num_keypoints=2048).to(device)                 # raises: trained weights are local files, never fetched
+        self.min_matches, self.device, self.extractor, self.matcher = min_matches, device, extractor, matcher
+
+    @staticmethod
+    def _frames_u8(frames):
+        """a clip (array / tensor / list of frames) as uint8 [T,H,W,3] the way the reference's `_to_numpy_thwc` and `_frame2tensor` read it"""
+        x = torch.stack([torch.as_tensor(f) for f in frames]) if isinstance(frames, (list, tuple)) else torch.as_tensor(frames)
+        if x.dim() == 3:
+            x = x[None]
+        if x.dim() != 4:
+            raise ValueError(f"LightGlueMatcher: frames are [T,H,W,3] or [T,3,H,W], got {tuple(x.shape)}")
+        if x.shape[1] in (1, 3) and x.shape[-1] not in (1, 3):
+            x = x.permute(0, 2, 3, 1)
+        if x.dtype != torch.uint8:
+            x = x.float()
+            x = (x + 1.0) * 127.5 if float(x.min()) < 0 else (x * 255.0 if float(x.max()) <= 1.0 else x)
+            x = x.clamp(0, 255).to(torch.uint8)
+        if x.shape[-1] == 1:
+            x = x.expand(-1, -1, -1, 3)                                                # the gray formula maps (g, g, g) to g exactly
+        return x.contiguous()
+
+    def _pair(self, feats0, feats1):
+        with torch.no_grad():
+            matches01 = self.matcher({"image0": feats0, "image1": feats1})
+        f0, f1, m01 = _rbd(feats0), _rbd(feats1), _rbd(matches01)
+        matches = m01["matches"]
+        k0, k1 = f0["keypoints"][matches[..., 0]], f1["keypoints"][matches[..., 1]]
+        n = len(k0)
+        meta = {"descriptor_type": "lightglue", "total_matches": n}
+        if n < self.min_matches:
+            meta["error"] = f"Too few matches ({n})"
+            return None, None, n, meta
+        return k0.cpu().numpy(), k1.cpu().numpy(), n, meta
+
+    def get_matched_points(self, frame1, frame2):
+        feats = self.extractor.extract_clip(self._frames_u8([frame1, frame2]))
+        return self._pair(feats[0], feats[1])
+
+    def __call__(self, frame1, frame2):
+        return self.get_matched_points(frame1, frame2)[:2]
+
+    def match_clip(self, frames):
+        """[(pts1, pts2)] of the consecutive pairs, every frame extracted once (the reference extracts every inner frame twice)"""
+        feats = self.extractor.extract_clip(self._frames_u8(frames))
+        return [self._pair(feats[i], feats[i + 1])[:2] for i in range(len(feats) - 1)]
+
+
 class EpipolarMetric(Metric):
-    """Video-level epipolar consistency (metrics/epipolar.py:142-232).  `matcher(frame_i, frame_j) -> (pts1, pts2)` is the
-    caller's SIFT / LightGlue front end (third-party); the 8-point + Sampson geometry runs on device."""
+    """Video-level epipolar consistency (metrics/epipolar.py:142-232).  `matcher(frame_i, frame_j) -> (pts1, pts2)` is the front end:
+    `LightGlueMatcher` above (SuperPoint on the device, the caller's LightGlue) or any callable; the 8-point + Sampson geometry runs on device."""
 
     def __init__(self, descriptor_type: str = "sift", ratio_thresh: float = 0.75, min_matches: int = 20, device: str = None, matcher=None):
         """Reference signature (metrics/epipolar.py:146-158) + `matcher`: the reference builds a cv2-SIFT or LightGlue matcher from
@@ -353,8 +417,11 @@ class EpipolarMetric(Metric):
 
     def compute(self, *, gt, rep=None, **kwargs) -> float:
         if self.matcher is None:
-            raise RuntimeError("EpipolarMetric.compute needs a keypoint matcher (SIFT / LightGlue are third-party); "
-                               "use compute_from_matches with precomputed correspondences")
+            raise RuntimeError("EpipolarMetric.compute needs a keypoint matcher (SIFT / LightGlue are third-party; LightGlueMatcher runs SuperPoint "
+                               "on the device in front of the caller's LightGlue); use compute_from_matches with precomputed correspondences")
         frames = gt
-        m = [self.matcher(frames[i], frames[i + 1]) for i in range(len(frames) - 1)]
+        if hasattr(self.matcher, "match_clip"):
+            m = self.matcher.match_clip(frames)
+        else:
+            m = [self.matcher(frames[i], frames[i + 1]) for i in range(len(frames) - 1)]
         return self.compute_from_matches([a for a, _ in m], [b for _, b in m])

@@ -367,10 +367,11 @@ int32_t vgpa_epipolar_sampson(const float* p1, const float* p2, const int64_t* o
                               float* F_out, vgpa_stream_t stream);
 
 /* Confidence cut of get_colored_pointcloud, utils/pointcloud_utils.py:44-73: thr_out[0] (device) = k-th largest valid
- * confidence, k = max(1, ceil(n_valid * (1 - conf_thres / 100))); -inf for conf_thres <= 0 or no valid point.  On-device
+ * confidence, k = max(1, ceil(n_valid * (1 - conf_thres / 100))) in double, as the reference forms it from the Python float (a
+ * float32 conf_thres moves k by one, e.g. 33.3 at n_valid = 1000); -inf for conf_thres <= 0 or no valid point.  On-device
  * radix select (replaces torch.topk + .item()). */
 size_t vgpa_conf_threshold_workspace_bytes(void);
-int32_t vgpa_conf_threshold(const float* conf, int64_t N, float conf_thres, float* thr_out, void* workspace, size_t ws_bytes,
+int32_t vgpa_conf_threshold(const float* conf, int64_t N, double conf_thres, float* thr_out, void* workspace, size_t ws_bytes,
                             vgpa_stream_t stream);
 /* MSEMetric / PSNRMetric.compute incl. the bilinear-resize branch, metrics/mse.py:14-29,56-80: rep [T,C,H2,W2] is resized to
  * gt's [H,W] (F.interpolate bilinear, align_corners=False).  psnr 0: mse; 1: 10 log10(1/mse), 100 when mse == 0.

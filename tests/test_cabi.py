@@ -14,7 +14,7 @@ def _header_symbols():
     return set(re.findall(r"\b(vgpa_[a-z0-9_]+)\s*\(", src))
 
 
-_CTYPE = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "size_t": ctypes.c_size_t, "vgpa_stream_t": ctypes.c_void_p}
+_CTYPE = {"int64_t": ctypes.c_int64, "int32_t": ctypes.c_int32, "float": ctypes.c_float, "double": ctypes.c_double, "size_t": ctypes.c_size_t, "vgpa_stream_t": ctypes.c_void_p}
 
 
 def _header_signatures(variants):

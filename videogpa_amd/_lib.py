@@ -8,14 +8,14 @@ import os
 # would fail; after torch, our NEEDED libamdhip64.so.7 resolves to the instance already loaded.
 import torch  # noqa: F401
 
-from ctypes import c_float, c_int32, c_int64, c_size_t, c_void_p
+from ctypes import c_double, c_float, c_int32, c_int64, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # VGPA_LIB=<path> selects another build of the SAME C-ABI (tools/build_variant.sh writes var/lib_NAME.so) for in-session A/B
 # measurements, so nothing ever has to be copied over the product library.
 LIB_PATH = os.environ.get("VGPA_LIB") or os.path.join(_HERE, "csrc", "libvgpa_hip.so")
 
-P, I64, I32, F32, SZ = c_void_p, c_int64, c_int32, c_float, c_size_t
+P, I64, I32, F32, F64, SZ = c_void_p, c_int64, c_int32, c_float, c_double, c_size_t
 
 # name -> (restype, [argtypes]) ; must mirror include/videogpa_hip.h (tests/test_cabi.py checks every prototype against it)
 SIGNATURES = {
@@ -81,7 +81,7 @@ SIGNATURES = {
     "vgpa_project_points_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_project_points": (I32, [P, P, P, F32, P, P, P, I32, I64, I64, I64, I64, P, P, P, SZ, P]),
     "vgpa_conf_threshold_workspace_bytes": (SZ, []),
-    "vgpa_conf_threshold": (I32, [P, I64, F32, P, P, SZ, P]),
+    "vgpa_conf_threshold": (I32, [P, I64, F64, P, P, SZ, P]),
     "vgpa_frame_metric_workspace_bytes": (SZ, []),
     "vgpa_frame_metric": (I32, [P, I32, I32, I32, P, I32, I32, I32, I64, I64, I64, I64, I64, I64, I32, P, P, SZ, P]),
     "vgpa_frame_ssim_workspace_bytes": (SZ, [I64, I64, I64, I64]),

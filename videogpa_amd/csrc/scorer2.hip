@@ -382,16 +382,16 @@ size_t vgpa_conf_threshold_workspace_bytes(void) { return sizeof(SelState); }
 // thr_out[0] (device fp32) = the k-th largest valid confidence, k = max(1, ceil(n_valid * (1 - conf_thres/100))): points with
 // conf >= thr (and valid) are the top (100 - conf_thres) % that get_colored_pointcloud keeps (utils/pointcloud_utils.py:55-73).
 // conf_thres <= 0 or no valid point: -inf.  conf fp32 [N].
-int32_t vgpa_conf_threshold(const float* conf, int64_t N, float conf_thres, float* thr_out, void* workspace, size_t ws_bytes,
+int32_t vgpa_conf_threshold(const float* conf, int64_t N, double conf_thres, float* thr_out, void* workspace, size_t ws_bytes,
                             hipStream_t stream) {
     if (!conf || !thr_out || !workspace || N <= 0) return VGPA_ERR_INVALID;
     if (ws_bytes < sizeof(SelState)) return VGPA_ERR_WORKSPACE;
     SelState* st = (SelState*)workspace;
     if (hipMemsetAsync(st, 0, sizeof(SelState), stream) != hipSuccess) return VGPA_ERR_LAUNCH;
-    double keep = 1.0 - (double)conf_thres / 100.0;
+    double keep = 1.0 - conf_thres / 100.0;   // conf_thres is the caller's Python double: a float32 here can move k by one
     keep = keep < 0.0 ? 0.0 : (keep > 1.0 ? 1.0 : keep);
     const unsigned nb = s2_grid(N, 1024);
-    if (conf_thres <= 0.f) {
+    if (conf_thres <= 0.0) {
         if (hipMemsetD32Async((hipDeviceptr_t)thr_out, (int)0xFF800000u /* -inf */, 1, stream) != hipSuccess) return VGPA_ERR_LAUNCH;
         return VGPA_OK;
     }

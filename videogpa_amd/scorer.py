@@ -65,7 +65,8 @@ def batch_reproject(pc, colors, intrinsics, extrinsics, H, W, save_path=None):
 
 def confidence_threshold(conf, conf_thres):
     """The top-(100 - conf_thres) % confidence cut of utils/pointcloud_utils.py:55-73 -> device fp32 tensor [1] holding the
-    k-th largest valid confidence (-inf when nothing is cut).  On-device radix select: no sort, no host round trip."""
+    k-th largest valid confidence (-inf when nothing is cut).  On-device radix select: no sort, no host round trip.  conf_thres travels as the
+    Python double it is: the rank k = max(1, ceil(n (1 - conf_thres / 100))) formed from a float32 threshold is one off for e.g. 33.3 at n = 1000."""
     vals = _dev_f32(conf).reshape(-1)
     thr = torch.empty(1, dtype=torch.float32, device=vals.device)
     if vals.numel() == 0:

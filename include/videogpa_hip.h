@@ -628,6 +628,59 @@ int32_t vgpa_sp_select(const float* nms, float threshold, int64_t T, int64_t Hs,
 int32_t vgpa_sp_sample_desc_f32(const float* dmap, const float* kp, const int32_t* counts, float* out, int64_t T, int64_t h, int64_t wd, int64_t kcap,
                                 vgpa_stream_t stream);
 
+/* ---- LightGlue (features = "superpoint": 256 features, 4 heads of 64) between its GEMMs: csrc/lightglue.hip.  Forward only, fp32 in and out.
+ * Variable-length form: a sample owns R rows of an activation; rows [0, S0) are image 0 with count c0[b], rows [S0, R) image 1 with count c1[b]
+ * (c1 NULL: one segment and S0 == R).  Counts are device int32 [B], clamped to the segment; rows at or past a count are never read as keys and never
+ * written.  A sample's result does not depend on B, on R or on the other samples, bit for bit; no float atomics; at most 4096 rows per segment. */
+/* The Linears and sim in exact fp32 (v_mfma_f32_32x32x2_f32): c[b c_batch_stride + r ldc + n] = alpha sum_k a[b a_batch_stride + r lda + k]
+ * bm[b b_batch_stride + n ldb + k] + bias[n] for r < R, n < N, or, with accumulate (then bias is NULL), c += alpha sum.  Both operands are row-major
+ * over k: bm is an nn.Linear weight [N][K] as it stands (batch stride 0) or a second activation.  K is a multiple of 16; a, bm 16-byte aligned, lda, ldb
+ * and their batch strides multiples of 4.  Every element is one fixed sum over k that does not depend on B, R, N or the element's place: a row's result is
+ * the same bits in any batch.  c0 not NULL: only rows below the counts of the segments (S0, c0, c1) are computed and written; cn (int32 [B], may be
+ * NULL): only columns below cn[b]. */
+int32_t vgpa_lg_gemm(const float* a, int64_t a_batch_stride, int64_t lda, const float* bm, int64_t b_batch_stride, int64_t ldb, const float* bias, float* c,
+                     int64_t c_batch_stride, int64_t ldc, int64_t B, int64_t R, int64_t N, int64_t K, float alpha, int32_t accumulate, int64_t S0,
+                     const int32_t* c0, const int32_t* c1, const int32_t* cn, vgpa_stream_t stream);
+/* o = softmax(q k^T / 8) v per head of 64.  ptrs holds, per direction, {q, k, v, o, nq, nk, qcos, qsin, kcos, ksin} (10 pointers) and strides
+ * {q_b, q_h, q_t, k_b, k_h, k_t, v_b, v_h, v_t, o_b, o_t, rq_b, rk_b, nq_max, nk_max, 0} (16 values, in elements): q, k, v are fp32 views whose element
+ * (b, h, t, d) is at b x_b + h x_h + t x_t + d dim_stride, dim_stride 1 or 3 (3: the interleaved Wqkv output read in place); o fp32 with head h at
+ * o[b o_b + t o_t + 64 h], 16-byte aligned rows; nq / nk int32 [B]; the rotary tables fp32 [.][32] cos and sin with batch stride rq_b / rk_b, or NULL.
+ * The loader forms rope(x) q_premul in fp32 for q and k and rounds once to fp16; both products are fp16 MFMA with fp32 accumulators, the softmax is fp32
+ * and online, the weights are rounded to fp16 and normalised by their rounded sum.  nk = 0: the nq rows are written as 0.  ndir 1 or 2 directions
+ * (blockIdx.z) in one launch. */
+int32_t vgpa_lg_attn_fwd(const void* const* ptrs, const int64_t* strides, int64_t B, int64_t H, int64_t ndir, int64_t dim_stride, float q_premul,
+                         vgpa_stream_t stream);
+/* cos / sin of p = Wr k' (Wr fp32 [32][2]) for kpts [B,N,2], k' = (k - size / 2) / (max(size) / 2), size = image_size [B,2] or, when NULL,
+ * 1 + max - min over the sample's own keypoints; row i of sample b goes to out[b out_batch_stride + 32 i ..]. */
+int32_t vgpa_lg_posenc(const float* kpts, const int32_t* counts, const float* image_size, const float* Wr, float* cos_out, float* sin_out, int64_t B, int64_t N,
+                       int64_t out_batch_stride, vgpa_stream_t stream);
+/* h [B R][512] = gelu_erf(LayerNorm(u [B R][512]; gamma, beta, eps)).  resid not NULL: resid[row resid_stride + 0..255] += resid_bias, the bias of the
+ * GEMM that then accumulates into the residual stream. */
+int32_t vgpa_lg_ln_gelu(const float* u, const float* gamma, const float* beta, float eps, float* h, float* resid, int64_t resid_stride, const float* resid_bias,
+                        int64_t B, int64_t R, int64_t S0, const int32_t* c0, const int32_t* c1, vgpa_stream_t stream);
+/* z = w . x[row] + bias over 256 features, conf = sigmoid(z) (either output may be NULL); below[b] += number of the sample's rows with conf < thr,
+ * compared in double (below is zeroed by the caller; an integer count). */
+int32_t vgpa_lg_confidence(const float* x, int64_t x_stride, const float* w, float bias, float* conf, float* z, double thr, int32_t* below, int64_t B, int64_t R,
+                           int64_t S0, const int32_t* c0, const int32_t* c1, vgpa_stream_t stream);
+/* Point pruning.  A segment with more than prune_min rows keeps row i iff match[i] > thr_keep or conf[i] <= thr_conf (in double); any other keeps all and
+ * leaves prune alone.  Kept rows move, in order, to the front of the segment of the OUTPUT buffers (never in place): 256 features of x, the rotary
+ * tables [B R][32], ind; prune{0,1}[b][ind] += 1 ([B][P0], [B][P1]); c{0,1}_out = rows kept; keep_out (may be NULL) the mask by input row. */
+int32_t vgpa_lg_prune(const float* conf, const float* match, double thr_conf, double thr_keep, int64_t prune_min, const float* x_in, float* x_out, int64_t x_stride,
+                      const float* cos_in, const float* sin_in, float* cos_out, float* sin_out, const int32_t* ind_in, int32_t* ind_out, int32_t* prune0,
+                      int32_t* prune1, int64_t P0, int64_t P1, int64_t B, int64_t R, int64_t S0, const int32_t* c0, const int32_t* c1, int32_t* c0_out,
+                      int32_t* c1_out, uint8_t* keep_out, vgpa_stream_t stream);
+/* Assignment from sim [B,Mmax,Nmax], the matchability logits z0 [B,Mmax], z1 [B,Nmax] and the counts m, n.  stages is a bit set:
+ * 1 = max and log-sum-exp of sim by row and column; 2 = maximum and argmax by row and column of the log score
+ * ((sim - rmax) - rlog) + ((sim - cmax) - clog) + (logsigmoid(z0) + logsigmoid(z1)), TIES TO THE LOWEST INDEX as torch.max on the CPU, and, if scores is
+ * not NULL, the full log assignment with its dustbins in scores [B,Mmax+1,Nmax+1] (dustbin row at m, column at n); 4 = mutual check, exp, score > thr
+ * (double): matches0 [B,M0] / matches1 [B,N0] / mscores0 / mscores1 (pre-filled by the caller with -1 / 0; written through ind0 / ind1 [B,Mmax] / [B,Nmax]
+ * when given) and the valid (i, j) in row order in matches [B,M0,2] with mscores [B,M0] and nmatch [B].  The workspace holds, as fp32 / int32 words,
+ * rmax, rlog, rbest, rarg [B Mmax] each, then cmax, clog, cbest, carg [B Nmax] each. */
+size_t vgpa_lg_assign_workspace_bytes(int64_t B, int64_t Mmax, int64_t Nmax);
+int32_t vgpa_lg_assign(const float* sim, const float* z0, const float* z1, const int32_t* m, const int32_t* n, int64_t B, int64_t Mmax, int64_t Nmax, double thr,
+                       const int32_t* ind0, const int32_t* ind1, int64_t M0, int64_t N0, int32_t* matches0, int32_t* matches1, float* mscores0, float* mscores1,
+                       int32_t* matches, float* mscores, int32_t* nmatch, float* scores, int32_t stages, void* workspace, size_t ws_bytes, vgpa_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

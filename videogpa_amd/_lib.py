@@ -131,6 +131,14 @@ SIGNATURES = {
     "vgpa_sp_select_workspace_bytes": (SZ, [I64, I64, I64]),
     "vgpa_sp_select": (I32, [P, F32, I64, I64, I64, I64, P, P, P, P, SZ, P]),
     "vgpa_sp_sample_desc_f32": (I32, [P, P, P, P, I64, I64, I64, I64, P]),
+    "vgpa_lg_gemm": (I32, [P, I64, I64, P, I64, I64, P, P, I64, I64, I64, I64, I64, I64, F32, I32, I64, P, P, P, P]),
+    "vgpa_lg_attn_fwd": (I32, [P, P, I64, I64, I64, I64, F32, P]),
+    "vgpa_lg_posenc": (I32, [P, P, P, P, P, P, I64, I64, I64, P]),
+    "vgpa_lg_ln_gelu": (I32, [P, P, P, F32, P, P, I64, P, I64, I64, I64, P, P, P]),
+    "vgpa_lg_confidence": (I32, [P, I64, P, F32, P, P, F64, P, I64, I64, I64, P, P, P]),
+    "vgpa_lg_prune": (I32, [P, P, F64, F64, I64, P, P, I64, P, P, P, P, P, P, P, P, I64, I64, I64, I64, I64, P, P, P, P, P, P]),
+    "vgpa_lg_assign_workspace_bytes": (SZ, [I64, I64, I64]),
+    "vgpa_lg_assign": (I32, [P, P, P, P, P, I64, I64, I64, F64, P, P, I64, I64, P, P, P, P, P, P, P, P, I32, P, SZ, P]),
 }
 
 # exported only by variant builds (tools/build_variant.sh -> VGPA_LIB=...): measured-slower experiments kept out of the product library

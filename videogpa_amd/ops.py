@@ -2246,3 +2246,232 @@ def sp_sample_desc_f32(dmap, kp, counts):
     _timed("sp_sample_desc_f32", 4.0 * 5 * T * K * 256,
            lambda: _lib.call("vgpa_sp_sample_desc_f32", dmap, kp, counts, out, T, h, wd, K, _stream()), "byte")
     return out
+
+
+# ---- LightGlue between its GEMMs (csrc/lightglue.hip): fp32, forward only, variable-length --------------------------------------------------------
+LG_MAX_N = 4096   # rows per image
+
+
+def _lg_f32(name, *ts, contiguous=True):
+    for t in ts:
+        if t is not None:
+            _req(t, torch.float32, contiguous=contiguous)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in ts):
+        raise RuntimeError(f"{name} is forward only: call it under torch.no_grad()")
+
+
+def _lg_seg(name, B, R, seg):
+    """seg = (S0, c0, c1): rows [0, S0) of a sample are image 0 with counts c0 int32 [B], rows [S0, R) image 1 with counts c1 (None: one segment)"""
+    S0, c0, c1 = seg
+    for c in (c0, c1):
+        if c is not None and (_req(c, torch.int32).numel() != B):
+            raise RuntimeError(f"{name}: counts are int32 [B] = [{B}]")
+    if not (0 < S0 <= R and (S0 < R if c1 is not None else S0 == R) and S0 <= LG_MAX_N and R - S0 <= LG_MAX_N):
+        raise RuntimeError(f"{name}: segments S0 = {S0} of R = {R} rows (at most {LG_MAX_N} rows per image)")
+    return int(S0), c0, c1
+
+
+def lg_gemm(a, w, out=None, bias=None, accumulate=False, alpha=1.0, seg=None, ncount=None):
+    """out[b, r, n] = alpha sum_k a[b, r, k] w[(b,) n, k] + bias[n] (accumulate: out += alpha sum, no bias) in exact fp32.  a [B,R,K] and out [B,R,N]
+    are views with contiguous rows and one batch stride, w an nn.Linear weight [N,K] as it stands or a second activation view [B,N,K]; K a multiple of
+    16.  Every element is one fixed sum over k wherever it sits, so a sample's rows come out bit-equal in any batch (a vendor GEMM may change its order
+    with the row count).  seg = (S0, c0, c1): only rows below the counts are computed and written; ncount int32 [B]: only columns below it."""
+    _lg_f32("lg_gemm", a, w, out, contiguous=False)
+    _lg_f32("lg_gemm", bias)
+    if a.dim() != 3 or w.dim() not in (2, 3) or a.stride(2) != 1 or w.stride(-1) != 1 or a.shape[2] != w.shape[-1] or (w.dim() == 3 and w.shape[0] != a.shape[0]):
+        raise RuntimeError(f"lg_gemm: a [B,R,K] and w [N,K] | [B,N,K] with contiguous rows, got {tuple(a.shape)}, {tuple(w.shape)}")
+    B, R, K = a.shape
+    N = w.shape[-2]
+    if out is None:
+        if accumulate:
+            raise RuntimeError("lg_gemm: accumulate needs out")
+        out = torch.empty(B, R, N, device=a.device, dtype=torch.float32)
+    if tuple(out.shape) != (B, R, N) or out.stride(2) != 1 or K % 16 or (bias is not None and (accumulate or bias.numel() != N)):
+        raise RuntimeError(f"lg_gemm: out is a [B,R,N] = [{B},{R},{N}] view with contiguous rows, K a multiple of 16, bias [N] without accumulate")
+    S0, c0, c1 = (0, None, None) if seg is None else _lg_seg("lg_gemm", B, R, seg)
+    if ncount is not None and _req(ncount, torch.int32).numel() != B:
+        raise RuntimeError("lg_gemm: ncount is int32 [B]")
+    _timed("lg_gemm", 2.0 * B * R * N * K,
+           lambda: _lib.call("vgpa_lg_gemm", a, a.stride(0), a.stride(1), w, w.stride(0) if w.dim() == 3 else 0, w.stride(-2), bias, out, out.stride(0),
+                             out.stride(1), B, R, N, K, float(alpha), int(bool(accumulate)), S0, c0, c1, ncount, _stream()))
+    return out
+
+
+def lg_attention(dirs, q_premul=1.0):
+    """softmax(q k^T / 8) v per head of 64 for one or two directions in one launch.  Each direction is a dict: q [B,Tq,H,64], k, v [B,Tk,H,64] fp32 VIEWS
+    (last-dim stride 1, or 3 for the interleaved Wqkv output, the same in all of them), nq, nk int32 [B], rope_q / rope_k = (cos, sin) views
+    [B,T,32] or None, out = an fp32 [B,Tq,H*64] view (last dim contiguous; created when absent).  The loader applies rotary and q_premul to q and k in fp32
+    and rounds once to fp16.  -> the list of outs.  Rows at or past nq are not written; nk = 0 writes zeros."""
+    if len(dirs) not in (1, 2):
+        raise RuntimeError("lg_attention: one or two directions")
+    B, _, H, _ = dirs[0]["q"].shape
+    ds = dirs[0]["q"].stride(3)
+    ptrs, strides, outs, keep = [], [], [], []
+    for d in dirs:
+        q, k, v = d["q"], d["k"], d["v"]
+        _lg_f32("lg_attention", q, k, v, contiguous=False)
+        if q.dim() != 4 or q.shape[3] != 64 or k.shape != v.shape or k.shape[0] != B or q.shape[0] != B or k.shape[2:] != q.shape[2:] or q.shape[2] != H:
+            raise RuntimeError(f"lg_attention: q [B,Tq,H,64] and k, v [B,Tk,H,64], got {tuple(q.shape)}, {tuple(k.shape)}, {tuple(v.shape)}")
+        if ds not in (1, 3) or any(t.stride(3) != ds for t in (q, k, v)):
+            raise RuntimeError("lg_attention: the last-dim stride of q, k and v is 1 or 3, the same in all")
+        Tq, Tk = q.shape[1], k.shape[1]
+        if not (1 <= Tq <= LG_MAX_N and 1 <= Tk <= LG_MAX_N):
+            raise RuntimeError(f"lg_attention: 1 <= T <= {LG_MAX_N}, got {Tq}, {Tk}")
+        nq, nk = _req(d["nq"], torch.int32), _req(d["nk"], torch.int32)
+        if nq.numel() != B or nk.numel() != B:
+            raise RuntimeError("lg_attention: nq and nk are int32 [B]")
+        out = d.get("out")
+        if out is None:
+            out = torch.empty(B, Tq, H * 64, device=q.device, dtype=torch.float32)
+        _lg_f32("lg_attention", out, contiguous=False)
+        if tuple(out.shape) != (B, Tq, H * 64) or out.stride(2) != 1:
+            raise RuntimeError(f"lg_attention: out is [B,Tq,{H * 64}] with a contiguous last dim, got {tuple(out.shape)}")
+        rp, rs = [], []
+        for key, T in (("rope_q", Tq), ("rope_k", Tk)):
+            r = d.get(key)
+            if r is None:
+                rp += [None, None]
+                rs.append(0)
+                continue
+            c, s = r
+            _lg_f32("lg_attention", c, s, contiguous=False)
+            if tuple(c.shape) != (B, T, 32) or c.shape != s.shape or c.stride()[1:] != (32, 1) or s.stride() != c.stride():
+                raise RuntimeError(f"lg_attention: {key} is (cos, sin), each a [B,T,32] view with contiguous rows, got {tuple(c.shape)}")
+            rp += [c.data_ptr(), s.data_ptr()]
+            rs.append(c.stride(0))
+        ptrs += [q.data_ptr(), k.data_ptr(), v.data_ptr(), out.data_ptr(), nq.data_ptr(), nk.data_ptr()] + rp
+        strides += [q.stride(0), q.stride(2), q.stride(1), k.stride(0), k.stride(2), k.stride(1), v.stride(0), v.stride(2), v.stride(1),
+                    out.stride(0), out.stride(1), rs[0], rs[1], Tq, Tk, 0]
+        outs.append(out)
+        keep += [nq, nk]
+    pa = (ctypes.c_void_p * len(ptrs))(*ptrs)
+    sa = (ctypes.c_int64 * len(strides))(*strides)
+    flops = sum(4.0 * B * H * d["q"].shape[1] * d["k"].shape[1] * 64 for d in dirs)
+    _timed("lg_attn_fwd", flops, lambda: _lib.call("vgpa_lg_attn_fwd", pa, sa, B, H, len(dirs), ds, float(q_premul), _stream()))
+    return outs
+
+
+def lg_posenc(kpts, counts, Wr, image_size=None, out=None):
+    """kpts [B,N,2], counts int32 [B], Wr [32,2], image_size [B,2] or None (then 1 + max - min of the sample's keypoints) -> (cos, sin), each [B,N,32]
+    (`out` = a pair of [B,N,32] views with contiguous rows to write into)"""
+    _lg_f32("lg_posenc", kpts, Wr, image_size)
+    _req(counts, torch.int32)
+    B, N = kpts.shape[:2]
+    if kpts.dim() != 3 or kpts.shape[2] != 2 or tuple(Wr.shape) != (32, 2) or counts.numel() != B or not 1 <= N <= LG_MAX_N or \
+            (image_size is not None and tuple(image_size.shape) != (B, 2)):
+        raise RuntimeError(f"lg_posenc: kpts [B,N,2], counts [B], Wr [32,2], image_size [B,2] | None, got {tuple(kpts.shape)}, {tuple(Wr.shape)}")
+    if out is None:
+        out = (torch.empty(B, N, 32, device=kpts.device, dtype=torch.float32), torch.empty(B, N, 32, device=kpts.device, dtype=torch.float32))
+    c, s = out
+    _lg_f32("lg_posenc", c, s, contiguous=False)
+    if tuple(c.shape) != (B, N, 32) or c.shape != s.shape or c.stride() != s.stride() or c.stride()[1:] != (32, 1):
+        raise RuntimeError("lg_posenc: out is a pair of [B,N,32] views with contiguous rows and equal strides")
+    _timed("lg_posenc", 8.0 * B * N * 32, lambda: _lib.call("vgpa_lg_posenc", kpts, counts, image_size, Wr, c, s, B, N, c.stride(0), _stream()), "byte")
+    return c, s
+
+
+def lg_ln_gelu(u, gamma, beta, seg, eps=1e-5, resid=None, resid_bias=None):
+    """u [B,R,512] -> gelu_erf(LayerNorm(u)) [B,R,512] on the rows below the counts of seg = (S0, c0, c1).  resid ([B,R,256] view with contiguous
+    rows, e.g. the left half of a [B,R,512] buffer) gets resid_bias [256] added in place: the bias of the GEMM that then accumulates into it."""
+    _lg_f32("lg_ln_gelu", u, gamma, beta, resid_bias)
+    B, R = u.shape[:2]
+    if u.dim() != 3 or u.shape[2] != 512 or gamma.numel() != 512 or beta.numel() != 512:
+        raise RuntimeError(f"lg_ln_gelu: u [B,R,512] with 512 weights and biases, got {tuple(u.shape)}")
+    S0, c0, c1 = _lg_seg("lg_ln_gelu", B, R, seg)
+    rs = 0
+    if resid is not None:
+        _lg_f32("lg_ln_gelu", resid, contiguous=False)
+        if tuple(resid.shape) != (B, R, 256) or resid.stride(2) != 1 or resid.stride(0) != R * resid.stride(1) or resid_bias is None or resid_bias.numel() != 256:
+            raise RuntimeError("lg_ln_gelu: resid is a [B,R,256] view with one row stride and resid_bias holds 256 values")
+        rs = resid.stride(1)
+    h = torch.empty_like(u)
+    _timed("lg_ln_gelu", 4096.0 * B * R, lambda: _lib.call("vgpa_lg_ln_gelu", u, gamma, beta, float(eps), h, resid, rs, resid_bias, B, R, S0, c0, c1, _stream()),
+           "byte")
+    return h
+
+
+def lg_confidence(x, w, bias, seg, thr=None, below=None, want_conf=True, want_z=False):
+    """x [B,R,256] view with one row stride; z = w . x + bias, conf = sigmoid(z) -> (conf [B,R] | None, z [B,R] | None).  With thr (a Python float,
+    compared in double) and below int32 [B] (zeroed by the caller): below[b] += the number of the sample's rows with conf < thr."""
+    _lg_f32("lg_confidence", x, contiguous=False)
+    _lg_f32("lg_confidence", w)
+    B, R = x.shape[:2]
+    if x.dim() != 3 or x.shape[2] != 256 or x.stride(2) != 1 or x.stride(0) != R * x.stride(1) or w.numel() != 256 or not (want_conf or want_z):
+        raise RuntimeError(f"lg_confidence: x is a [B,R,256] view with one row stride, w holds 256 values, got {tuple(x.shape)}")
+    S0, c0, c1 = _lg_seg("lg_confidence", B, R, seg)
+    if (thr is None) != (below is None) or (below is not None and _req(below, torch.int32).numel() != B):
+        raise RuntimeError("lg_confidence: thr and below (int32 [B]) come together")
+    conf = torch.zeros(B, R, device=x.device, dtype=torch.float32) if want_conf else None
+    z = torch.zeros(B, R, device=x.device, dtype=torch.float32) if want_z else None
+    _timed("lg_confidence", 1024.0 * B * R, lambda: _lib.call("vgpa_lg_confidence", x, x.stride(1), w, float(bias), conf, z, 0.0 if thr is None else float(thr),
+                                                                below, B, R, S0, c0, c1, _stream()), "byte")
+    return conf, z
+
+
+def lg_prune(conf, match, thr_conf, thr_keep, prune_min, x_in, x_out, rope_in, rope_out, ind_in, ind_out, prune, seg, counts_out, want_keep=False):
+    """Point pruning of every segment with more than prune_min rows: keep row i iff match[i] > thr_keep or conf[i] <= thr_conf (Python floats, compared
+    in double); other segments keep everything.  conf, match [B,R]; x_in / x_out [B,R,256] views of two different buffers with the same row stride;
+    rope_* = (cos, sin) [B,R,32]; ind_* int32 [B,R]; prune = (prune0 [B,P0], prune1 [B,P1] | None) int32, += 1 at the kept rows' ind;
+    counts_out = (c0_out, c1_out | None).  Ordered and stable.  -> the keep mask uint8 [B,R] by input row when want_keep."""
+    _lg_f32("lg_prune", conf, match, *rope_in, *rope_out)
+    _lg_f32("lg_prune", x_in, x_out, contiguous=False)
+    B, R = conf.shape
+    S0, c0, c1 = _lg_seg("lg_prune", B, R, seg)
+    for t in (x_in, x_out):
+        if tuple(t.shape) != (B, R, 256) or t.stride(2) != 1 or t.stride(0) != R * t.stride(1) or t.stride(1) != x_in.stride(1):
+            raise RuntimeError("lg_prune: x_in and x_out are [B,R,256] views with one and the same row stride")
+    if match.shape != conf.shape or any(tuple(t.shape) != (B, R, 32) for t in (*rope_in, *rope_out)) or any(_req(t, torch.int32).shape != conf.shape for t in (ind_in, ind_out)):
+        raise RuntimeError("lg_prune: conf, match, ind [B,R]; rotary tables [B,R,32]")
+    p0, p1 = prune
+    o0, o1 = counts_out
+    for t in (p0, p1, o0, o1):
+        if t is not None:
+            _req(t, torch.int32)
+    if (c1 is None) != (p1 is None) or (c1 is None) != (o1 is None) or p0.shape[0] != B or o0.numel() != B:
+        raise RuntimeError("lg_prune: prune and counts_out follow the segments")
+    keep = torch.zeros(B, R, device=conf.device, dtype=torch.uint8) if want_keep else None
+    _timed("lg_prune", 2.0 * 1280 * B * R,
+           lambda: _lib.call("vgpa_lg_prune", conf, match, float(thr_conf), float(thr_keep), int(prune_min), x_in, x_out, x_in.stride(1), rope_in[0], rope_in[1],
+                             rope_out[0], rope_out[1], ind_in, ind_out, p0, p1, p0.shape[1], 0 if p1 is None else p1.shape[1], B, R, S0, c0, c1, o0, o1, keep,
+                             _stream()), "byte")
+    return keep
+
+
+def lg_assign_workspace(B, Mmax, Nmax, device):
+    """the workspace of lg_assign as fp32 words, and its views: rmax, rlog, rbest, rarg [B,Mmax], cmax, clog, cbest, carg [B,Nmax] (the args as int32)"""
+    ws = torch.zeros(_lib.query("vgpa_lg_assign_workspace_bytes", B, Mmax, Nmax) // 4, device=device, dtype=torch.float32)
+    nr, nc = B * Mmax, B * Nmax
+    r = [ws[i * nr:(i + 1) * nr].view(B, Mmax) for i in range(4)]
+    c = [ws[4 * nr + i * nc:4 * nr + (i + 1) * nc].view(B, Nmax) for i in range(4)]
+    views = {"rmax": r[0], "rlog": r[1], "rbest": r[2], "rarg": r[3].view(torch.int32), "cmax": c[0], "clog": c[1], "cbest": c[2], "carg": c[3].view(torch.int32)}
+    return ws, views
+
+
+def lg_assign(sim, z0, z1, m, n, thr, ind0=None, ind1=None, M0=None, N0=None, want_scores=False, stages=7, workspace=None):
+    """LightGlue's assignment and filter_matches from sim [B,Mmax,Nmax], the matchability logits z0 [B,Mmax], z1 [B,Nmax] and the counts m, n int32 [B];
+    thr a Python float compared in double.  stages: 1 log-sum-exps, 2 argmax of the log score (ties to the lowest index), 4 matches; a later stage
+    alone reads what `workspace` (lg_assign_workspace) holds.  ind0 / ind1 int32 [B,Mmax] / [B,Nmax] map rows to the original indices of a side with
+    M0 / N0 points.  -> dict(matches0 [B,M0], matches1 [B,N0] int32, matching_scores0, matching_scores1, matches [B,M0,2] int32, scores [B,M0],
+    count int32 [B], log_assignment [B,Mmax+1,Nmax+1] | None, workspace)"""
+    _lg_f32("lg_assign", sim, z0, z1)
+    B, Mmax, Nmax = sim.shape
+    if tuple(z0.shape) != (B, Mmax) or tuple(z1.shape) != (B, Nmax) or _req(m, torch.int32).numel() != B or _req(n, torch.int32).numel() != B or \
+            not (1 <= Mmax <= LG_MAX_N and 1 <= Nmax <= LG_MAX_N) or (ind0 is None) != (ind1 is None):
+        raise RuntimeError(f"lg_assign: sim [B,M,N], z0 [B,M], z1 [B,N], counts [B], got {tuple(sim.shape)}, {tuple(z0.shape)}, {tuple(z1.shape)}")
+    M0, N0 = Mmax if M0 is None else int(M0), Nmax if N0 is None else int(N0)
+    if ind0 is not None and (tuple(_req(ind0, torch.int32).shape) != (B, Mmax) or tuple(_req(ind1, torch.int32).shape) != (B, Nmax)):
+        raise RuntimeError("lg_assign: ind0 [B,Mmax] and ind1 [B,Nmax] int32")
+    if M0 < Mmax or N0 < Nmax:
+        raise RuntimeError("lg_assign: M0 >= Mmax and N0 >= Nmax")
+    dev = sim.device
+    ws = lg_assign_workspace(B, Mmax, Nmax, dev)[0] if workspace is None else _req(workspace, torch.float32)
+    i32 = dict(device=dev, dtype=torch.int32)
+    out = {"matches0": torch.full((B, M0), -1, **i32), "matches1": torch.full((B, N0), -1, **i32),
+           "matching_scores0": torch.zeros(B, M0, device=dev), "matching_scores1": torch.zeros(B, N0, device=dev),
+           "matches": torch.zeros(B, M0, 2, **i32), "scores": torch.zeros(B, M0, device=dev), "count": torch.zeros(B, **i32),
+           "log_assignment": torch.zeros(B, Mmax + 1, Nmax + 1, device=dev) if want_scores else None, "workspace": ws}
+    _timed("lg_assign", 16.0 * sim.numel(),
+           lambda: _lib.call("vgpa_lg_assign", sim, z0, z1, m, n, B, Mmax, Nmax, float(thr), ind0, ind1, M0, N0, out["matches0"], out["matches1"],
+                             out["matching_scores0"], out["matching_scores1"], out["matches"], out["scores"], out["count"], out["log_assignment"], int(stages),
+                             ws, ws.numel() * 4, _stream()), "byte")
+    return out

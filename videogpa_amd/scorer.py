@@ -2,8 +2,8 @@
 (utils/projection_utils.py), `get_colored_pointcloud` (utils/pointcloud_utils.py), `Metric` / `MSEMetric`
 / `PSNRMetric` / `SSIMMetric` (metrics/base.py, metrics/mse.py), `compute_motion_score_vectorized` / `Consistency_Score`
 (metrics/consistency_score.py) and the geometry half of `EpipolarMetric` (metrics/epipolar.py:161-213).
-Kernels: videogpa_amd/csrc/{scorer,scorer2,scorer_ssim}.hip.  Networks (LPIPS-VGG, SuperPoint in front of the caller's LightGlue, VGGT / DA3
-backbones) are passed in: the project's own device modules, or third-party callables / precomputed matches (SIFT, LightGlue's transformer)."""
+Kernels: videogpa_amd/csrc/{scorer,scorer2,scorer_ssim}.hip.  Networks (LPIPS-VGG, SuperPoint and LightGlue, VGGT / DA3 backbones) are passed in:
+the project's own device modules, or third-party callables / precomputed matches (SIFT)."""
 from abc import ABC, abstractmethod
 from typing import Any
 
@@ -339,7 +339,8 @@ def _rbd(d):
 class LightGlueMatcher:
     """The reference's LightGlueMatcher (metrics/epipolar.py:72-139) with the two networks passed in.  `extractor` is SuperPoint on the device
     (videogpa_amd.superpoint.SuperPoint: gray conversion, / 255, resize, network, NMS, selection and descriptors all run there);
-    `matcher({'image0': feats0, 'image1': feats1}) -> {'matches': ...}` is the caller's LightGlue, the one third-party piece left.
+    `matcher({'image0': feats0, 'image1': feats1}) -> {'matches': ...}` is LightGlue on the device (videogpa_amd.lightglue.LightGlue; `from_pretrained`
+    below builds both networks from local files) or any callable of that form.  A matcher with `match_batch` gets the whole clip in one call.
     Unlike the reference, nothing is swallowed: an exception inside either network reaches the caller."""
 
     def __init__(self, min_matches: int = 20, device: str = "cuda", extractor=None, matcher=None):
@@ -350,6 +351,14 @@ class LightGlueMatcher:
             from .superpoint import SuperPoint
             extractor = SuperPoint(max_num_keypoints=2048).to(device)                 # raises: trained weights are local files, never fetched
         self.min_matches, self.device, self.extractor, self.matcher = min_matches, device, extractor, matcher
+
+    @classmethod
+    def from_pretrained(cls, path, min_matches: int = 20, device: str = "cuda"):
+        """both networks from one LOCAL directory: superpoint_v1.pth and superpoint_lightglue.pth (or their .safetensors forms); nothing is fetched"""
+        from .lightglue import LightGlue
+        from .superpoint import SuperPoint
+        return cls(min_matches=min_matches, device=device, extractor=SuperPoint.from_pretrained(path, max_num_keypoints=2048).to(device),
+                   matcher=LightGlue.from_pretrained(path).to(device))
 
     @staticmethod
     def _frames_u8(frames):
@@ -369,9 +378,10 @@ class LightGlueMatcher:
             x = x.expand(-1, -1, -1, 3)                                                # the gray formula maps (g, g, g) to g exactly
         return x.contiguous()
 
-    def _pair(self, feats0, feats1):
-        with torch.no_grad():
-            matches01 = self.matcher({"image0": feats0, "image1": feats1})
+    def _pair(self, feats0, feats1, matches01=None):
+        if matches01 is None:
+            with torch.no_grad():
+                matches01 = self.matcher({"image0": feats0, "image1": feats1})
         f0, f1, m01 = _rbd(feats0), _rbd(feats1), _rbd(matches01)
         matches = m01["matches"]
         k0, k1 = f0["keypoints"][matches[..., 0]], f1["keypoints"][matches[..., 1]]
@@ -392,12 +402,16 @@ class LightGlueMatcher:
     def match_clip(self, frames):
         """[(pts1, pts2)] of the consecutive pairs, every frame extracted once (the reference extracts every inner frame twice)"""
         feats = self.extractor.extract_clip(self._frames_u8(frames))
+        if hasattr(self.matcher, "match_batch"):                                       # all pairs of the clip as one padded batch
+            with torch.no_grad():
+                m = self.matcher.match_batch(feats)
+            return [self._pair(feats[i], feats[i + 1], m[i])[:2] for i in range(len(feats) - 1)]
         return [self._pair(feats[i], feats[i + 1])[:2] for i in range(len(feats) - 1)]
 
 
 class EpipolarMetric(Metric):
     """Video-level epipolar consistency (metrics/epipolar.py:142-232).  `matcher(frame_i, frame_j) -> (pts1, pts2)` is the front end:
-    `LightGlueMatcher` above (SuperPoint on the device, the caller's LightGlue) or any callable; the 8-point + Sampson geometry runs on device."""
+    `LightGlueMatcher` above (SuperPoint and LightGlue on the device) or any callable; the 8-point + Sampson geometry runs on device."""
 
     def __init__(self, descriptor_type: str = "sift", ratio_thresh: float = 0.75, min_matches: int = 20, device: str = None, matcher=None):
         """Reference signature (metrics/epipolar.py:146-158) + `matcher`: the reference builds a cv2-SIFT or LightGlue matcher from

@@ -510,6 +510,27 @@ int32_t vgpa_da3_pose_decode(const float* pose_enc, int64_t n, float image_h, fl
 int32_t vgpa_dualdpt_aux_tail_f32(const float* x, const float* xtab, const float* ytab, const float* w1_packed, const float* b1,
                                   const float* ln_w, const float* ln_b, float eps, const float* w2, const float* b2, float* preds, float* conf,
                                   int64_t N, int64_t h, int64_t w, int64_t C, int32_t output_dim, vgpa_stream_t stream);
+/* DepthAnything3Net._process_ray_pose_estimation (depth_anything_3/model/da3.py:181-201, utils/ray_utils.py:20-93,313-421; csrc/da3_ray_pose.hip): cameras
+ * from the ray map by confidence-weighted RANSAC of a homography.  ray fp32 [V,N,6] with N = ph * pw, conf fp32 [V,N]; gx [pw] / gy [ph] are the plane
+ * grid's coordinates (the source points, z = 1).  All arithmetic behind the fp32 inputs is fp64; no input is written; two calls on one input are
+ * bit-identical.
+ *   ray_weights  wm [V,N] = conf where |ray z| > z_threshold (strict, compared in fp32), else 0: the weights every later step and the caller's sort use.
+ *   ray_ransac   cand int32 [V,n_sample]: point indices by descending wm; sample_idx int32 [n_iter,8]: positions in cand, one table for every view
+ *                (an entry outside [0, n_sample) or a candidate outside [0, N) makes that hypothesis score 0).  Fits n_iter <= 128 homographies per
+ *                view (smallest eigenvector of the 9 x 9 weighted DLT normal matrix, H / H[2,2]), scores each by the summed wm of the points whose
+ *                reprojection error is < reproj_threshold (a non-finite error is an outlier) -> best int32 [V] (largest score, lowest index on a
+ *                tie), inlier uint8 [V,N] of the winner, n_inliers int32 [V].  workspace: vgpa_da3_ray_pose_workspace_bytes(V, N, n_iter), 8-byte aligned.
+ *   ray_refit    use uint8 [V,N] marks the points the refit reads -> H [V,3,3] (refitted, / H[2,2]), R [V,3,3], T [V,3] (mean of ray[3:] under wm over
+ *                ALL points), focal [V,2] and pp [V,2] (normalised, image size 2), ext [V,3,4] = rows :3 of the inverse of [R|T], intr [V,3,3] in
+ *                pixels of image_h x image_w, n_used int32 [V] = the number of marked points. */
+size_t vgpa_da3_ray_pose_workspace_bytes(int64_t V, int64_t N, int64_t n_iter);
+int32_t vgpa_da3_ray_weights(const float* ray, const float* conf, int64_t V, int64_t N, float z_threshold, float* wm, vgpa_stream_t stream);
+int32_t vgpa_da3_ray_ransac(const float* ray, const float* wm, const float* gx, const float* gy, const int32_t* cand, const int32_t* sample_idx, int64_t V,
+                            int64_t ph, int64_t pw, int64_t n_sample, int64_t n_iter, float z_threshold, double reproj_threshold, int32_t* best,
+                            uint8_t* inlier, int32_t* n_inliers, void* workspace, size_t workspace_bytes, vgpa_stream_t stream);
+int32_t vgpa_da3_ray_refit(const float* ray, const float* wm, const float* gx, const float* gy, const uint8_t* use, int64_t V, int64_t ph, int64_t pw,
+                           float z_threshold, float image_h, float image_w, float* H, float* R, float* T, float* focal, float* pp, float* ext, float* intr,
+                           int32_t* n_used, vgpa_stream_t stream);
 
 /* ---- CogVideoX VAE encoder on one frame (diffusers' autoencoder_kl_cogvideox.py; videogpa_amd/vae.py, csrc/vae.hip): fp32, NHWC, forward only ----
  * The 3x3 convolution of vgpa_conv3x3_f32 with its zero padding given per side: pad_lo rows / columns in front of index 0, pad_hi behind the last

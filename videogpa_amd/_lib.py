@@ -110,6 +110,10 @@ SIGNATURES = {
     "vgpa_da3_tap": (I32, [P, P, P, P, F32, P, P, P, I64, I64, I64, I64, P]),
     "vgpa_da3_pose_decode": (I32, [P, I64, F32, F32, P, P, P]),
     "vgpa_dualdpt_aux_tail_f32": (I32, [P, P, P, P, P, P, P, F32, P, P, P, P, I64, I64, I64, I64, I32, P]),
+    "vgpa_da3_ray_pose_workspace_bytes": (SZ, [I64, I64, I64]),
+    "vgpa_da3_ray_weights": (I32, [P, P, I64, I64, F32, P, P]),
+    "vgpa_da3_ray_ransac": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, F32, F64, P, P, P, P, SZ, P]),
+    "vgpa_da3_ray_refit": (I32, [P, P, P, P, P, I64, I64, I64, F32, F32, F32, P, P, P, P, P, P, P, P, P]),
     "vgpa_conv3x3_pad_f32": (I32, [P, P, P, P, P, I64, I64, I64, I64, I64, I64, I32, I32, P]),
     "vgpa_conv3x3x3_causal_f32": (I32, [P, P, P, P, P, P, I64, I64, I64, I64, I64, I64, P]),
     "vgpa_vae_downsample_f32": (I32, [P, P, P, P, I64, I64, I64, I64, I64, I64, I32, P]),

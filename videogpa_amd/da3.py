@@ -10,7 +10,8 @@ runs for `depth` / `depth_conf` / `ray` / `ray_conf` / `extrinsics` / `intrinsic
     DualDPT                 depth_anything_3/model/dualdpt.py:30-364, model/dpt.py (_make_scratch, _make_fusion_block): the head shared with VGGT
                             (videogpa_amd/dpt.py, fp32 on the convolution kernels of csrc/vggt_heads.hip) plus the auxiliary branch, whose tail is
                             csrc/dualdpt.hip
-    DepthAnything3Net       da3.py:40-221 without cam_enc, the GS heads, ray-pose and exported feature layers
+    DepthAnything3Net       da3.py:40-221 without cam_enc, the GS heads and exported feature layers; `use_ray_pose` (da3.py:181-201, utils/ray_utils.py) is
+                            ops.da3_ray_pose on csrc/da3_ray_pose.hip
     DA3Cameras              backbone + camera decoder only, for callers that want the cameras and bring no head
     DepthAnything3          depth_anything_3/api.py:48-446: `inference(frames of any size)` -> `Prediction`; the input processing in front of the network is
                             videogpa_amd/da3_input.py on csrc/da3_input.hip
@@ -335,6 +336,9 @@ class DualDPT(DPTBase):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the whole network
+_RAY_POSE_NEEDS_GPU = ("use_ray_pose: the ray-based pose estimation runs on the HIP kernels only (ops.da3_ray_pose); this package has no CPU fallback, "
+                       "so the module and its input must be on a GPU")
+
 # depth_anything_3/configs/da3-{small,base,large}.yaml: the presets whose head is DualDPT on a vits / vitb / vitl encoder
 _PRESETS = {
     "da3-small": dict(net=dict(name="vits", out_layers=[5, 7, 9, 11], alt_start=4, qknorm_start=4, rope_start=4, cat_token=True),
@@ -350,8 +354,10 @@ class DepthAnything3Net(nn.Module):
     """depth_anything_3/model/da3.py:40-221: `forward(x [B,S,3,H,W] normalised, H and W multiples of 14, ..., aux=True)` -> the head's dict (depth,
     depth_conf and, with aux, ray, ray_conf) plus `extrinsics [B,S,3,4]` (world-to-camera) / `intrinsics [B,S,3,3]` when there is a `cam_dec`.  The
     backbone runs in whatever precision the caller set (bf16 autocast in the scorer); head, camera decoder and pose decoding run with autocast off.
-    Not built: cam_enc (given extrinsics / intrinsics), the GS heads, ray-pose and exported feature layers.  The input resizing of api.py is
-    `DepthAnything3` below, not this class."""
+    `use_ray_pose=True` (da3.py:181-201) runs the head with its auxiliary branch whatever `aux` says and takes the cameras from the ray map instead
+    of `cam_dec`: ops.da3_ray_pose, whose random draws come from `ray_pose_generator` (None: the device's default generator).  Not built: cam_enc
+    (given extrinsics / intrinsics), the GS heads and exported feature layers.  The input resizing of api.py is `DepthAnything3` below, not this
+    class."""
 
     PATCH_SIZE = 14
     SKIPPED_PREFIXES = ("cam_enc.", "gs_head.", "gs_adapter.")
@@ -396,21 +402,23 @@ class DepthAnything3Net(nn.Module):
         return sorted(met)
 
     def forward(self, x, extrinsics=None, intrinsics=None, export_feat_layers=(), infer_gs=False, use_ray_pose=False,
-                ref_view_strategy="saddle_balanced", aux=True):
+                ref_view_strategy="saddle_balanced", aux=True, ray_pose_generator=None):
         if extrinsics is not None or intrinsics is not None:
             raise NotImplementedError("given extrinsics / intrinsics need cam_enc, which is not built")
         if infer_gs:
             raise NotImplementedError("infer_gs: the Gaussian-splatting heads are not built")
-        if use_ray_pose:
-            raise NotImplementedError("use_ray_pose: the ray-based pose estimation is not built (cameras come from cam_dec)")
+        if use_ray_pose and not x.is_cuda:
+            raise NotImplementedError(_RAY_POSE_NEEDS_GPU)
         if export_feat_layers is not None and len(export_feat_layers):
             raise NotImplementedError("export_feat_layers: auxiliary feature maps are not built (no VideoGPA path asks for them)")
         _forward_only(self, x)
         feats, _ = self.backbone(x, cam_token=None, ref_view_strategy=ref_view_strategy)
         H, W = x.shape[-2:]
         with torch.autocast(x.device.type, enabled=False):
-            output = self.head(feats, H, W, patch_start_idx=0, aux=aux)
-            if self.cam_dec is not None:
+            output = self.head(feats, H, W, patch_start_idx=0, aux=aux or use_ray_pose)
+            if use_ray_pose:
+                output.extrinsics, output.intrinsics, _ = ops.da3_ray_pose(output.ray, output.ray_conf, (H, W), generator=ray_pose_generator)
+            elif self.cam_dec is not None:
                 output.extrinsics, output.intrinsics = decode_cameras(self.cam_dec(feats[-1][1]), (H, W))
         return output
 
@@ -431,18 +439,22 @@ class Prediction:
 class DepthAnything3(nn.Module):
     """depth_anything_3/api.py:48-446 over `DepthAnything3Net`: `inference(frames)` takes uint8 frames of ANY size -- InputProcessor on the device
     (videogpa_amd/da3_input.py: cv2-style area / cubic resizing to `process_res`, centre crop, normalisation), the network under no_grad + bf16
-    autocast with aux=False, and a `Prediction`.  `.model` is the network, so a DA3 checkpoint's `model.*` keys load by name.  Not built, and refused
-    with NotImplementedError as the network refuses them: caller-given extrinsics / intrinsics (cam_enc, Umeyama alignment), infer_gs, use_ray_pose,
-    exports.  Weights come from local files only."""
+    autocast with aux=False, and a `Prediction`.  `.model` is the network, so a DA3 checkpoint's `model.*` keys load by name.  `use_ray_pose=True`
+    takes the cameras from the ray map (the auxiliary branch runs for it) instead of the camera decoder.  Not built, and refused with
+    NotImplementedError as the network refuses them: caller-given extrinsics / intrinsics (cam_enc, Umeyama alignment), infer_gs, exports; and
+    use_ray_pose on a module that is not on a GPU.  Weights come from local files only."""
 
-    def __init__(self, model_name="da3-large", model=None, process_res=504, process_res_method="upper_bound_resize"):
-        """`model`: a ready `DepthAnything3Net` (any configuration) instead of the preset `model_name` names.  `process_res` / `process_res_method`:
-        what `inference` uses when its caller names none -- `VideoProcessor` calls `inference(frames)` bare, as the reference does, so a scorer that
-        wants another processing size than upstream's 504 sets it here"""
+    def __init__(self, model_name="da3-large", model=None, process_res=504, process_res_method="upper_bound_resize", use_ray_pose=False,
+                 ray_pose_generator=None):
+        """`model`: a ready `DepthAnything3Net` (any configuration) instead of the preset `model_name` names.  `process_res` / `process_res_method` /
+        `use_ray_pose`: what `inference` uses when its caller names none -- `VideoProcessor` calls `inference(frames)` bare, as the reference does, so
+        a scorer that wants another processing size than upstream's 504, or the ray-based cameras, sets it here.  `ray_pose_generator`: the
+        torch.Generator the ray-pose RANSAC draws from (None: the device's default generator)"""
         super().__init__()
         from .da3_input import InputProcessor
         self.model_name = model_name
         self.process_res, self.process_res_method = process_res, process_res_method
+        self.use_ray_pose, self.ray_pose_generator = bool(use_ray_pose), ray_pose_generator
         self.model = (model if model is not None else DepthAnything3Net.from_preset(model_name)).eval()
         self.input_processor = InputProcessor
         self.device = None
@@ -455,23 +467,29 @@ class DepthAnything3(nn.Module):
     def load_state_dict(self, state_dict, strict=True, **kw):
         return self.model.load_state_dict(state_dict, strict=strict, **kw)
 
-    def forward(self, image, extrinsics=None, intrinsics=None, export_feat_layers=None, infer_gs=False, use_ray_pose=False,
+    def forward(self, image, extrinsics=None, intrinsics=None, export_feat_layers=None, infer_gs=False, use_ray_pose=None,
                 ref_view_strategy="saddle_balanced"):
-        """api.py:99-131: image [B,N,3,H,W] normalised, on the model's device -> the network's dict (depth, depth_conf, extrinsics, intrinsics)"""
+        """api.py:99-131: image [B,N,3,H,W] normalised, on the model's device -> the network's dict (depth, depth_conf, extrinsics, intrinsics; with
+        use_ray_pose also ray, ray_conf).  use_ray_pose None: the instance's default"""
+        use_ray_pose = self.use_ray_pose if use_ray_pose is None else bool(use_ray_pose)
         with torch.no_grad(), torch.autocast(image.device.type, dtype=torch.bfloat16, enabled=image.device.type == "cuda"):
-            return self.model(image, extrinsics, intrinsics, export_feat_layers or (), infer_gs, use_ray_pose, ref_view_strategy, aux=False)
+            if not use_ray_pose:
+                return self.model(image, extrinsics, intrinsics, export_feat_layers or (), infer_gs, False, ref_view_strategy, aux=False)
+            return self.model(image, extrinsics, intrinsics, export_feat_layers or (), infer_gs, True, ref_view_strategy, aux=True,
+                              ray_pose_generator=self.ray_pose_generator)
 
-    def inference(self, image, extrinsics=None, intrinsics=None, align_to_input_ext_scale=True, infer_gs=False, use_ray_pose=False,
+    def inference(self, image, extrinsics=None, intrinsics=None, align_to_input_ext_scale=True, infer_gs=False, use_ray_pose=None,
                   ref_view_strategy="saddle_balanced", render_exts=None, render_ixts=None, render_hw=None, process_res=None,
                   process_res_method=None, export_dir=None, export_format="mini_npz", export_feat_layers=None, **export_kwargs):
         """api.py:133-273: frames (a list of uint8 [H,W,3] or uint8 [T,H,W,3], host or device) -> Prediction at the processed size.  `process_res` /
-        `process_res_method` default to the instance's (504, "upper_bound_resize" unless the constructor was told otherwise)"""
+        `process_res_method` / `use_ray_pose` default to the instance's (504, "upper_bound_resize", False unless the constructor was told otherwise)"""
+        use_ray_pose = self.use_ray_pose if use_ray_pose is None else bool(use_ray_pose)
         if extrinsics is not None or intrinsics is not None:
             raise NotImplementedError("given extrinsics / intrinsics need cam_enc and the Umeyama pose alignment, which are not built")
         if infer_gs:
             raise NotImplementedError("infer_gs: the Gaussian-splatting heads are not built")
-        if use_ray_pose:
-            raise NotImplementedError("use_ray_pose: the ray-based pose estimation is not built (cameras come from cam_dec)")
+        if use_ray_pose and self._get_model_device().type != "cuda":
+            raise NotImplementedError(_RAY_POSE_NEEDS_GPU)
         if export_dir is not None or render_exts is not None or render_ixts is not None or render_hw is not None:
             raise NotImplementedError("export_dir / export_format / render_*: the export formats are host I/O outside the on-device path")
         if export_feat_layers is not None and len(export_feat_layers):
@@ -479,7 +497,7 @@ class DepthAnything3(nn.Module):
         device = self._get_model_device()
         x, _, _, processed = self.input_processor(device).process(image, None, None, self.process_res if process_res is None else process_res,
                                                                   self.process_res_method if process_res_method is None else process_res_method)
-        out = self.forward(x, ref_view_strategy=ref_view_strategy)
+        out = self.forward(x, use_ray_pose=use_ray_pose, ref_view_strategy=ref_view_strategy)
         cams = {k: out[k].squeeze(0) if out.get(k) is not None else None for k in ("extrinsics", "intrinsics")}
         return Prediction(depth=out["depth"].squeeze(0), conf=out["depth_conf"].squeeze(0), processed_images=processed, **cams)
 

@@ -2059,6 +2059,104 @@ def da3_pose_decode(pose_enc, image_size_hw):
     return ext, intr
 
 
+# ray-based cameras (csrc/da3_ray_pose.hip; depth_anything_3/utils/ray_utils.py:313-432): upstream's constants
+DA3_RAY_N_ITER, DA3_RAY_SAMPLES, DA3_RAY_SAMPLE_RATIO, DA3_RAY_MAX_INLIERS, DA3_RAY_Z_THRESHOLD = 100, 8, 0.3, 8000, 1e-4
+_DA3_RAY_GRIDS = {}
+
+
+def da3_ray_grid(ph, pw):
+    """The source points of the ray-pose homography: the identity camera's plane grid of `unproject_depth(..., ixt_normalized=True)` (utils/geometry.py:
+    461-487 through the inverse of K = [[1,0,1],[0,1,1],[0,0,1]]) -> host fp32 (x [pw], y [ph]), cell centres in (-1, 1); z is 1.  A host fp32 linspace
+    minus 1, which is bit for bit what upstream's CPU run builds."""
+    axis = lambda n: torch.linspace(-(1 - 1 / n) + 1.0, (1 - 1 / n) + 1.0, n, dtype=torch.float32) - 1.0
+    return axis(pw), axis(ph)
+
+
+def da3_ray_sample_table(n_sample, generator=None, device=None, n_iter=DA3_RAY_N_ITER):
+    """The RANSAC sample table: int32 [n_iter, 8] on `device`, every row 8 distinct positions in [0, n_sample) drawn uniformly (the 8 largest of n_sample
+    uniform numbers: the first 8 of a random permutation, which is what upstream's randperm(n_sample)[:8] per row is) from `generator`, on the
+    generator's own device; None: the default generator of `device`"""
+    if n_sample < DA3_RAY_SAMPLES:
+        raise ValueError(f"da3_ray_sample_table: {DA3_RAY_SAMPLES} distinct samples need n_sample >= {DA3_RAY_SAMPLES}, got {n_sample}")
+    src = generator.device if generator is not None else device
+    keys = torch.rand(n_iter, n_sample, generator=generator, device=src)
+    return keys.topk(DA3_RAY_SAMPLES, dim=1).indices.to(device=device, dtype=torch.int32).contiguous()
+
+
+def da3_ray_pose(ray, ray_conf, image_hw, sample_idx=None, generator=None, reproj_threshold=0.2):
+    """DepthAnything3Net._process_ray_pose_estimation (da3.py:181-201 over ray_utils.get_extrinsic_from_camray): ray fp32 [B,S,ph,pw,6] and ray_conf fp32
+    [B,S,ph,pw] of the auxiliary DualDPT branch -> (extrinsics fp32 [B,S,3,4] world-to-camera, intrinsics fp32 [B,S,3,3] in pixels of image_hw, info).
+    Per view: the top max(8, int(0.3 N)) points by masked confidence (ties: lower index first) are the candidates, `sample_idx` (integer [n_iter, 8]
+    positions among them; None: da3_ray_sample_table from `generator`) picks 8 per hypothesis, the hypothesis with the largest inlier weight wins and
+    is refitted on its inliers -- on a random 8000 of the top 95 % by weight when there are more, drawn from `generator`.  Neither input is written
+    (upstream zeroes the masked confidences in place; their effect on T is reproduced).  info: R [B,S,3,3], T [B,S,3], focal and pp [B,S,2]
+    (normalised), H [B,S,3,3] (the refitted homography), best, n_inliers, n_used int32 [B,S], sample_idx int32 [n_iter,8].  Reads n_inliers back once;
+    a view with fewer than 4 inliers raises ValueError, as upstream."""
+    _req(ray, torch.float32)
+    _req(ray_conf, torch.float32)
+    if ray.dim() != 5 or ray.shape[-1] != 6 or tuple(ray_conf.shape) != tuple(ray.shape[:-1]) or ray.numel() == 0:
+        raise RuntimeError(f"da3_ray_pose: ray [B,S,ph,pw,6] and ray_conf [B,S,ph,pw], got {tuple(ray.shape)} and {tuple(ray_conf.shape)}")
+    if torch.is_grad_enabled() and (ray.requires_grad or ray_conf.requires_grad):
+        raise RuntimeError("da3_ray_pose is forward only: call it under torch.no_grad()")
+    B, S, ph, pw, _ = ray.shape
+    V, N, dev = B * S, ph * pw, ray.device
+    if N < DA3_RAY_SAMPLES:
+        raise RuntimeError(f"da3_ray_pose: a ray map of {N} points cannot give {DA3_RAY_SAMPLES} samples")
+    n_sample = max(DA3_RAY_SAMPLES, int(N * DA3_RAY_SAMPLE_RATIO))
+    if sample_idx is None:
+        sample_idx = da3_ray_sample_table(n_sample, generator, dev)
+    else:
+        if sample_idx.dim() != 2 or sample_idx.shape[1] != DA3_RAY_SAMPLES or sample_idx.is_floating_point():
+            raise RuntimeError(f"da3_ray_pose: sample_idx is an integer table [n_iter, {DA3_RAY_SAMPLES}], got {tuple(sample_idx.shape)} {sample_idx.dtype}")
+        sample_idx = sample_idx.to(device=dev, dtype=torch.int32).contiguous()
+    n_iter = sample_idx.shape[0]
+    key = (ph, pw, str(dev))
+    if key not in _DA3_RAY_GRIDS:
+        if len(_DA3_RAY_GRIDS) > 16:
+            _DA3_RAY_GRIDS.clear()
+        _DA3_RAY_GRIDS[key] = tuple(t.to(dev) for t in da3_ray_grid(ph, pw))
+    gx, gy = _DA3_RAY_GRIDS[key]
+    z_thr, H, W = DA3_RAY_Z_THRESHOLD, *image_hw
+
+    wm = torch.empty(V, N, device=dev, dtype=torch.float32)
+    _timed("da3_ray_weights", 32.0 * V * N, lambda: _lib.call("vgpa_da3_ray_weights", ray, ray_conf, V, N, z_thr, wm, _stream()), "byte")
+    order = torch.sort(wm, dim=1, descending=True, stable=True).indices                       # ties: the lower index first
+    cand = order[:, :n_sample].to(torch.int32).contiguous()
+    ws_bytes = _lib.query("vgpa_da3_ray_pose_workspace_bytes", V, N, n_iter)
+    if ws_bytes == 0:
+        raise RuntimeError(f"da3_ray_pose: {V} views x {N} points x {n_iter} hypotheses is outside what the kernels take (n_iter <= 128)")
+    ws = torch.empty(ws_bytes, device=dev, dtype=torch.uint8)
+    best = torch.empty(V, device=dev, dtype=torch.int32)
+    n_inl = torch.empty(V, device=dev, dtype=torch.int32)
+    inlier = torch.empty(V, N, device=dev, dtype=torch.uint8)
+    _timed("da3_ray_ransac", 30.0 * V * n_iter * N,
+           lambda: _lib.call("vgpa_da3_ray_ransac", ray, wm, gx, gy, cand, sample_idx, V, ph, pw, n_sample, n_iter, z_thr, float(reproj_threshold), best,
+                             inlier, n_inl, ws, ws_bytes, _stream()))
+    counts = n_inl.tolist()                                    # the one read-back: the refit's subset sizes are host arithmetic, as upstream's
+    if min(counts) < 4:
+        raise ValueError("At least 4 points are required to compute homography.")
+    use = inlier
+    if max(counts) > DA3_RAY_MAX_INLIERS:                      # a random 8000 of the top 95 % by weight (ray_utils.py:402-411), view after view
+        use = inlier.clone()
+        for v, n in enumerate(counts):
+            if n <= DA3_RAY_MAX_INLIERS:
+                continue
+            keep_len = max(int(n * 0.95), DA3_RAY_MAX_INLIERS)
+            by_weight = torch.sort(torch.where(inlier[v].bool(), wm[v], wm.new_tensor(float("-inf"))), descending=True, stable=True).indices[:keep_len]
+            perm = torch.randperm(keep_len, generator=generator, device=generator.device if generator is not None else dev)[:DA3_RAY_MAX_INLIERS]
+            use[v].zero_()
+            use[v, by_weight[perm.to(dev)]] = 1
+    out = {k: torch.empty(B, S, *shape, device=dev, dtype=torch.float32)
+           for k, shape in (("H", (3, 3)), ("R", (3, 3)), ("T", (3,)), ("focal", (2,)), ("pp", (2,)), ("extrinsics", (3, 4)), ("intrinsics", (3, 3)))}
+    n_used = torch.empty(V, device=dev, dtype=torch.int32)
+    _timed("da3_ray_refit", 32.0 * V * N,
+           lambda: _lib.call("vgpa_da3_ray_refit", ray, wm, gx, gy, use, V, ph, pw, z_thr, float(H), float(W), out["H"], out["R"], out["T"], out["focal"],
+                             out["pp"], out["extrinsics"], out["intrinsics"], n_used, _stream()), "byte")
+    ext, intr = out.pop("extrinsics"), out.pop("intrinsics")
+    out.update(best=best.view(B, S), n_inliers=n_inl.view(B, S), n_used=n_used.view(B, S), sample_idx=sample_idx)
+    return ext, intr, out
+
+
 # ---- T5 encoder between its GEMMs (csrc/t5.hip): forward only -------------------------------------------------------------------------------
 T5_MAX_S = 512
 
